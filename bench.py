@@ -4,6 +4,15 @@ n=4096 d=256 k=1024 fp32, fixed step 1/L, through the C ABI, one process per GPU
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload fista|em|c3|conv|cd] [--scaling strong|weak]
                     [--shape c4|c5] [--dtype bf16|f32] [--rows R] [--backend nccl|gloo] [--share-gpu]
+                    [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the K steps and prints the headline line (value, ms_per_step, the roofline of
+the timed steps).  --full adds everything else this file measures or checks, each in timed regions of its own: the
+CPU baseline, the time-to-tol legs, the per-shard timings, the ISTA / Lipschitz / lr='auto' / sustained legs, the
+weak-scaling figure at N > 1 and the objective of the fista workload against the reference's answer.
+--dump-outputs DIR: after the timed steps, what the last timed step returned is written as DIR/<name>.npy (float32 /
+  float64, at most 64 MB in all: a larger array is cut to a fixed, seeded sample of its rows, whose indices are written
+  beside it as DIR/<name>_rows.npy).  The inputs are seeded: the same arguments give the same inputs on every run.
 
 --workload fista (default): a "step" is one sparse_encode solve of --iters FISTA iterations
   (default 100, the count BASELINE.md's config-2 timing uses), inputs resident in HBM, tol=0.
@@ -274,9 +283,10 @@ class Ranks:
             self.dist.destroy_process_group()
 
 
-def timed_steps(ranks, step, steps, warmup, events=True):
+def timed_steps(ranks, step, steps, warmup, events=True, last=None):
     """W untimed warm-up steps, then exactly K steps bracketed by barrier + synchronize on both
-    sides; returns (max-over-ranks seconds, sorted per-step device ms on this rank)."""
+    sides; returns (max-over-ranks seconds, sorted per-step device ms on this rank).  `last` (a dict): receives
+    what the last timed step returned, under "out"."""
     import torch
     for _ in range(warmup):
         step()
@@ -287,13 +297,42 @@ def timed_steps(ranks, step, steps, warmup, events=True):
     t0 = time.perf_counter()
     if events:
         ev[0].record()
+    res = None
     for i in range(steps):
-        step()
+        res = step()
     if events:
         ev[1].record()
     ranks.sync()
     elapsed = ranks.max(time.perf_counter() - t0)
+    if last is not None:
+        last["out"] = res
     return elapsed, ([ev[0].elapsed_time(ev[1]) / steps] if events else [])
+
+
+MAX_DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(args, rank, world, arrays):
+    """--dump-outputs DIR: write {name: tensor} as DIR/<name>.npy in float32 (float64 stays float64), rank-suffixed at
+    N > 1.  An array over its share of the 64 MB is cut to a fixed, seeded sample of its rows (indices in
+    DIR/<name>_rows.npy)."""
+    if not args.dump_outputs:
+        return
+    import numpy as np
+    import torch
+    os.makedirs(args.dump_outputs, exist_ok=True)
+    share = MAX_DUMP_BYTES // max(1, len(arrays))
+    for name, t in arrays.items():
+        t = torch.as_tensor(t).detach()
+        t = t.to("cpu", torch.float64 if t.dtype == torch.float64 else torch.float32)
+        suffix = "" if world == 1 else ".rank%d" % rank
+        if t.numel() * t.element_size() > share:
+            row_bytes = max(1, (t.numel() // max(1, t.shape[0])) * t.element_size())
+            keep = max(1, share // row_bytes)
+            rows = torch.randperm(t.shape[0], generator=torch.Generator().manual_seed(0))[:keep].sort().values
+            t = t[rows]
+            np.save(os.path.join(args.dump_outputs, name + "_rows" + suffix + ".npy"), rows.double().numpy())
+        np.save(os.path.join(args.dump_outputs, name + suffix + ".npy"), t.contiguous().numpy())
 
 
 # --------------------------------------------------------------------------------------
@@ -318,19 +357,22 @@ def run_fista(args, ranks):
 
     n_rows = args.rows
     results = {}
-    modes = ["strong"] if world == 1 else ["strong", "weak"]
+    main_mode = args.scaling if world > 1 else "strong"
+    # the other scaling figure of an N > 1 run has a timed region of its own: --full
+    modes = ["strong", "weak"] if (world > 1 and args.full) else [main_mode]
     for mode in modes:
         rows = n_rows // world if mode == "strong" else n_rows
         if mode == "strong" and n_rows % world:
             raise SystemExit("bench.py: %d rows do not split over %d ranks" % (n_rows, world))
         X, W, Xg, Wg, z0, solve = shard_solver(rows * world, rows)
-        elapsed, kern_ms = timed_steps(ranks, solve, args.steps, args.warmup)
+        last = {}
+        elapsed, kern_ms = timed_steps(ranks, solve, args.steps, args.warmup, last=last)
         results[mode] = dict(rows=rows, elapsed=elapsed, kern_ms=kern_ms, X=X, W=W, Xg=Xg, Wg=Wg, z0=z0,
-                             z=solve())
-    main_mode = args.scaling if world > 1 else "strong"
+                             z=last["out"])
     r = results[main_mode]
+    dump_outputs(args, rank, world, {"z": r["z"]})
     ttt = None
-    if not args.no_time_to_tol:
+    if args.full and not args.no_time_to_tol:
         # time-to-tol with the reference's rule (ista.py:64,93: ONE sum over ALL rows of the batch, also when the rows
         # are spread over the ranks): every rank runs the solve on its shard, the per-iteration sums of a chunk of <= 64
         # iterations meet in one small all-reduce, every rank stops at the same iteration; time = max over the ranks
@@ -399,13 +441,13 @@ def run_fista(args, ranks):
                          "avg_launch_note": "HIP events around the K timed steps / K: the solve's launches (prepare + "
                                             "the persistent kernel) back to back"},
         }
-        if world > 1:
+        if world > 1 and args.full:
             other = "weak" if main_mode == "strong" else "strong"
             q = results[other]
             out[other + "_scaling"] = {"value": line(other), "unit": "iterations/s", "rows_per_gpu": q["rows"],
                                        "rows_total": q["rows"] * world,
                                        "ms_per_step": 1e3 * q["elapsed"] / args.steps}
-        if world == 1 and not args.no_shards and n_rows == N_ROWS:
+        if args.full and world == 1 and not args.no_shards and n_rows == N_ROWS:
             # what ONE rank of an N-GPU strong-scaling run of this batch does (4096/N rows, no
             # data-path collective): timed here on this GPU -- the per-rank ceiling of the N-GPU value
             shards = {}
@@ -440,7 +482,7 @@ def run_fista(args, ranks):
             out["strong_scaling_shards_on_one_gpu"] = shards
         if ttt is not None:
             out["time_to_tol"] = ttt
-        if not args.no_extras and world == 1:
+        if args.full and not args.no_extras and world == 1:
             # SURVEY 8d's other figures for this configuration, each with its own timed region
             Xg, Wg, z0 = r["Xg"], r["Wg"], r["z0"]
             el, _ = timed_steps(ranks, lambda: ista(Xg, z0, Wg, ALPHA, fast=False, lr=lr, maxiter=args.iters, tol=0.0),
@@ -469,13 +511,13 @@ def run_fista(args, ranks):
                                 "seconds": el, "tflops": 4.0 * r["rows"] * D * K * long_iters * 10 / el / 1e12,
                                 "note": "the same kernel held busy ~10x longer than the headline region (clock under "
                                         "sustained load)"}
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(r["X"], r["W"], lr)
-        elif not args.no_cpu_baseline:
+        elif args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = None
     # objective of the timed result (HIP lasso_loss) against the reference's known answer; the
     # whole 4096-row batch when it is sharded (strong): sums all-reduced
-    if args.iters == 100 and n_rows == N_ROWS:
+    if args.full and args.iters == 100 and n_rows == N_ROWS:
         from lasso_amd.engine import HipEngine
         q = results["strong"]
         _, sums = HipEngine(dev).objective_sums(q["Xg"], q["z"], q["Wg"], ALPHA)
@@ -548,6 +590,7 @@ def run_em(args, ranks):
         elapsed = ranks.max(time.perf_counter() - t0)
     finally:
         parallel._all_reduce = real_all_reduce
+    dump_outputs(args, rank, world, {"D": state["D"], "losses": torch.as_tensor(state["loss"], dtype=torch.float64)})
     out = None
     if rank == 0:
         # messages per EM step: one ([A | B | tail]), or -- pipelined M-step (d = 256, k a multiple of 256) -- one per
@@ -631,7 +674,9 @@ def run_c3(args, ranks):
         if not ranks.sharded:
             return ista(Xg, z0, Wg, ALPHA, return_info=info, **kw)
         return parallel.sharded_encode(eng, Xg, Wg, ALPHA, z0, n_global=n_all, return_info=info, **kw)
-    elapsed, kern_ms = timed_steps(ranks, solve, args.steps, args.warmup)
+    last = {}
+    elapsed, kern_ms = timed_steps(ranks, solve, args.steps, args.warmup, last=last)
+    dump_outputs(args, rank, world, {"z": last["out"]})
     z, info = solve(True)
     _, sums = eng.objective_sums(Xg.float(), z.float(), Wg.float(), ALPHA)
     ranks.sum_(sums)
@@ -707,8 +752,10 @@ def run_conv(args, ranks):
 
     def solve():
         return ista_conv2d(xg, zg, wg, 0.1, stride=1, padding=pd, maxiter=CONV_ITERS, lr=lr, tol=0.0)
-    elapsed, kern_ms = timed_steps(ranks, solve, args.steps, args.warmup)
-    z = solve()
+    last = {}
+    elapsed, kern_ms = timed_steps(ranks, solve, args.steps, args.warmup, last=last)
+    z = last["out"]
+    dump_outputs(args, rank, world, {"z": z})
     nnz = torch.tensor([float((z != 0).sum())], device=dev, dtype=torch.float64)
     ranks.sum_(nnz)
     if rank != 0:
@@ -764,7 +811,9 @@ def run_cd(args, ranks):
 
     def solve():
         return coord_descent(Xg, Wg, None, ALPHA, maxiter=CD_STEPS)
-    elapsed, kern_ms = timed_steps(ranks, solve, args.steps, args.warmup)
+    last = {}
+    elapsed, kern_ms = timed_steps(ranks, solve, args.steps, args.warmup, last=last)
+    dump_outputs(args, rank, world, {"z": last["out"]})
     z, info = coord_descent(Xg, Wg, None, ALPHA, maxiter=CD_STEPS, return_info=True)
     # the objective of the returned codes, all-reduced (dict_learning.py:10-13 on all rows)
     from lasso_amd.engine import HipEngine
@@ -796,7 +845,7 @@ def run_cd(args, ranks):
         "max_steps": info["max_steps"], "n_active": info["n_active"],
         "objective": float((0.5 * sums[0] + ALPHA * sums[1]) / n_all),
     }
-    if not args.no_cpu_baseline and world == 1:
+    if args.full and not args.no_cpu_baseline and world == 1:
         from oracle import lasso_oracle as orc
         sample = 256
         orc.coordinate_descent(X[:8], W, None, ALPHA, maxiter=10)
@@ -850,6 +899,11 @@ def parser():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extras", action="store_true", help="skip the ISTA / Lipschitz / lr='auto' / sustained legs")
     ap.add_argument("--no-time-to-tol", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline figure: CPU baseline, time-to-tol, per-shard, extra "
+                         "legs, the other scaling figure at N > 1, the objective check against the reference")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (float32/float64, <= 64 MB)")
     return ap
 
 

@@ -39,3 +39,16 @@ def golden():
     def load(name):
         return np.load(os.path.join(GOLDEN, name + ".npz"))
     return load
+
+
+@pytest.fixture(scope="session")
+def golden_this_cpu():
+    """For the bitwise oracle tests: golden(name) with the arrays of the recorded run this CPU reproduces
+    (tests/golden_runs.py) in place of the primary's; .run names that run (None: the primary)."""
+    import golden_runs
+    run = golden_runs.this_cpu_run()
+
+    def load(name):
+        return golden_runs.load(name, run)
+    load.run = run
+    return load

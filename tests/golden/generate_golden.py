@@ -12,7 +12,14 @@ The reference does not import as-is under scipy 1.15 (iterative_ridge.py:5
 imports a private scipy symbol); the 3-line shim below aliases that symbol
 BEFORE importing -- no reference file is edited or copied.
 
-Usage:  python tests/golden/generate_golden.py [g1 g2 g3 g3trace g4 g5 small inits cd conv]
+Usage:  python tests/golden/generate_golden.py [--run NAME] [g1 g2 g3 g3trace g4 g5 small inits cd conv recipes]
+
+The reference's float32 GEMMs, convolutions and QR round differently on different CPUs, so a bitwise fixture holds
+on the kind of CPU it was recorded on.  --run NAME records the reference on this CPU as a further run:
+tests/golden/NAME/<fixture>.npz keeps only the arrays that differ from tests/golden/<fixture>.npz (the inputs are the
+same seeded draws; an array over tests/golden_runs.py's DIGEST_BYTES as its SHA-256), and tests/conftest.py's
+`golden_this_cpu` picks the run whose first FISTA iterate of config 2 this CPU
+reproduces.  `recipes` (a run only) records lambda_max of the config-4 init dictionary, which QR decides.
 """
 import os
 import sys
@@ -35,6 +42,7 @@ ref_ista = ref_ista_mod.ista
 ref_loss = ref_dl_mod.lasso_loss
 
 HERE = os.path.dirname(os.path.abspath(__file__))
+RUN = None            # --run NAME: write the arrays that differ from the primary fixtures to HERE/NAME/
 sys.path.insert(0, os.path.dirname(HERE))
 from recipes import (recipe_xw, recipe_c4_init, recipe_c5, LAMBDA_MAX_C2,  # noqa: E402
                      LAMBDA_MAX_C4)
@@ -47,8 +55,19 @@ def zstats(z):
 
 
 def save(name, **arrays):
+    arrays = {k: np.asarray(v) for k, v in arrays.items()}
     path = os.path.join(HERE, name + ".npz")
-    np.savez_compressed(path, **{k: np.asarray(v) for k, v in arrays.items()})
+    if RUN:
+        if os.path.exists(path):
+            primary = np.load(path)
+            arrays = {k: v for k, v in arrays.items()
+                      if k not in primary.files or not np.array_equal(primary[k], v)}
+        from golden_runs import DIGEST_BYTES, SUFFIX, Digest
+        big = {k for k, v in arrays.items() if v.nbytes > DIGEST_BYTES}
+        arrays = {(k + SUFFIX if k in big else k): (np.array(Digest.of(v)) if k in big else v) for k, v in arrays.items()}
+        os.makedirs(os.path.join(HERE, RUN), exist_ok=True)
+        path = os.path.join(HERE, RUN, name + ".npz")
+    np.savez_compressed(path, **arrays)
     print("wrote", path, os.path.getsize(path), "bytes")
 
 
@@ -326,6 +345,14 @@ def g5():
          check_X=X[0, :3].numpy())
 
 
+def recipes():
+    """lambda_max of the config-4 init dictionary and its first entries (a run only: the primary run's value is
+    recipes.LAMBDA_MAX_C4)."""
+    D0 = recipe_c4_init()
+    w = D0.double()
+    save("recipes", lambda_max_c4=torch.linalg.eigvalsh(w @ w.T)[-1].item(), check_D0=D0[0, :3].numpy())
+
+
 def small():
     """Small full-output cases (all shapes ragged on purpose)."""
     out = {}
@@ -447,6 +474,8 @@ def conv():
 
 if __name__ == "__main__":
     which = sys.argv[1:] or ["g1", "g2", "g3", "g5", "small", "g4"]
+    if which[0] == "--run":
+        RUN, which = which[1], which[2:]
     torch.set_num_threads(8)
     for w in which:
         t = time.time()

@@ -62,6 +62,9 @@ def test_argument_parsing_of_the_workloads():
     assert (a.gpus, a.steps, a.warmup, a.workload, a.dtype) == (8, 7, 2, "c3", "f32")
     a = ap.parse_args("--workload em --shape c5 --rows 8192 --backend gloo --share-gpu".split())
     assert (a.workload, a.shape, a.rows, a.backend, a.share_gpu) == ("em", "c5", 8192, "gloo", True)
+    assert (a.full, a.dump_outputs) == (False, None)
+    a = ap.parse_args("--full --dump-outputs out".split())
+    assert (a.full, a.dump_outputs) == (True, "out")
     for bad in (["--workload", "c9"], ["--shape", "c2"], ["--dtype", "fp8"], ["--backend", "mpi"]):
         with pytest.raises(SystemExit):
             ap.parse_args(bad)

@@ -30,7 +30,7 @@ SHARED = ["--gpus", "2", "--backend", "gloo", "--share-gpu", "--steps", "2", "--
 
 
 def test_two_rank_fista_line_and_global_time_to_tol():
-    out = _bench(SHARED + ["--workload", "fista", "--no-cpu-baseline"])
+    out = _bench(SHARED + ["--workload", "fista", "--no-cpu-baseline", "--full"])
     assert out["n_gpus"] == 2 and out["steps"] == 2 and out["scaling"] == "strong"
     assert out["config"]["rows_per_gpu"] == 2048 and out["config"]["rows_total"] == 4096
     assert out["weak_scaling"]["rows_per_gpu"] == 4096 and out["weak_scaling"]["value"] > 0
@@ -93,6 +93,26 @@ def test_one_rank_lines_of_configs_3_and_5():
     assert out["n_gpus"] == 1 and out["all_reduce_ms"]["per_step"] == 0.0
 
 
+def test_plain_fista_line_is_the_headline_and_dumps_the_last_step(tmp_path):
+    """a plain run times its steps and nothing else; --dump-outputs writes the codes of its last timed step, and the
+    objective of those codes is the reference's answer after 100 iterations"""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    out = _bench(["--gpus", "1", "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path)])
+    assert out["steps"] == 3 and out["warmup"] == 1 and out["ms_per_step"] > 0 and out["dtype"] == "f32"
+    assert out["value"] == pytest.approx(3 * 100 / (out["ms_per_step"] * 3e-3), rel=1e-9)
+    for key in ("cpu_baseline", "time_to_tol", "strong_scaling_shards_on_one_gpu", "sustained", "objective_after_100"):
+        assert key not in out
+    z = np.load(str(tmp_path / "z.npy"))
+    assert z.dtype == np.float32 and z.shape == (4096, 1024)
+    X, W = bench.recipe(4096)
+    zt = torch.from_numpy(z).double()
+    obj = (0.5 * (zt @ W.double().T - X.double()).pow(2).sum() + 0.5 * zt.abs().sum()).item() / 4096
+    assert abs(obj - bench.OBJ_REF_100) <= 2e-6 * bench.OBJ_REF_100
+
+
 # ---- the RCCL arms, executed: ONE rank, a real nccl (= RCCL) process group, LASSO_FORCE_COLLECTIVES ------------------
 # `--force-dist` makes the N = 1 run take every multi-rank code path (lasso_amd.parallel._sharded): the in-place
 # all-reduce of DEVICE tensors, Ranks.max on a device tensor, the sharded E-step with its stop-rule sums in the M-step
@@ -102,7 +122,7 @@ FORCED = ["--gpus", "1", "--backend", "nccl", "--force-dist", "--steps", "2", "-
 
 
 def test_one_rank_rccl_group_fista_line():
-    out = _bench(FORCED + ["--workload", "fista", "--no-cpu-baseline", "--no-shards", "--no-extras"])
+    out = _bench(FORCED + ["--workload", "fista", "--no-cpu-baseline", "--no-shards", "--no-extras", "--full"])
     assert out["n_gpus"] == 1 and "ONE-rank process group" in out["backend"] and out["backend"].startswith("nccl")
     assert abs(out["objective_after_100"] - 63.609337) <= 2e-6 * 63.609337        # sums all-reduced on the device
     t = out["time_to_tol"]                                                        # parallel.sharded_encode: chunks +
