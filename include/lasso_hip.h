@@ -553,6 +553,39 @@ int lasso_conv_lip_bound(const void* w_dev, int64_t K, int64_t C, int ksize, int
                          int take_sqrt, double* l_out,
                          void* workspace_dev, size_t workspace_bytes, void* stream);
 
+/* ---- reverse-mode derivative of the unrolled convolutional solve ---------------------
+ * The reference's ista_conv2d (lasso/conv2d/ista.py:7-49) is plain torch code: torch.autograd
+ * differentiates it with respect to x, weight and z0.  Same geometry arguments as above.
+ *   lasso_conv_ista_run_traced: exactly `iterations` iterations (no stop rule) of the solve with
+ *       the fixed step lr, bitwise those of lasso_conv_ista_solve; z_out_dev [N][K][Hz][Wz] = z_T
+ *       and trace_dev = the iterates z_0 .. z_T in the solver's layout ([T+1][N*Hz*Wz][K], an
+ *       opaque buffer of lasso_conv_ista_trace_bytes bytes; only lasso_conv_ista_backward reads
+ *       it).  Workspace: lasso_conv_ista_workspace_bytes.
+ *   lasso_conv_ista_backward: given the trace of such a run and dL/dz_T (grad_z_dev, NCHW),
+ *       writes dL/dx [N][C][H][W], dL/dW [K][C][kh][kw], dL/dz0 [N][K][Hz][Wz] (each nullable,
+ *       contiguous; a null grad_w_dev skips the weight-gradient kernel).  Same derivative as
+ *       torch.autograd through the reference loop: softshrink passes the gradient where
+ *       |u| > alpha*lr, the step and the momentum schedule are constants.  dL/dW is bitwise
+ *       reproducible (no float atomics).  No host synchronisation.
+ */
+size_t lasso_conv_ista_trace_bytes(int64_t N, int64_t C, int64_t H, int64_t W, int64_t K,
+                                   int64_t Hz, int64_t Wz, int kh, int kw, int sh, int sw, int ph, int pw,
+                                   int iterations);
+int lasso_conv_ista_run_traced(const void* x_dev, const void* w_dev, const void* z0_dev, void* z_out_dev,
+                               int64_t N, int64_t C, int64_t H, int64_t W, int64_t K, int64_t Hz, int64_t Wz,
+                               int kh, int kw, int sh, int sw, int ph, int pw, int dtype,
+                               double alpha, double lr, int fast, int iterations, void* trace_dev,
+                               void* workspace_dev, size_t workspace_bytes, void* stream);
+size_t lasso_conv_ista_backward_workspace_bytes(int64_t N, int64_t C, int64_t H, int64_t W, int64_t K,
+                                                int64_t Hz, int64_t Wz, int kh, int kw, int sh, int sw,
+                                                int ph, int pw);
+int lasso_conv_ista_backward(const void* x_dev, const void* w_dev, const void* trace_dev, const void* grad_z_dev,
+                             int64_t N, int64_t C, int64_t H, int64_t W, int64_t K, int64_t Hz, int64_t Wz,
+                             int kh, int kw, int sh, int sw, int ph, int pw, int dtype,
+                             double lr, int fast, int iterations,
+                             void* grad_x_dev, void* grad_w_dev, void* grad_z0_dev,
+                             void* workspace_dev, size_t workspace_bytes, void* stream);
+
 /* ---- reverse-mode derivative of the unrolled fixed-step solve ------------------------
  * The reference's ista() is ordinary autograd-traceable torch code (ista.py:57-104; the
  * README advertises back-propagation through the solver).  Given the iterates

@@ -548,15 +548,19 @@ hipError_t launch_conv_residual(const float* Ym, const float* Wt, const float* w
   return hipGetLastError();
 }
 
-// G [M][K] = conv2d(R, W) in row layout: pixel-major patches, then G = RC Wp^T on the general
-// MFMA GEMM (contraction over the taps)
-hipError_t launch_conv_gradient(const float* r, const float* Wp, float* rc, int ldr, float* G, const ConvGeom& g,
-                                hipStream_t stream) {
+hipError_t launch_conv_patches(const float* r, float* rc, int ldr, const ConvGeom& g, hipStream_t stream) {
   const int64_t M = (int64_t)g.N * g.Hz * g.Wz;
   hipLaunchKernelGGL(conv_patches_kernel, dim3(grid_for(M * (ldr / 4))), dim3(256), 0, stream, r, rc, ldr, g);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return e;
-  return launch_gemm_nt_sub(rc, ldr, Wp, ldr, nullptr, 0, G, g.K, (int)M, g.K, ldr, stream, /*add=*/1);
+  return hipGetLastError();
+}
+
+// G [M][K] = conv2d(R, W) in row layout: pixel-major patches, then G = RC Wp^T on the general
+// MFMA GEMM (contraction over the taps); add_to (the reverse pass: yb = ub + conv2d(rb, W)) rides in its epilogue
+hipError_t launch_conv_gradient(const float* r, const float* Wp, float* rc, int ldr, float* G, const ConvGeom& g,
+                                hipStream_t stream, const float* add_to) {
+  const int64_t M = (int64_t)g.N * g.Hz * g.Wz;
+  if (hipError_t e = launch_conv_patches(r, rc, ldr, g, stream); e != hipSuccess) return e;
+  return launch_gemm_nt_sub(rc, ldr, Wp, ldr, add_to, add_to ? g.K : 0, G, g.K, (int)M, g.K, ldr, stream, /*add=*/1);
 }
 
 // The fused implicit-GEMM gradient + prox step, when the geometry fits (C kh kw <= 192 and the

@@ -1627,6 +1627,37 @@ ConvGeom make_geom(int64_t N, int64_t C, int64_t H, int64_t W, int64_t K, int64_
   return g;
 }
 
+// One iteration of the two-kernel form on (ws.Zm, ws.Ym) (ista.py:19-20,29,42,44): the synthesis residual, then the
+// fused implicit-GEMM gradient + prox when the geometry fits, else patches + GEMM + prox.  *dcount = the number of
+// partial sums |z - z+| left in ws.dpart.
+int conv_two_kernel_step(const ConvWorkspace& ws, const ConvGeom& g, const float* x, const float* w, float lr, float lam,
+                         float coef, int cus, int* dcount, hipStream_t st) {
+  const int ldr = (g.C * g.kh * g.kw + 3) / 4 * 4;
+  *dcount = 0;
+  LASSO_HIP_TRY(launch_conv_residual(ws.Ym, ws.Wt, w, x, ws.PT, ws.R, g, cus, st));                   // :19
+  LASSO_HIP_TRY(launch_conv_grad_prox(ws.R, ws.Wp, ldr, ws.Zm, ws.Ym, lr, lam, coef, ws.dpart, kGenGrid, g, cus,
+                                      dcount, st));                                                   // :20,:29,:42,:44
+  if (*dcount == 0) {
+    LASSO_HIP_TRY(launch_conv_gradient(ws.R, ws.Wp, ws.PT, ldr, ws.G, g, st));                         // :20
+    LASSO_HIP_TRY(launch_generic_prox(ws.Zm, g.K, ws.Ym, ws.G, (int)((int64_t)g.N * g.Hz * g.Wz), g.K, lr, lam, coef,
+                                      ws.dpart, kGenGrid, st));                                       // :29,:42,:44
+    *dcount = kGenGrid;
+  }
+  return LASSO_OK;
+}
+
+// momentum coefficients c_i = (t_i - 1) / t_{i+1} of iterations 0 .. iterations-1 (ista.py:41-42; 0 without momentum)
+std::vector<float> fista_coefs(int iterations, int fast) {
+  std::vector<float> coef((size_t)std::max(iterations, 1), 0.0f);
+  double t = 1.0;
+  for (int i = 0; i < iterations; ++i) {
+    const double tn = (1.0 + sqrt(1.0 + 4.0 * t * t)) / 2.0;
+    coef[i] = fast ? (float)((t - 1.0) / tn) : 0.0f;
+    t = tn;
+  }
+  return coef;
+}
+
 }  // namespace
 }  // namespace lasso
 
@@ -3081,16 +3112,7 @@ int lasso_conv_ista_solve(const void* x_dev, const void* w_dev, const void* z0_d
       return LASSO_OK;
     }
     int dcount = 0;
-    LASSO_HIP_TRY(launch_conv_residual(ws.Ym, ws.Wt, conv_w, (const float*)x_dev, ws.PT, ws.R, g, cus, st));   // :19
-    // gradient + prox: the fused implicit-GEMM kernel when the geometry fits, else patches + GEMM + prox
-    LASSO_HIP_TRY(launch_conv_grad_prox(ws.R, ws.Wp, ldr, ws.Zm, ws.Ym, lr_f, lam, coef, ws.dpart, kGenGrid, g, cus,
-                                        &dcount, st));                                            // :20,:29,:42,:44
-    if (dcount == 0) {
-      LASSO_HIP_TRY(launch_conv_gradient(ws.R, ws.Wp, ws.PT, ldr, ws.G, g, st));                  // :20
-      LASSO_HIP_TRY(launch_generic_prox(ws.Zm, g.K, ws.Ym, ws.G, (int)M, g.K, lr_f, lam, coef, ws.dpart,
-                                        kGenGrid, st));                                           // :29,:42,:44
-      dcount = kGenGrid;
-    }
+    if (int s = conv_two_kernel_step(ws, g, (const float*)x_dev, conv_w, lr_f, lam, coef, cus, &dcount, st)) return s;
     t_mom = t_next;
     if (delta_slot) {
       hipLaunchKernelGGL(reduce_partials_kernel, dim3(1), dim3(256), 0, st, ws.dpart, dcount, delta_slot);
@@ -3147,6 +3169,167 @@ int lasso_conv_objective(const void* x_dev, const void* w_dev, const void* z_dev
                                      std::max(device_cus(), 1), st));
   LASSO_HIP_TRY(launch_objective_reduce(ws.R, (int64_t)g.N * g.C * g.H * g.W, ws.Zm, g.K, (int)M, g.K, ws.dpart,
                                         kGenGrid, alpha, (double)g.N, ws.sums, loss_dev, st));
+  return LASSO_OK;
+}
+
+// ---- reverse pass of the convolutional solve (conv_autograd.hip) ------------
+size_t lasso_conv_ista_trace_bytes(int64_t N, int64_t C, int64_t H, int64_t W, int64_t K, int64_t Hz, int64_t Wz,
+                                   int kh, int kw, int sh, int sw, int ph, int pw, int iterations) {
+  const ConvGeom g = make_geom(N, C, H, W, K, Hz, Wz, kh, kw, sh, sw, ph, pw);
+  if (iterations < 0 || check_conv(g, LASSO_F32)) return 0;
+  return (size_t)(iterations + 1) * (size_t)N * Hz * Wz * K * 4;
+}
+
+int lasso_conv_ista_run_traced(const void* x_dev, const void* w_dev, const void* z0_dev, void* z_out_dev, int64_t N,
+                               int64_t C, int64_t H, int64_t W, int64_t K, int64_t Hz, int64_t Wz, int kh, int kw,
+                               int sh, int sw, int ph, int pw, int dtype, double alpha, double lr, int fast,
+                               int iterations, void* trace_dev, void* workspace_dev, size_t workspace_bytes,
+                               void* stream) {
+  const ConvGeom g = make_geom(N, C, H, W, K, Hz, Wz, kh, kw, sh, sw, ph, pw);
+  if (int s = check_conv(g, dtype)) return s;
+  if (!w_dev || !workspace_dev || (N > 0 && (!x_dev || !z0_dev || !z_out_dev || !trace_dev)))
+    return fail(LASSO_ERR_BAD_ARG, "null pointer");
+  if (iterations < 0 || !(lr > 0.0) || !(alpha >= 0.0))
+    return fail(LASSO_ERR_BAD_ARG, "iterations=%d lr=%g alpha=%g", iterations, lr, alpha);
+  ConvWorkspace ws = carve_conv(workspace_dev, g);
+  if (workspace_bytes < ws.bytes) return fail(LASSO_ERR_WORKSPACE, "workspace %zu < %zu bytes", workspace_bytes, ws.bytes);
+  if (N == 0) return LASSO_OK;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const int ckk = g.C * g.kh * g.kw, P = g.Hz * g.Wz;
+  const int64_t mk = (int64_t)g.N * P * g.K;
+  const int cus = std::max(device_cus(), 1);
+  const float* const conv_w = (const float*)w_dev;
+  float* const trace = (float*)trace_dev;
+  LASSO_HIP_TRY(launch_conv_pack_w(conv_w, ws.Wt, ws.Wp, g.K, ckk, (ckk + 3) / 4 * 4, st));
+  LASSO_HIP_TRY(launch_conv_relayout((const float*)z0_dev, ws.Zm, ws.Ym, g.N, g.K, P, 1, st));
+  LASSO_HIP_TRY(hipMemcpyAsync(trace, ws.Zm, (size_t)mk * 4, hipMemcpyDeviceToDevice, st));
+  // the two-kernel form for every geometry: conv_fused.hip computes the same iterates bitwise
+  // (tests/test_conv_gpu.py::test_many_iterations_per_launch_kernel)
+  const std::vector<float> coef = fista_coefs(iterations, fast);
+  const float lr_f = (float)lr, lam = (float)(alpha * lr);
+  for (int it = 0; it < iterations; ++it) {
+    int dcount = 0;
+    if (int s = conv_two_kernel_step(ws, g, (const float*)x_dev, conv_w, lr_f, lam, coef[it], cus, &dcount, st)) return s;
+    LASSO_HIP_TRY(hipMemcpyAsync(trace + (it + 1) * mk, ws.Zm, (size_t)mk * 4, hipMemcpyDeviceToDevice, st));
+  }
+  LASSO_HIP_TRY(launch_conv_relayout(ws.Zm, (float*)z_out_dev, nullptr, g.N, g.K, P, 0, st));
+  return LASSO_OK;
+}
+
+namespace {
+struct ConvBwWorkspace {
+  float* Wt; float* Wp;                                    // the weight as the forward's kernels take it
+  float* zbA; float* zbB; float* yb; float* ub; float* gb; float* y;     // [M][K]
+  float* R; float* RB;                                     // r_i, rb [N][C][H][W]
+  float* PT;                                               // patches / COLSt of the explicit paths
+  float* T1; float* T2; float* scratch;                    // conv_patches + gram_tn form of dW
+  float* part; int splits;                                 // conv_wgrad_kernel's partial tiles
+  size_t bytes;
+};
+ConvBwWorkspace carve_conv_bw(void* base, const ConvGeom& g, int cus) {
+  ConvBwWorkspace w;
+  char* p = static_cast<char*>(base);
+  size_t off = 0;
+  auto take = [&](size_t bytes) {
+    char* r = p ? p + off : nullptr;
+    off += align_up(std::max<size_t>(bytes, 4));
+    return reinterpret_cast<float*>(r);
+  };
+  const size_t ckk = (size_t)g.C * g.kh * g.kw, M = (size_t)g.N * g.Hz * g.Wz, ldr = (ckk + 3) / 4 * 4;
+  const size_t mk = M * g.K * 4, img = (size_t)g.N * g.C * g.H * g.W * 4, kc = ckk * g.K * 4;
+  w.Wt = take(kc); w.Wp = take(ldr * g.K * 4);
+  w.zbA = take(mk); w.zbB = take(mk); w.yb = take(mk); w.ub = take(mk); w.gb = take(mk); w.y = take(mk);
+  w.R = take(img); w.RB = take(img);
+  w.PT = take(ldr * M * 4);
+  w.T1 = take(kc); w.T2 = take(kc); w.scratch = take(16 * kc);
+  w.splits = std::max(conv_wgrad_splits(g, cus), 1);
+  w.part = take((size_t)w.splits * kc);
+  w.bytes = off;
+  return w;
+}
+}  // namespace
+
+size_t lasso_conv_ista_backward_workspace_bytes(int64_t N, int64_t C, int64_t H, int64_t W, int64_t K, int64_t Hz,
+                                                int64_t Wz, int kh, int kw, int sh, int sw, int ph, int pw) {
+  const ConvGeom g = make_geom(N, C, H, W, K, Hz, Wz, kh, kw, sh, sw, ph, pw);
+  if (check_conv(g, LASSO_F32)) return 0;
+  return carve_conv_bw(nullptr, g, std::max(device_cus(), 1)).bytes;
+}
+
+int lasso_conv_ista_backward(const void* x_dev, const void* w_dev, const void* trace_dev, const void* grad_z_dev,
+                             int64_t N, int64_t C, int64_t H, int64_t W, int64_t K, int64_t Hz, int64_t Wz, int kh,
+                             int kw, int sh, int sw, int ph, int pw, int dtype, double lr, int fast, int iterations,
+                             void* grad_x_dev, void* grad_w_dev, void* grad_z0_dev, void* workspace_dev,
+                             size_t workspace_bytes, void* stream) {
+  const ConvGeom g = make_geom(N, C, H, W, K, Hz, Wz, kh, kw, sh, sw, ph, pw);
+  if (int s = check_conv(g, dtype)) return s;
+  if (!w_dev || !workspace_dev || (N > 0 && (!x_dev || !trace_dev || !grad_z_dev)))
+    return fail(LASSO_ERR_BAD_ARG, "null pointer");
+  if (iterations < 0 || !(lr > 0.0)) return fail(LASSO_ERR_BAD_ARG, "iterations=%d lr=%g", iterations, lr);
+  const int cus = std::max(device_cus(), 1);
+  ConvBwWorkspace ws = carve_conv_bw(workspace_dev, g, cus);
+  if (workspace_bytes < ws.bytes) return fail(LASSO_ERR_WORKSPACE, "workspace %zu < %zu bytes", workspace_bytes, ws.bytes);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const int ckk = g.C * g.kh * g.kw, ldr = (ckk + 3) / 4 * 4, P = g.Hz * g.Wz;
+  const int64_t M = (int64_t)g.N * P, mk = M * g.K, img = (int64_t)g.N * g.C * g.H * g.W, kc = (int64_t)g.K * ckk;
+  const float* const X = (const float*)x_dev;
+  const float* const conv_w = (const float*)w_dev;
+  const float* const trace = (const float*)trace_dev;
+  float* const gx = (float*)grad_x_dev;
+  float* const gw = (float*)grad_w_dev;
+  float* const gz0 = (float*)grad_z0_dev;
+  // dW: conv_wgrad_kernel (conv_autograd.hip), or the composition conv_patches + gram_tn where it does not cover the
+  // geometry -- or where LASSO_CONV_WGRAD=gram asks for it (the A/B of tools/bench_conv_backward.py)
+  const char* form = getenv("LASSO_CONV_WGRAD");
+  const int splits = (form && strcmp(form, "gram") == 0) ? 0 : std::min(conv_wgrad_splits(g, cus), ws.splits);
+  if (gx && img > 0) LASSO_HIP_TRY(hipMemsetAsync(gx, 0, (size_t)img * 4, st));
+  if (gw && (splits == 0 || iterations == 0 || N == 0)) LASSO_HIP_TRY(hipMemsetAsync(gw, 0, (size_t)kc * 4, st));
+  if (N == 0) return LASSO_OK;
+  if (iterations == 0) {                       // z_T = z_0
+    if (gz0) LASSO_HIP_TRY(hipMemcpyAsync(gz0, grad_z_dev, (size_t)mk * 4, hipMemcpyDeviceToDevice, st));
+    return LASSO_OK;
+  }
+  const std::vector<float> coef = fista_coefs(iterations, fast);
+  const float lr_f = (float)lr;
+  LASSO_HIP_TRY(launch_conv_pack_w(conv_w, ws.Wt, ws.Wp, g.K, ckk, ldr, st));
+  float* zb_next = ws.zbA;
+  float* zb_cur = ws.zbB;
+  LASSO_HIP_TRY(launch_conv_relayout((const float*)grad_z_dev, zb_next, nullptr, g.N, g.K, P, 1, st));
+  LASSO_HIP_TRY(hipMemsetAsync(ws.yb, 0, (size_t)mk * 4, st));
+  const int gsplits = gram_splits(g.K, ckk, (int)M, 0, cus);
+  for (int i = iterations - 1; i >= 0; --i) {
+    const float* z_next = trace + (int64_t)(i + 1) * mk;
+    const float* z_i = trace + (int64_t)i * mk;
+    // zb_{i+1} += (1+c_i) yb_{i+1} ; zb_i = -c_i yb_{i+1} ; ub = [z_{i+1} != 0] zb_{i+1} ; gb = -lr ub
+    LASSO_HIP_TRY(launch_bw_prox(zb_next, zb_cur, ws.yb, z_next, ws.ub, ws.gb, mk, coef[i], lr_f, st));
+    // rb = conv_transpose2d(gb, W) (no x) ; yb_i = ub + conv2d(rb, W)
+    LASSO_HIP_TRY(launch_conv_residual(ws.gb, ws.Wt, conv_w, nullptr, ws.PT, ws.RB, g, cus, st));
+    LASSO_HIP_TRY(launch_conv_gradient(ws.RB, ws.Wp, ws.PT, ldr, ws.yb, g, st, ws.ub));
+    if (gw) {
+      // the point of iteration i, y_i = z_i + c_{i-1} (z_i - z_{i-1}) (y_0 = z_0), and its residual r_i
+      LASSO_HIP_TRY(launch_bw_point(z_i, (i > 0 && fast) ? trace + (int64_t)(i - 1) * mk : nullptr, ws.y, mk,
+                                    i > 0 ? coef[i - 1] : 0.0f, st));
+      if (splits == 0)                         // (PT holds P(rb) until the residual below reuses it)
+        LASSO_HIP_TRY(launch_gram_tn(ws.y, g.K, g.K, ws.PT, ldr, ckk, (int)M, ws.T2, ckk, 0, ws.scratch, gsplits, st));
+      LASSO_HIP_TRY(launch_conv_residual(ws.y, ws.Wt, conv_w, X, ws.PT, ws.R, g, cus, st));
+      // dW += gb^T P(r_i) + y_i^T P(rb)
+      if (splits > 0) {
+        LASSO_HIP_TRY(launch_conv_wgrad(ws.gb, ws.R, ws.y, ws.RB, ws.part, splits, i != iterations - 1, g, st));
+      } else {
+        LASSO_HIP_TRY(launch_conv_patches(ws.R, ws.PT, ldr, g, st));
+        LASSO_HIP_TRY(launch_gram_tn(ws.gb, g.K, g.K, ws.PT, ldr, ckk, (int)M, ws.T1, ckk, 0, ws.scratch, gsplits, st));
+        LASSO_HIP_TRY(launch_bw_axpy(gw, ws.T1, 1.0f, ws.T2, 1.0f, kc, st));
+      }
+    }
+    if (gx) LASSO_HIP_TRY(launch_bw_axpy(gx, ws.RB, -1.0f, nullptr, 0.0f, img, st));    // xb -= rb
+    std::swap(zb_next, zb_cur);
+  }
+  if (gw && splits > 0) LASSO_HIP_TRY(launch_conv_wgrad_sum(ws.part, splits, g, gw, st));
+  if (gz0) {
+    // z0b = zb_0 + yb_0 (y_0 = z_0), back to [N][K][Hz][Wz]
+    LASSO_HIP_TRY(launch_bw_axpy(zb_next, ws.yb, 1.0f, nullptr, 0.0f, mk, st));
+    LASSO_HIP_TRY(launch_conv_relayout(zb_next, gz0, nullptr, g.N, g.K, P, 0, st));
+  }
   return LASSO_OK;
 }
 

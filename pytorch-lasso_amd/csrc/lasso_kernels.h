@@ -414,8 +414,17 @@ hipError_t launch_conv_fused(const void* tables, const float* x, float* Zm, cons
 hipError_t launch_conv_grad_prox(const float* r, const float* Wp, int ldr, float* Zm, float* Ym, float lr, float lam,
                                  float coef, float* dpart, int dpart_cap, const ConvGeom& g, int cus, int* count,
                                  hipStream_t stream, int dry = 0);
+// G = add_to + conv2d(r, W) in row layout (add_to [M][K] or null)
 hipError_t launch_conv_gradient(const float* r, const float* Wp, float* rc, int ldr, float* G, const ConvGeom& g,
-                                hipStream_t stream);
+                                hipStream_t stream, const float* add_to = nullptr);
+// rc [M][ldr] = the pixel-major patches of r (conv_patches_kernel)
+hipError_t launch_conv_patches(const float* r, float* rc, int ldr, const ConvGeom& g, hipStream_t stream);
+// conv_autograd.hip: dW of the reverse pass as one implicit GEMM over the 2M rows (gb, P(r)) and (y, P(rb)) into
+// `splits` partial tiles (conv_wgrad_splits: 0 = not covered), summed in split order by launch_conv_wgrad_sum
+int conv_wgrad_splits(const ConvGeom& g, int cus);
+hipError_t launch_conv_wgrad(const float* gb, const float* r, const float* y, const float* rb, float* part, int splits,
+                             int accumulate, const ConvGeom& g, hipStream_t stream);
+hipError_t launch_conv_wgrad_sum(const float* part, int splits, const ConvGeom& g, float* gw, hipStream_t stream);
 hipError_t launch_patches_extract(const float* img, float* out, int64_t ld, float* means, const ConvGeom& g,
                                   int center, hipStream_t stream);
 hipError_t launch_patches_reconstruct(const float* pat, int64_t ld, const float* means, float* img,

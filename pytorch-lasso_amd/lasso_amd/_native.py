@@ -178,6 +178,14 @@ def _declare(lib):
                                                                     C.POINTER(C.c_float), vp, sz, vp]
     lib.lasso_conv_objective.restype = i32
     lib.lasso_conv_objective.argtypes = [vp, vp, vp] + geom + [i32, dbl, vp, vp, sz, vp]
+    lib.lasso_conv_ista_trace_bytes.restype = sz
+    lib.lasso_conv_ista_trace_bytes.argtypes = geom + [i32]
+    lib.lasso_conv_ista_run_traced.restype = i32
+    lib.lasso_conv_ista_run_traced.argtypes = [vp, vp, vp, vp] + geom + [i32, dbl, dbl, i32, i32, vp, vp, sz, vp]
+    lib.lasso_conv_ista_backward_workspace_bytes.restype = sz
+    lib.lasso_conv_ista_backward_workspace_bytes.argtypes = geom
+    lib.lasso_conv_ista_backward.restype = i32
+    lib.lasso_conv_ista_backward.argtypes = [vp, vp, vp, vp] + geom + [i32, dbl, i32, i32, vp, vp, vp, vp, sz, vp]
     lib.lasso_conv_lip_workspace_bytes.restype = sz
     lib.lasso_conv_lip_workspace_bytes.argtypes = [i64, i64, i32, i32]
     lib.lasso_conv_lip_bound.restype = i32

@@ -4,6 +4,7 @@ import ctypes as C
 
 import numpy as np
 import torch
+from torch.autograd.function import once_differentiable
 
 from .. import _native as nat
 from .lip_const import lip_bound_conv2d
@@ -52,27 +53,8 @@ def conv_loss(x, z, weight, alpha, stride=1, padding=0):
     return loss
 
 
-def ista_conv2d(x, z0, weight, alpha=1.0, stride=1, padding=0, fast=True,
-                maxiter=10, lr='auto', tol=1e-5, verbose=False, return_info=False):
-    """x [N,C,H,W], z0 [N,K,Hz,Wz], weight [K,C,kh,kw] -> z [N,K,Hz,Wz] (a new tensor;
-    ``maxiter=0`` returns ``z0`` itself, ista.py:32,49).  ``lr='auto'`` uses the Toeplitz
-    bound and, like the reference, needs ``stride == 1`` (:9-15).  ``return_info``
-    (extension) also returns ``dict(iterations=..., last_delta=...)``.  No CPU fallback."""
-    nat.require_gpu()
-    if lr == 'auto':
-        if stride != 1:
-            raise NotImplementedError("auto lr is only implemented for stride == 1.")   # :10-12
-        Lb = lip_bound_conv2d(weight, padding)                                           # :14
-        lr = float(np.float32(1.0) / np.float32(Lb.item()))                             # :15 (fp32 like the tensor op)
-    geom = _geometry(x, z0, weight, stride, padding)
-    if not (x.dtype == z0.dtype == weight.dtype == torch.float32):
-        raise NotImplementedError("lasso_amd: ista_conv2d is implemented for float32 tensors")
-    if maxiter == 0:
-        return (z0, dict(iterations=0, last_delta=float('nan'))) if return_info else z0
-    out_device = z0.device
-    dev = x.device if x.is_cuda else (weight.device if weight.is_cuda else
-                                      (z0.device if z0.is_cuda else torch.device('cuda', torch.cuda.current_device())))
-    xg, zg, wg = (t.detach().to(dev).contiguous() for t in (x, z0, weight))
+def _solve(xg, zg, wg, geom, alpha, lr, fast, maxiter, tol, verbose, dev):
+    """The solve on device tensors (contiguous fp32) -> (z, iterations, last_delta)."""
     L = nat.lib()
     z = torch.empty_like(zg)
     iters, last = C.c_int32(0), C.c_float(float('nan'))
@@ -89,7 +71,8 @@ def ista_conv2d(x, z0, weight, alpha=1.0, stride=1, padding=0, fast=True,
             # the reference prints the objective of z before every iteration (:37-38); one HIP
             # iteration at a time cannot carry the momentum state across calls, so the verbose
             # trace re-solves with maxiter = i for the printed value (debugging mode)
-            budget = float(np.float32(z0.numel() * tol))
+            stride, padding = geom[9:11], geom[11:13]
+            budget = float(np.float32(zg.numel() * tol))
             for i in range(int(maxiter)):
                 zi = zg
                 if i > 0:
@@ -103,8 +86,101 @@ def ista_conv2d(x, z0, weight, alpha=1.0, stride=1, padding=0, fast=True,
                                                   float(tol), C.byref(iters), C.byref(last), wsp, wsn, st))
                 if iters.value <= i or (tol > 0 and last.value <= budget):
                     break
+    return z, iters.value, last.value
+
+
+class _UnrolledConvIsta(torch.autograd.Function):
+    """Differentiable convolutional solve (SURVEY.md 8f rows f3 + f4): the reference's loop is plain
+    torch code, so torch.autograd differentiates through its unrolled iterations (ista.py:36-46).
+    Forward: the solve as without grad (its z, iteration count and last delta are returned), then
+    lasso_conv_ista_run_traced replays its T iterations keeping z_0..z_T; backward:
+    lasso_conv_ista_backward (csrc/conv_autograd.hip).  The step lr, the momentum schedule and the
+    stop decision are constants of the graph."""
+
+    @staticmethod
+    def forward(ctx, x, z0, weight, geom, alpha, lr, fast, maxiter, tol, verbose, info):
+        dev = x.device
+        xg, zg, wg = (t.detach().contiguous() for t in (x, z0, weight))
+        L = nat.lib()
+        z, iters, last = None, int(maxiter), float('nan')
+        # With the stop rule active T is not known in advance: the ordinary solve finds it first (bitwise
+        # deterministic, so the replay lands on the same iterates) -- the trace is then exactly T + 1 iterates
+        if tol > 0 or verbose or geom[0] == 0:
+            z, iters, last = _solve(xg, zg, wg, geom, alpha, lr, fast, maxiter, tol, verbose, dev)
+        steps = int(iters)
+        trace = torch.empty(L.lasso_conv_ista_trace_bytes(*geom, steps) // 4, dtype=torch.float32, device=dev)
+        if geom[0] > 0:
+            zt = torch.empty_like(zg)
+            with torch.cuda.device(dev):
+                ws = nat.workspace(dev, L.lasso_conv_ista_workspace_bytes(*geom), "conv")
+                nat.check(L.lasso_conv_ista_run_traced(nat.ptr(xg), nat.ptr(wg), nat.ptr(zg), nat.ptr(zt), *geom,
+                                                       nat.LASSO_F32, float(alpha), float(lr), int(bool(fast)), steps,
+                                                       nat.ptr(trace), nat.ptr(ws), ws.numel(), nat.stream_ptr(dev)))
+            if z is None:
+                z = zt
+        ctx.save_for_backward(xg, wg, trace)
+        ctx.geom, ctx.lr, ctx.fast, ctx.steps, ctx.zshape = geom, float(lr), bool(fast), steps, zg.shape
+        info.update(iterations=iters, last_delta=last)
+        return z
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_z):
+        xg, wg, trace = ctx.saved_tensors
+        dev = xg.device
+        L = nat.lib()
+        need_x, need_z0, need_w = ctx.needs_input_grad[:3]
+        gx = torch.empty_like(xg) if need_x else None
+        gw = torch.empty_like(wg) if need_w else None
+        gz0 = torch.empty(ctx.zshape, dtype=torch.float32, device=dev) if need_z0 else None
+        gz = grad_z.detach().to(device=dev, dtype=torch.float32).contiguous()
+        with torch.cuda.device(dev):
+            ws = nat.workspace(dev, L.lasso_conv_ista_backward_workspace_bytes(*ctx.geom), "conv_bw")
+            nat.check(L.lasso_conv_ista_backward(nat.ptr(xg), nat.ptr(wg), nat.ptr(trace), nat.ptr(gz), *ctx.geom,
+                                                 nat.LASSO_F32, ctx.lr, int(ctx.fast), ctx.steps, nat.ptr(gx),
+                                                 nat.ptr(gw), nat.ptr(gz0), nat.ptr(ws), ws.numel(),
+                                                 nat.stream_ptr(dev)))
+        return (gx, gz0, gw) + (None,) * 8
+
+
+def ista_conv2d(x, z0, weight, alpha=1.0, stride=1, padding=0, fast=True,
+                maxiter=10, lr='auto', tol=1e-5, verbose=False, return_info=False):
+    """x [N,C,H,W], z0 [N,K,Hz,Wz], weight [K,C,kh,kw] -> z [N,K,Hz,Wz] (a new tensor;
+    ``maxiter=0`` returns ``z0`` itself, ista.py:32,49).  ``lr='auto'`` uses the Toeplitz
+    bound and, like the reference, needs ``stride == 1`` (:9-15).  ``return_info``
+    (extension) also returns ``dict(iterations=..., last_delta=...)``.  No CPU fallback.
+
+    Differentiable like the reference's loop: with grad mode on and any of x, z0, weight
+    requiring grad, z carries the derivative of the iterations run (the step, the momentum
+    schedule and the stop decision are constants; double backward is not supported).  With
+    ``lr='auto'`` the step is computed from the detached weight and is a constant too -- an
+    extension: the reference raises TypeError there when weight requires grad."""
+    nat.require_gpu()
+    wants_grad = torch.is_grad_enabled() and (x.requires_grad or z0.requires_grad or weight.requires_grad)
+    if lr == 'auto':
+        if stride != 1:
+            raise NotImplementedError("auto lr is only implemented for stride == 1.")   # :10-12
+        Lb = lip_bound_conv2d(weight, padding)                                           # :14
+        lr = float(np.float32(1.0) / np.float32(Lb.item()))                             # :15 (fp32 like the tensor op)
+    geom = _geometry(x, z0, weight, stride, padding)
+    if not (x.dtype == z0.dtype == weight.dtype == torch.float32):
+        raise NotImplementedError("lasso_amd: ista_conv2d is implemented for float32 tensors")
+    if maxiter == 0:
+        return (z0, dict(iterations=0, last_delta=float('nan'))) if return_info else z0
+    out_device = z0.device
+    dev = x.device if x.is_cuda else (weight.device if weight.is_cuda else
+                                      (z0.device if z0.is_cuda else torch.device('cuda', torch.cuda.current_device())))
+    if wants_grad:
+        # CPU inputs are staged through the device inside the graph: their gradients arrive on their own devices
+        info = {}
+        z = _UnrolledConvIsta.apply(x.to(dev), z0.to(dev), weight.to(dev), geom, float(alpha), float(lr), bool(fast),
+                                    int(maxiter), float(tol), bool(verbose), info)
+        iters, last = info['iterations'], info['last_delta']
+    else:
+        xg, zg, wg = (t.detach().to(dev).contiguous() for t in (x, z0, weight))
+        z, iters, last = _solve(xg, zg, wg, geom, alpha, lr, fast, maxiter, tol, verbose, dev)
     if z.device != out_device:
         z = z.to(out_device)
     if return_info:
-        return z, dict(iterations=iters.value, last_delta=last.value)
+        return z, dict(iterations=iters, last_delta=last)
     return z
