@@ -19,7 +19,11 @@
  *   - dtype: LASSO_F32; LASSO_BF16 (x, W, z0, z_out all bf16, leading dimensions in bf16
  *     elements) is accepted by lasso_fista_solve on the fused shapes (bf16-MFMA kernels,
  *     fp32 accumulation and state; fixed step or line search) and LASSO_ERR_UNSUPPORTED
- *     elsewhere;
+ *     elsewhere; LASSO_F64 (all tensors double, leading dimensions in doubles) is accepted by
+ *     lasso_fista_workspace_bytes / _kernel_name / _solve (any d, k: fp64-MFMA general-GEMM path, csrc/gemm_f64.hip;
+ *     every value, sum and comparison in IEEE double), lasso_lipschitz, lasso_objective(_throttled) and
+ *     lasso_init_transpose, and LASSO_ERR_UNSUPPORTED elsewhere; results that an fp32 signature carries as
+ *     float have double siblings (lasso_fista_solve_f64, lasso_objective_f64);
  *   - shapes: d <= 256 and k <= 1024 run the fused kernels; beyond that lasso_fista_solve
  *     (fixed step, and the line search on fp32 tensors), lasso_objective and
  *     lasso_gram_accumulate take any d, k (unfused MFMA GEMM paths), lasso_dict_sweep
@@ -58,7 +62,7 @@ typedef enum {
                                  verdict kernel itself -- no lasso_fista_solve_collect needed          */
 } lasso_status;
 
-typedef enum { LASSO_F32 = 0, LASSO_BF16 = 1 } lasso_dtype;
+typedef enum { LASSO_F32 = 0, LASSO_BF16 = 1, LASSO_F64 = 2 } lasso_dtype;
 
 /* How the global stopping rule of ista.py:93 is evaluated. */
 typedef enum {
@@ -190,6 +194,23 @@ int lasso_fista_solve(const void* x_dev, int64_t ldx,
                       float* objective_out,
                       void* workspace_dev, size_t workspace_bytes, void* stream);
 
+/* lasso_fista_solve on float64 tensors (dtype LASSO_F64 is implied) with the host results as doubles: the last sum
+ * |z - z_next|, the accepted step and F(z_next) per outer iteration, the mean objective.  lasso_fista_solve itself
+ * accepts LASSO_F64 and runs the same solve, rounding these to its float slots.  Fixed step or line search, fast on /
+ * off, z0 or NULL, tol > 0 (the stop rule compares double sums, once per chunk of speculated iterations),
+ * lr = LASSO_LR_AUTO (one host round trip), any d, k.  stop_mode: LASSO_STOP_* only -- the asynchronous / sharded flags
+ * and the LASSO_KERNEL_TILE / _SPLITK hints answer LASSO_ERR_UNSUPPORTED.  Two solves of the same arguments give
+ * bitwise the same code.  Workspace: lasso_fista_workspace_bytes(..., LASSO_F64, ...). */
+int lasso_fista_solve_f64(const void* x_dev, int64_t ldx, const void* w_dev, int64_t ldw,
+                          const void* z0_dev, int64_t ldz0, void* z_out_dev, int64_t ldz,
+                          int64_t n, int64_t d, int64_t k,
+                          double alpha, double lr, int fast, int maxiter, double tol, int stop_mode,
+                          int backtrack, double eta_backtrack,
+                          int32_t* iters_out, double* last_delta_out,
+                          int32_t* trials_out, double* accepted_lr_out, double* accepted_f_out,
+                          double* objective_out,
+                          void* workspace_dev, size_t workspace_bytes, void* stream);
+
 /* ---- building blocks for multi-GPU / custom drivers ---------------------------------
  * lasso_fista_prepare packs W into the padded layouts the kernels stream
  * (W [256][Kp] and W^T [Kp][256]) at the start of `workspace_dev` and builds the
@@ -217,7 +238,7 @@ int lasso_fista_run(const void* x_dev, int64_t ldx,
                     void* workspace_dev, size_t workspace_bytes, void* stream);
 
 /* ---- Lipschitz constant: replaces _lipschitz_constant, ista.py:8-14 -----------------
- * L = lambda_max(W^T W), deterministic, fp64, computed on the device (Gram of the
+ * L = lambda_max(W^T W) of an fp32 or float64 (LASSO_F64) dictionary, deterministic, fp64, computed on the device (Gram of the
  * smaller side + repeated squaring; see csrc/lipschitz.hip).  Synchronises `stream`
  * to return the value through the HOST pointer l_out (the reference returns a python
  * float the same way).  ((double*)workspace_dev)[0] also holds the value on the device.
@@ -243,6 +264,15 @@ int lasso_objective_throttled(const void* x_dev, int64_t ldx, const void* w_dev,
                               const void* z_dev, int64_t ldz, int64_t n, int64_t d, int64_t k, int dtype,
                               double alpha, float* loss_dev, double* sums_dev, int max_workgroups,
                               void* workspace_dev, size_t workspace_bytes, void* stream);
+
+/* float64 tensors: lasso_objective / _throttled accept LASSO_F64 with a workspace of
+ * lasso_objective_f64_workspace_bytes and round the loss to the float at loss_dev (max_workgroups does not apply);
+ * lasso_objective_f64 leaves it as a device double.  The residual, both sums and the loss are computed in double. */
+size_t lasso_objective_f64_workspace_bytes(int64_t n, int64_t d, int64_t k);
+int lasso_objective_f64(const void* x_dev, int64_t ldx, const void* w_dev, int64_t ldw,
+                        const void* z_dev, int64_t ldz, int64_t n, int64_t d, int64_t k,
+                        double alpha, double* loss_dev, double* sums_dev,
+                        void* workspace_dev, size_t workspace_bytes, void* stream);
 
 /* ---- constrained M-step in Gram form: replaces update_dict, dict_learning.py:56-103 --
  * lasso_gram_accumulate: A = Z^T Z [k][k] (ld k), B = Z^T X [k][d] (ld d) of this row
@@ -455,7 +485,8 @@ int lasso_fista_solve_finish(int64_t n, int64_t d, int64_t k, int dtype, int max
                              size_t workspace_bytes, void* stream);
 
 /* ---- init='transpose': replaces torch.matmul(x, weight), sparse_encode.py:24-25 ---------
- * z0 [n][k] (ldz) = x [n][d] W [d][k] on the library's fp32-MFMA NT GEMM (csrc/gemm.hip).
+ * z0 [n][k] (ldz) = x [n][d] W [d][k] on the library's fp32-MFMA NT GEMM (csrc/gemm.hip); LASSO_F64: on the
+ * fp64-MFMA GEMM (csrc/gemm_f64.hip).
  */
 size_t lasso_init_transpose_workspace_bytes(int64_t d, int64_t k);
 int lasso_init_transpose(int64_t n, int64_t d, int64_t k, int dtype, const void* x_dev, int64_t ldx,

@@ -1238,24 +1238,7 @@ int speculate_stop_rule(int maxiter, float budget, float* delta_dev, hipStream_t
     if (hit < 0) {
       it += c;
       last = deltas[c - 1];
-      // Size of the next chunk -- only speed depends on it; a stop inside a chunk costs one chunk (the speculated rest
-      // plus the replay).  Within a factor 2 of the budget: one iteration at a time (the reference's own cadence: the
-      // sums of a momentum run are not monotone, and an iteration speculated past the stop costs more than the wait it
-      // saves).  Further away: the iterations the rule is still away at the chunk's average decay -- that many when it
-      // is near (so that it fires at the chunk's END: nothing to replay), half as many when it is far; without a
-      // decaying chunk behind us, as many iterations as the solve has done; at most half the iterations done, and
-      // never fewer than the sums would need if they halved every iteration.
-      int next = 1;
-      if (last > 2.0f * budget) {
-        next = std::min(kChunkMax, std::max(2, it));
-        if (c > 1 && deltas[0] > 0.0f && last < deltas[0] && budget > 0.0f) {
-          const double rate = log((double)deltas[0] / (double)last) / (double)(c - 1);
-          const double away = log((double)last / (double)budget) / rate;
-          next = away <= 8.0 ? std::max(1, (int)ceil(away)) : (int)std::min((double)kChunkMax, away / 2.0);
-        }
-        const int lg = budget > 0.0f ? (int)std::min((double)kChunkMax, log2((double)last / (double)budget)) : kChunkMax;
-        next = std::max(lg, std::min(next, std::max(2, it / 2)));
-      }
+      const int next = next_stop_chunk<float>(deltas[0], last, budget, c, it, kChunkMax);   // (lasso_kernels.h)
       chunk = next;
       continue;
     }
@@ -1754,8 +1737,22 @@ __global__ void step_from_lipschitz_kernel(const double* __restrict__ L, double 
   out[1] = (float)(alpha * lr);
 }
 
+// LASSO_F64: the solver's workspace, then the objective's behind a 256-byte slot for the device double of the loss
+// (objective_out), then the Lipschitz computation's, whose first double is lambda_max (lr = LASSO_LR_AUTO; absent when
+// min(d, k) > 2048)
+struct F64Regions { size_t solver, objective, lipschitz, total; };
+static F64Regions f64_workspace(int64_t n, int64_t d, int64_t k, int maxiter, double tol, int stop_mode, int backtrack) {
+  F64Regions r;
+  r.solver = align_up(f64::solve_workspace_bytes(n, d, k, maxiter, tol, stop_mode, backtrack));
+  r.objective = align_up(f64::objective_workspace_bytes(n, d, k)) + 256;
+  r.lipschitz = std::min(d, k) > 2048 ? 0 : align_up(lipschitz_workspace_bytes(d, k));
+  r.total = r.solver + r.objective + r.lipschitz;
+  return r;
+}
+
 const char* lasso_fista_kernel_name(int64_t n, int64_t d, int64_t k, int dtype, int backtrack) {
   if (n <= 0 || d <= 0 || k <= 0) return "";
+  if (dtype == LASSO_F64) return f64::solve_kernel_name(backtrack);
   if (!fused_shape(d, k)) return "lasso::gemm_nt_kernel + lasso::gemm_nt_kernel<.., prox epilogue> (unfused)";
   if (dtype == LASSO_BF16) {
     int per_cu = 0;
@@ -1804,6 +1801,7 @@ const char* lasso_fista_kernel_name(int64_t n, int64_t d, int64_t k, int dtype, 
 size_t lasso_fista_workspace_bytes(int64_t n, int64_t d, int64_t k, int dtype, int maxiter,
                                    double tol, int stop_mode, int backtrack) {
   if (n < 0 || d <= 0 || k <= 0) return 0;
+  if (dtype == LASSO_F64) return f64_workspace(n, d, k, maxiter, tol, stop_mode, backtrack).total;
   const size_t solver = solver_workspace_bytes(n, d, k, dtype, maxiter, tol, stop_mode, backtrack);
   if (solver == 0) return 0;
   return align_up(solver) + objective_region_bytes(n, d, k, dtype) + lipschitz_region_bytes(d, k, dtype);
@@ -2152,6 +2150,70 @@ static int solve_impl(const void* x_dev, int64_t ldx, const void* w_dev, int64_t
   return LASSO_OK;
 }
 
+// float64 tensors: see lasso_fista_solve_f64 in include/lasso_hip.h
+int lasso_fista_solve_f64(const void* x_dev, int64_t ldx, const void* w_dev, int64_t ldw, const void* z0_dev,
+                          int64_t ldz0, void* z_out_dev, int64_t ldz, int64_t n, int64_t d, int64_t k, double alpha,
+                          double lr, int fast, int maxiter, double tol, int stop_mode, int backtrack,
+                          double eta_backtrack, int32_t* iters_out, double* last_delta_out, int32_t* trials_out,
+                          double* accepted_lr_out, double* accepted_f_out, double* objective_out, void* workspace_dev,
+                          size_t workspace_bytes, void* stream) {
+  if (objective_out) *objective_out = NAN;
+  if (stop_mode & ~0xFF & ~LASSO_KERNEL_MASK)
+    return fail(LASSO_ERR_UNSUPPORTED, "LASSO_F64: asynchronous and sharded solves are fp32 only");
+  if ((stop_mode & 0x300) == LASSO_KERNEL_TILE || (stop_mode & 0x300) == LASSO_KERNEL_SPLITK)
+    return fail(LASSO_ERR_UNSUPPORTED, "LASSO_F64: the fused tile / split-k kernels are fp32 only");
+  stop_mode &= 0xFF;
+  if (n < 0 || d <= 0 || k <= 0) return fail(LASSO_ERR_BAD_ARG, "bad shape n=%lld d=%lld k=%lld", (long long)n,
+                                              (long long)d, (long long)k);
+  if (!w_dev || !workspace_dev || (n > 0 && (!x_dev || !z_out_dev))) return fail(LASSO_ERR_BAD_ARG, "null pointer");
+  if (ldx < d || ldw < k || ldz < k || (z0_dev && ldz0 < k)) return fail(LASSO_ERR_BAD_ARG, "leading dimension too small");
+  if (maxiter < 0) return fail(LASSO_ERR_BAD_ARG, "maxiter < 0");
+  if (backtrack && !(eta_backtrack > 1.0)) return fail(LASSO_ERR_BAD_ARG, "eta must be > 1.");     // ista.py:18-19
+  if (stop_mode == LASSO_STOP_NONE) tol = 0.0;
+  const F64Regions reg = f64_workspace(n, d, k, maxiter, tol, stop_mode, backtrack);
+  hipStream_t st = (hipStream_t)stream;
+  if (lr == LASSO_LR_AUTO) {                            // lr = 1 / lambda_max(W^T W) (ista.py:59-63), one host round trip
+    if (reg.lipschitz == 0) return fail(LASSO_ERR_UNSUPPORTED, "lr = LASSO_LR_AUTO: min(d,k) > 2048");
+    if (workspace_bytes < reg.total) return fail(LASSO_ERR_WORKSPACE, "workspace %zu < %zu bytes", workspace_bytes, reg.total);
+    char* const lip_ws = (char*)workspace_dev + reg.solver + reg.objective;
+    LASSO_HIP_TRY(launch_lipschitz_f64((const double*)w_dev, ldw, d, k, lip_ws, 20, st));
+    double L = 0.0;
+    LASSO_HIP_TRY(hipMemcpyAsync(&L, lip_ws, sizeof(double), hipMemcpyDeviceToHost, st));
+    LASSO_HIP_TRY(hipStreamSynchronize(st));
+    lr = 1.0 / L;
+  }
+  if (n == 0) {                                         // nothing to solve (the reference's loop stops at once: 0 <= 0)
+    if (iters_out) *iters_out = maxiter > 0 ? 1 : 0;
+    if (last_delta_out) *last_delta_out = maxiter > 0 ? 0.0 : NAN;
+    return LASSO_OK;
+  }
+  char msg[400] = "";
+  int status;
+  if (backtrack)
+    status = f64::solve_backtracking((const double*)x_dev, ldx, (const double*)w_dev, ldw, (const double*)z0_dev, ldz0,
+                                     (double*)z_out_dev, ldz, n, d, k, alpha, lr, fast, maxiter, tol, eta_backtrack,
+                                     iters_out, last_delta_out, trials_out, accepted_lr_out, accepted_f_out,
+                                     workspace_dev, std::min(workspace_bytes, reg.solver), st, msg, sizeof(msg));
+  else
+    status = f64::solve((const double*)x_dev, ldx, (const double*)w_dev, ldw, (const double*)z0_dev, ldz0,
+                        (double*)z_out_dev, ldz, n, d, k, alpha, lr, fast, maxiter, tol, iters_out, last_delta_out,
+                        workspace_dev, std::min(workspace_bytes, reg.solver), st, msg, sizeof(msg));
+  if (status != LASSO_OK) fail(status, "%s", msg);
+  if ((status != LASSO_OK && status != LASSO_WARN_LINESEARCH) || !objective_out) return status;
+  // objective_out: the mean objective of the RETURNED code, in double (ista.py:66-69)
+  if (workspace_bytes < reg.solver + reg.objective)
+    return fail(LASSO_ERR_WORKSPACE, "objective_out: workspace %zu < %zu bytes", workspace_bytes, reg.solver + reg.objective);
+  double* const loss_dev = (double*)((char*)workspace_dev + reg.solver);
+  char msg2[400] = "";
+  if (int s2 = f64::objective((const double*)x_dev, ldx, (const double*)w_dev, ldw, (const double*)z_out_dev, ldz, n, d,
+                              k, alpha, loss_dev, nullptr, nullptr, (char*)loss_dev + 256, reg.objective - 256, st, msg2,
+                              sizeof(msg2)))
+    return fail(s2, "%s", msg2);
+  LASSO_HIP_TRY(hipMemcpyAsync(objective_out, loss_dev, sizeof(double), hipMemcpyDeviceToHost, st));
+  LASSO_HIP_TRY(hipStreamSynchronize(st));
+  return status;
+}
+
 int lasso_fista_solve(const void* x_dev, int64_t ldx, const void* w_dev, int64_t ldw,
                       const void* z0_dev, int64_t ldz0, void* z_out_dev, int64_t ldz, int64_t n,
                       int64_t d, int64_t k, int dtype, double alpha, double lr, int fast,
@@ -2159,6 +2221,27 @@ int lasso_fista_solve(const void* x_dev, int64_t ldx, const void* w_dev, int64_t
                       int32_t* iters_out, float* last_delta_out, int32_t* trials_out,
                       float* accepted_lr_out, float* accepted_f_out, float* objective_out, void* workspace_dev,
                       size_t workspace_bytes, void* stream) {
+  if (dtype == LASSO_F64) {
+    // the same solve; the float slots receive the doubles rounded once (lasso_fista_solve_f64 keeps them)
+    const int cap = std::max(maxiter, 1);
+    std::vector<double> lr64(accepted_lr_out ? cap : 0), f64v(accepted_f_out ? cap : 0);
+    double last64 = NAN, obj64 = NAN;
+    int32_t iters = 0;
+    const int status = lasso_fista_solve_f64(x_dev, ldx, w_dev, ldw, z0_dev, ldz0, z_out_dev, ldz, n, d, k, alpha, lr, fast,
+                                             maxiter, tol, stop_mode, backtrack, eta_backtrack, &iters, &last64, trials_out,
+                                             accepted_lr_out ? lr64.data() : nullptr, accepted_f_out ? f64v.data() : nullptr,
+                                             objective_out ? &obj64 : nullptr, workspace_dev, workspace_bytes, stream);
+    if (status != LASSO_OK && status != LASSO_WARN_LINESEARCH) return status;
+    if (iters_out) *iters_out = iters;
+    if (last_delta_out) *last_delta_out = (float)last64;
+    if (objective_out) *objective_out = (float)obj64;
+    if (backtrack)
+      for (int i = 0; i < iters && i < cap; ++i) {
+        if (accepted_lr_out) accepted_lr_out[i] = (float)lr64[i];
+        if (accepted_f_out) accepted_f_out[i] = (float)f64v[i];
+      }
+    return status;
+  }
   if (objective_out) *objective_out = NAN;
   const bool async = (stop_mode & LASSO_SOLVE_ASYNC) != 0;
   const bool sharded = (stop_mode & LASSO_SOLVE_SHARDED) != 0;
@@ -2382,14 +2465,15 @@ size_t lasso_lipschitz_workspace_bytes(int64_t d, int64_t k) {
 
 int lasso_lipschitz(const void* w_dev, int64_t ldw, int64_t d, int64_t k, int dtype, double* l_out,
                     void* workspace_dev, size_t workspace_bytes, void* stream) {
-  if (dtype != LASSO_F32) return fail(LASSO_ERR_UNSUPPORTED, "dtype %d", dtype);
+  if (dtype != LASSO_F32 && dtype != LASSO_F64) return fail(LASSO_ERR_UNSUPPORTED, "dtype %d", dtype);
   if (!w_dev || !workspace_dev || d <= 0 || k <= 0 || ldw < k)
     return fail(LASSO_ERR_BAD_ARG, "bad argument");
   if (std::min(d, k) > 2048) return fail(LASSO_ERR_UNSUPPORTED, "min(d,k) > 2048");
   if (workspace_bytes < lipschitz_workspace_bytes(d, k))
     return fail(LASSO_ERR_WORKSPACE, "need %zu bytes", lipschitz_workspace_bytes(d, k));
   hipStream_t st = (hipStream_t)stream;
-  LASSO_HIP_TRY(launch_lipschitz((const float*)w_dev, ldw, d, k, workspace_dev, 20, st));
+  if (dtype == LASSO_F64) LASSO_HIP_TRY(launch_lipschitz_f64((const double*)w_dev, ldw, d, k, workspace_dev, 20, st));
+  else LASSO_HIP_TRY(launch_lipschitz((const float*)w_dev, ldw, d, k, workspace_dev, 20, st));
   if (l_out) {
     LASSO_HIP_TRY(hipMemcpyAsync(l_out, workspace_dev, sizeof(double), hipMemcpyDeviceToHost, st));
     LASSO_HIP_TRY(hipStreamSynchronize(st));
@@ -2413,10 +2497,42 @@ size_t lasso_objective_workspace_bytes(int64_t n, int64_t d, int64_t k) {
          align_up((size_t)std::max<int64_t>(ntiles, 1) * 2 * 4) + 256;
 }
 
+size_t lasso_objective_f64_workspace_bytes(int64_t n, int64_t d, int64_t k) {
+  if (n < 0 || d <= 0 || k <= 0) return 0;
+  return f64::objective_workspace_bytes(n, d, k);
+}
+
+// float64 tensors: the loss as a device double (loss_dev) and / or rounded to a device float (loss32_dev)
+static int objective_f64_impl(const void* x_dev, int64_t ldx, const void* w_dev, int64_t ldw, const void* z_dev,
+                              int64_t ldz, int64_t n, int64_t d, int64_t k, double alpha, double* loss_dev,
+                              float* loss32_dev, double* sums_dev, void* workspace_dev, size_t workspace_bytes,
+                              void* stream) {
+  if (n < 0 || d <= 0 || k <= 0) return fail(LASSO_ERR_BAD_ARG, "bad shape n=%lld d=%lld k=%lld", (long long)n,
+                                              (long long)d, (long long)k);
+  if (!x_dev || !w_dev || !z_dev || !workspace_dev) return fail(LASSO_ERR_BAD_ARG, "null pointer");
+  if (ldx < d || ldw < k || ldz < k) return fail(LASSO_ERR_BAD_ARG, "leading dimension too small");
+  char msg[400] = "";
+  if (int s = f64::objective((const double*)x_dev, ldx, (const double*)w_dev, ldw, (const double*)z_dev, ldz, n, d, k,
+                             alpha, loss_dev, loss32_dev, sums_dev, workspace_dev, workspace_bytes, (hipStream_t)stream,
+                             msg, sizeof(msg)))
+    return fail(s, "%s", msg);
+  return LASSO_OK;
+}
+
+int lasso_objective_f64(const void* x_dev, int64_t ldx, const void* w_dev, int64_t ldw, const void* z_dev, int64_t ldz,
+                        int64_t n, int64_t d, int64_t k, double alpha, double* loss_dev, double* sums_dev,
+                        void* workspace_dev, size_t workspace_bytes, void* stream) {
+  return objective_f64_impl(x_dev, ldx, w_dev, ldw, z_dev, ldz, n, d, k, alpha, loss_dev, nullptr, sums_dev, workspace_dev,
+                            workspace_bytes, stream);
+}
+
 static int objective_impl(const void* x_dev, int64_t ldx, const void* w_dev, int64_t ldw, const void* z_dev,
                           int64_t ldz, int64_t n, int64_t d, int64_t k, int dtype, double alpha,
                           float* loss_dev, double* sums_dev, int max_workgroups, void* workspace_dev,
                           size_t workspace_bytes, void* stream) {
+  if (dtype == LASSO_F64)      // (workspace: lasso_objective_f64_workspace_bytes; max_workgroups does not apply)
+    return objective_f64_impl(x_dev, ldx, w_dev, ldw, z_dev, ldz, n, d, k, alpha, nullptr, loss_dev, sums_dev, workspace_dev,
+                              workspace_bytes, stream);
   if (int s = check_common(n, d, k, dtype, /*allow_large=*/true)) return s;
   if (!x_dev || !w_dev || !z_dev || !workspace_dev) return fail(LASSO_ERR_BAD_ARG, "null pointer");
   if (ldx < d || ldw < k || ldz < k) return fail(LASSO_ERR_BAD_ARG, "leading dimension too small");
@@ -2865,7 +2981,7 @@ size_t lasso_init_transpose_workspace_bytes(int64_t d, int64_t k) {
 int lasso_init_transpose(int64_t n, int64_t d, int64_t k, int dtype, const void* x_dev, int64_t ldx,
                          const void* w_dev, int64_t ldw, void* z0_dev, int64_t ldz, void* workspace_dev,
                          size_t workspace_bytes, void* stream) {
-  if (dtype != LASSO_F32) return fail(LASSO_ERR_UNSUPPORTED, "dtype %d", dtype);
+  if (dtype != LASSO_F32 && dtype != LASSO_F64) return fail(LASSO_ERR_UNSUPPORTED, "dtype %d", dtype);
   if (n < 0 || d <= 0 || k <= 0 || n > INT32_MAX || d > INT32_MAX || k > INT32_MAX)
     return fail(LASSO_ERR_BAD_ARG, "bad shape");
   if (!w_dev || !workspace_dev || (n > 0 && (!x_dev || !z0_dev))) return fail(LASSO_ERR_BAD_ARG, "null pointer");
@@ -2874,6 +2990,13 @@ int lasso_init_transpose(int64_t n, int64_t d, int64_t k, int dtype, const void*
     return fail(LASSO_ERR_WORKSPACE, "need %zu bytes", lasso_init_transpose_workspace_bytes(d, k));
   if (n == 0) return LASSO_OK;
   hipStream_t st = static_cast<hipStream_t>(stream);
+  if (dtype == LASSO_F64) {                                 // reads W as it is: the workspace is not used
+    char msg[400] = "";
+    if (int s = f64::init_transpose((const double*)x_dev, ldx, (const double*)w_dev, ldw, (double*)z0_dev, ldz, n, d, k,
+                                    st, msg, sizeof(msg)))
+      return fail(s, "%s", msg);
+    return LASSO_OK;
+  }
   float* const Wt = (float*)workspace_dev;                  // [k][d]: z0 = x Wt^T on the NT GEMM
   LASSO_HIP_TRY(launch_transpose_pad((const float*)w_dev, ldw, (int)d, (int)k, Wt, d, (int)k, (int)d, st));
   LASSO_HIP_TRY(launch_gemm_nt_sub((const float*)x_dev, ldx, Wt, d, nullptr, 0, (float*)z0_dev, ldz, (int)n, (int)k,

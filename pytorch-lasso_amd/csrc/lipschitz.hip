@@ -713,8 +713,11 @@ size_t lipschitz_workspace_bytes(int64_t d, int64_t k) {
 }
 
 // Enqueue the whole computation; the result lands in ((double*)workspace)[0].
-hipError_t launch_lipschitz(const float* W, int64_t ldw, int64_t d, int64_t k, void* workspace,
-                            int squarings, hipStream_t stream, const PrepareJob* job, bool* fused, LipLr lr) {
+// TW = float, or double for a float64 dictionary (LASSO_F64): then the Gram product is syrk_f64_kernel<double, false>
+template <typename TW>
+static hipError_t launch_lipschitz_t(const TW* W, int64_t ldw, int64_t d, int64_t k, void* workspace,
+                                     int squarings, hipStream_t stream, const PrepareJob* job, bool* fused, LipLr lr) {
+  constexpr bool kF32 = sizeof(TW) == sizeof(float);
   if (fused) *fused = false;
   const bool rows = d <= k;                 // G = W W^T (rows) or W^T W (columns)
   const int m = (int)(rows ? d : k), len = (int)(rows ? k : d);
@@ -728,9 +731,12 @@ hipError_t launch_lipschitz(const float* W, int64_t ldw, int64_t d, int64_t k, v
   lip_splits(len, &gs, &gspans);
   lip_splits(mp, &ps, &pspans);
   const dim3 fold_grid((unsigned)((mm + 255) / 256));
-  const bool span_ok = gspans == 1 && (ldw & 3) == 0 && (((uintptr_t)W) & 15) == 0 && (rows ? (len & 3) == 0 : (m & 3) == 0) &&
+  const bool span_ok = kF32 && gspans == 1 && (ldw & 3) == 0 && (((uintptr_t)W) & 15) == 0 && (rows ? (len & 3) == 0 : (m & 3) == 0) &&
                        len >= 4 && m >= 4;
-  if (span_ok) {                            // one span per workgroup: the low-latency kernel
+  if constexpr (!kF32) {
+    hipLaunchKernelGGL((syrk_f64_kernel<double, false>), dim3(mp / kLipTile, mp / kLipTile, gs), dim3(256), 0, stream,
+                       W, rows ? ldw : (int64_t)1, rows ? (int64_t)1 : ldw, m, len, mp, gspans, gs > 1 ? part : G);
+  } else if (span_ok) {                     // one span per workgroup: the low-latency kernel
     const size_t lds = (size_t)64 * 257 * sizeof(double);
     const void* fn = rows ? (const void*)&gram_span_f64_kernel<true> : (const void*)&gram_span_f64_kernel<false>;
     if (hipError_t e = ensure_dynamic_lds(fn, lds); e != hipSuccess) return e;
@@ -808,6 +814,16 @@ hipError_t launch_lipschitz(const float* W, int64_t ldw, int64_t d, int64_t k, v
   }
   launch_rayleigh(G, src, mp, out, part, stream, lr);
   return hipGetLastError();
+}
+
+hipError_t launch_lipschitz(const float* W, int64_t ldw, int64_t d, int64_t k, void* workspace,
+                            int squarings, hipStream_t stream, const PrepareJob* job, bool* fused, LipLr lr) {
+  return launch_lipschitz_t<float>(W, ldw, d, k, workspace, squarings, stream, job, fused, lr);
+}
+
+hipError_t launch_lipschitz_f64(const double* W, int64_t ldw, int64_t d, int64_t k, void* workspace, int squarings,
+                                hipStream_t stream) {
+  return launch_lipschitz_t<double>(W, ldw, d, k, workspace, squarings, stream, nullptr, nullptr, LipLr{nullptr, 0.0});
 }
 
 }  // namespace lasso

@@ -15,7 +15,7 @@ import torch
 LASSO_OK, LASSO_ERR_BAD_ARG, LASSO_ERR_UNSUPPORTED = 0, 1, 2
 LASSO_ERR_WORKSPACE, LASSO_ERR_HIP, LASSO_WARN_LINESEARCH = 3, 4, 5
 LASSO_PENDING, LASSO_WARN_ABORTED, LASSO_PENDING_MAPPED, LASSO_PENDING_DEFERRED = 6, 7, 8, 9
-LASSO_F32, LASSO_BF16 = 0, 1
+LASSO_F32, LASSO_BF16, LASSO_F64 = 0, 1, 2
 STOP_GLOBAL, STOP_NONE, STOP_GLOBAL_CHUNKED = 0, 1, 2
 ABI_VERSION = 7
 KERNEL_AUTO, KERNEL_TILE, KERNEL_SPLITK = 0, 0x100, 0x200
@@ -71,6 +71,16 @@ def _declare(lib):
         dbl, dbl, i32, i32, dbl, i32, i32, dbl, C.POINTER(C.c_int32), C.POINTER(C.c_float),
         C.POINTER(C.c_int32), C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float),
         vp, sz, vp]
+    pdbl = C.POINTER(dbl)
+    lib.lasso_fista_solve_f64.restype = i32
+    lib.lasso_fista_solve_f64.argtypes = [
+        vp, i64, vp, i64, vp, i64, vp, i64, i64, i64, i64,
+        dbl, dbl, i32, i32, dbl, i32, i32, dbl, C.POINTER(C.c_int32), pdbl,
+        C.POINTER(C.c_int32), pdbl, pdbl, pdbl, vp, sz, vp]
+    lib.lasso_objective_f64_workspace_bytes.restype = sz
+    lib.lasso_objective_f64_workspace_bytes.argtypes = [i64, i64, i64]
+    lib.lasso_objective_f64.restype = i32
+    lib.lasso_objective_f64.argtypes = [vp, i64, vp, i64, vp, i64, i64, i64, i64, dbl, vp, vp, vp, sz, vp]
     lib.lasso_fista_prepare.restype = i32
     lib.lasso_fista_prepare.argtypes = [vp, i64, i64, i64, i32, i32, vp, sz, vp]
     lib.lasso_fista_run.restype = i32

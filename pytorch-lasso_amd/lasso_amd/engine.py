@@ -359,15 +359,31 @@ class HipEngine:
 
     def objective_sums(self, X, Z, W, alpha, loss_out=None, max_workgroups=0):
         """-> (loss_local 0-d float tensor, sums double[2] = {sum r^2, sum |z|}) on device.
-        ``loss_out``: an optional 0-d fp32 device tensor (e.g. one slot of a loss history) the loss is
-        written to directly."""
+        ``loss_out``: an optional 0-d device tensor of the tensors' dtype (e.g. one slot of a loss history) the
+        loss is written to directly.  float64 tensors: residual, sums and loss in double, a 0-d float64 loss
+        (lasso_objective_f64)."""
         n, d = X.shape
         k = W.shape[1]
         L = self.lib
+        f64 = [t.dtype == torch.float64 for t in (X, Z, W)]
+        if any(f64) and not all(f64):
+            raise RuntimeError("expected X, Z, weight of one dtype")
         with torch.cuda.device(self.device):
+            sums = torch.empty(2, dtype=torch.float64, device=self.device)
+            if all(f64):
+                ws = self._ws(L.lasso_objective_f64_workspace_bytes(n, d, k), "obj")
+                if loss_out is not None and loss_out.dtype != torch.float64:
+                    raise RuntimeError("objective_sums: float64 tensors need a float64 loss_out, got %s" % loss_out.dtype)
+                loss = loss_out if loss_out is not None else torch.empty((), dtype=torch.float64, device=self.device)
+                if n == 0:      # an empty batch: nothing to launch, the reference's 0 / 0
+                    loss.fill_(float('nan'))
+                    return loss, sums.zero_()
+                nat.check(L.lasso_objective_f64(nat.ptr(X), X.stride(0), nat.ptr(W), W.stride(0), nat.ptr(Z), Z.stride(0),
+                                                n, d, k, float(alpha), nat.ptr(loss), nat.ptr(sums), nat.ptr(ws),
+                                                ws.numel(), self._stream()))
+                return loss, sums
             ws = self._ws(L.lasso_objective_workspace_bytes(n, d, k), "obj")
             loss = loss_out if loss_out is not None else torch.empty((), dtype=torch.float32, device=self.device)
-            sums = torch.empty(2, dtype=torch.float64, device=self.device)
             nat.check(L.lasso_objective_throttled(nat.ptr(X), X.stride(0), nat.ptr(W), W.stride(0),
                                                   nat.ptr(Z), Z.stride(0), n, d, k, nat.LASSO_F32, float(alpha),
                                                   nat.ptr(loss), nat.ptr(sums), int(max_workgroups), nat.ptr(ws),
@@ -430,14 +446,14 @@ class HipEngine:
                                                   nat.ptr(mask), self._stream()))
 
     def init_transpose(self, X, W):
-        """z0 = X W (sparse_encode.py:24-25) on the library's NT GEMM."""
+        """z0 = X W (sparse_encode.py:24-25) on the library's NT GEMM (fp32, or float64 tensors on the fp64-MFMA one)."""
         n, d = X.shape
         k = W.shape[1]
         L = self.lib
         with torch.cuda.device(self.device):
             ws = self._ws(L.lasso_init_transpose_workspace_bytes(d, k), "init_t")
-            z0 = torch.empty((n, k), dtype=torch.float32, device=self.device)
-            nat.check(L.lasso_init_transpose(n, d, k, nat.LASSO_F32, nat.ptr(X), X.stride(0), nat.ptr(W), W.stride(0),
+            z0 = torch.empty((n, k), dtype=X.dtype, device=self.device)
+            nat.check(L.lasso_init_transpose(n, d, k, nat.LASSO_F64 if X.dtype == torch.float64 else nat.LASSO_F32, nat.ptr(X), X.stride(0), nat.ptr(W), W.stride(0),
                                              nat.ptr(z0), z0.stride(0), nat.ptr(ws), ws.numel(), self._stream()))
         return z0
 

@@ -8,11 +8,12 @@ from .. import _native as nat
 
 
 def lipschitz_constant(weight):
-    """Returns a python float, like the reference.  ``weight`` [d,k] fp32."""
+    """Returns a python float, like the reference.  ``weight`` [d,k] fp32 or float64 (the Gram matrix is then
+    formed from the doubles)."""
     nat.require_gpu()
-    if weight.dtype != torch.float32:
+    if weight.dtype not in (torch.float32, torch.float64):
         # the reference's bf16 + lr='auto' raises TypeError as well (ista.py:12)
-        raise TypeError("lasso_amd: lr='auto' needs an fp32 dictionary, got %s" % weight.dtype)
+        raise TypeError("lasso_amd: lr='auto' needs an fp32 or float64 dictionary, got %s" % weight.dtype)
     dev = weight.device if weight.is_cuda else torch.device('cuda', torch.cuda.current_device())
     w = weight.detach().to(dev).contiguous()
     d, k = w.shape
@@ -20,6 +21,7 @@ def lipschitz_constant(weight):
     with torch.cuda.device(dev):
         ws = nat.workspace(dev, L.lasso_lipschitz_workspace_bytes(d, k), tag='lip')
         out = C.c_double(0.0)
-        nat.check(L.lasso_lipschitz(nat.ptr(w), w.stride(0), d, k, nat.LASSO_F32, C.byref(out),
+        nat.check(L.lasso_lipschitz(nat.ptr(w), w.stride(0), d, k,
+                                    nat.LASSO_F64 if w.dtype == torch.float64 else nat.LASSO_F32, C.byref(out),
                                     nat.ptr(ws), ws.numel(), nat.stream_ptr(dev)))
     return out.value

@@ -6,7 +6,7 @@ import torch
 
 from ... import _native as nat
 
-_DT = {torch.float32: nat.LASSO_F32, torch.bfloat16: nat.LASSO_BF16}
+_DT = {torch.float32: nat.LASSO_F32, torch.bfloat16: nat.LASSO_BF16, torch.float64: nat.LASSO_F64}
 # bf16 tensors (BASELINE config 3).  On the fused shapes bf16 x, W, z0 go to the native
 # bf16-MFMA kernels (csrc/bt_bf16.hip: bf16 operands, fp32 accumulation and state), with or
 # without the backtracking line search.  Everything else (fp16, larger shapes, verbose,
@@ -201,7 +201,8 @@ def ista(x, z0, weight, alpha=1.0, fast=True, lr='auto', maxiter=10,
          return_info=False, stop_mode='global', kernel='auto', begin=False, shard=False):
     """Solve min_z 0.5*||z W^T - x||^2 + alpha*||z||_1 on the GPU.
 
-    x [n,d], z0 [n,k], weight [d,k]; returns a NEW tensor z [n,k] with the
+    x [n,d], z0 [n,k], weight [d,k] of one dtype -- float32, float64 (computed in double throughout on the
+    fp64 MFMA: _ista_f64), bfloat16 / float16 --; returns a NEW tensor z [n,k] with the
     dtype/device of z0 (``maxiter=0`` returns ``z0`` itself, ista.py:76,104).
     Inputs are never modified.  ``return_info`` (extension) additionally
     returns ``dict(iterations=..., last_delta=...)`` (plus ``trials`` / ``accepted_lr`` per
@@ -231,6 +232,9 @@ def ista(x, z0, weight, alpha=1.0, fast=True, lr='auto', maxiter=10,
                            % (tuple(x.shape), tuple(weight.shape), tuple(z0.shape)))
     if not (x.dtype == weight.dtype == z0.dtype):
         raise RuntimeError("expected x, weight, z0 of one dtype")
+    if x.dtype == torch.float64:
+        return _ista_f64(x, z0, weight, alpha, fast, lr, maxiter, tol, backtrack, eta_backtrack, verbose, return_info,
+                         stop_mode, kernel, begin, shard)
     if x.dtype in _UPCAST:
         if lr == 'auto':
             # the reference raises here as well: `.numpy()` has no bf16 (ista.py:12)
@@ -320,6 +324,74 @@ def ista(x, z0, weight, alpha=1.0, fast=True, lr='auto', maxiter=10,
     return _solve_native(xg, zg if zg is not None else z0, wg, alpha, fast, lr, maxiter, tol, backtrack, eta_backtrack,
                          verbose, return_info, out_device=out_device, stop_mode=stop_mode, kernel=kernel, begin=begin,
                          shard=shard)
+
+
+def _ista_f64(x, z0, weight, alpha, fast, lr, maxiter, tol, backtrack, eta_backtrack, verbose, return_info,
+              stop_mode, kernel, begin, shard):
+    """float64 tensors: lasso_fista_solve_f64 (csrc/gemm_f64.hip) -- the general-GEMM form of the solve on the fp64
+    MFMA, every value, sum and comparison in IEEE double, for any d, k; fixed step or lr='auto', line search, stop
+    rule, z0 (or the lazy_zeros sentinel), return_info.  The fp32-only extensions are refused by name."""
+    if verbose:
+        raise NotImplementedError("lasso_amd: verbose=True is not implemented for float64 tensors")
+    if begin:
+        raise NotImplementedError("lasso_amd: begin=%r (asynchronous solves) is not implemented for float64 tensors" % (begin,))
+    if shard:
+        raise NotImplementedError("lasso_amd: shard=True is not implemented for float64 tensors")
+    if kernel not in ('auto', 'unfused'):
+        raise NotImplementedError("lasso_amd: kernel=%r is an fp32 kernel; float64 tensors take the fp64-MFMA "
+                                  "general-GEMM path (kernel='auto')" % (kernel,))
+    if stop_mode not in ('global', 'chunked', 'none'):
+        raise NotImplementedError("lasso_amd: stop_mode=%r is not implemented for float64 tensors" % (stop_mode,))
+    if torch.is_grad_enabled() and (x.requires_grad or weight.requires_grad or z0.requires_grad):
+        raise NotImplementedError("lasso_amd: tensors with requires_grad=True: the differentiable path computes in "
+                                  "float32; detach() float64 tensors or solve under torch.no_grad()")
+    n, d = x.shape
+    k = weight.shape[1]
+    if maxiter == 0:
+        if _is_lazy_zeros(z0):
+            z0 = z0.contiguous()
+        return (z0, dict(iterations=0, last_delta=float('nan'))) if return_info else z0
+    if n == 0:      # empty batch: nothing to solve (the reference's loop stops at once: 0 <= 0)
+        z = z0.clone()
+        return (z, dict(iterations=1, last_delta=0.0)) if return_info else z
+    out_device = z0.device
+    dev = x.device if x.is_cuda else (weight.device if weight.is_cuda else
+                                      (z0.device if z0.is_cuda else torch.device('cuda', torch.cuda.current_device())))
+    xg = _to_device(x.detach(), dev).contiguous()
+    wg = _to_device(weight.detach(), dev).contiguous()
+    zg = None if _is_lazy_zeros(z0) else _to_device(z0.detach(), dev).contiguous()     # None -> NULL z0 = zeros
+    L = nat.lib()
+    z = torch.empty((n, k), dtype=torch.float64, device=dev)
+    cap = max(int(maxiter), 1)
+    with torch.cuda.device(dev):
+        nbytes = L.lasso_fista_workspace_bytes(n, d, k, nat.LASSO_F64, int(maxiter), float(tol), _STOP[stop_mode],
+                                               int(bool(backtrack)))
+        ws = nat.workspace(dev, nbytes)
+        iters = C.c_int32(0)
+        last = C.c_double(float('nan'))
+        want_trace = bool(backtrack) and bool(return_info)
+        trials = (C.c_int32 * cap)() if want_trace else None
+        acc_lr = (C.c_double * cap)() if want_trace else None
+        acc_f = (C.c_double * cap)() if want_trace else None
+        obj = C.c_double(float('nan')) if return_info == 'objective' else None
+        nat.check(L.lasso_fista_solve_f64(
+            nat.ptr(xg), xg.stride(0), nat.ptr(wg), wg.stride(0), nat.ptr(zg), zg.stride(0) if zg is not None else 0,
+            nat.ptr(z), z.stride(0), n, d, k, float(alpha), nat.LR_AUTO if lr == 'auto' else float(lr), int(bool(fast)),
+            int(maxiter), float(tol), _STOP[stop_mode], int(bool(backtrack)), float(eta_backtrack),
+            C.byref(iters) if return_info else None, C.byref(last) if return_info else None, trials, acc_lr, acc_f,
+            C.byref(obj) if obj is not None else None, nat.ptr(ws), ws.numel(), nat.stream_ptr(dev)))
+    if z.device != out_device:
+        z = z.to(out_device)
+    if not return_info:
+        return z
+    info = dict(iterations=iters.value, last_delta=last.value)
+    if want_trace:
+        info['trials'] = list(trials[:iters.value])
+        info['accepted_lr'] = list(acc_lr[:iters.value])
+        info['accepted_f'] = list(acc_f[:iters.value])
+    if obj is not None:
+        info['objective'] = obj.value
+    return z, info
 
 
 _STOP = {'global': nat.STOP_GLOBAL, 'chunked': nat.STOP_GLOBAL_CHUNKED, 'none': nat.STOP_NONE,

@@ -111,8 +111,11 @@ def initialize_code(x, weight, alpha, mode):
             z0 = torch.matmul(x, weight)
         else:                                                        # on the library's NT GEMM
             eng = _engine_for(x, weight)
-            z0 = eng.init_transpose(eng.to_device(x).float().contiguous(),
-                                    eng.to_device(weight).float().contiguous()).to(device=x.device, dtype=x.dtype)
+            if x.dtype == torch.float64 and weight.dtype == torch.float64:       # in double on the fp64-MFMA GEMM
+                z0 = eng.init_transpose(eng.to_device(x), eng.to_device(weight)).to(device=x.device)
+            else:
+                z0 = eng.init_transpose(eng.to_device(x).float().contiguous(),
+                                        eng.to_device(weight).float().contiguous()).to(device=x.device, dtype=x.dtype)
     elif mode == 'lstsq':                                            # :26-27 (utils.py:13-25)
         z0 = _lstsq_init(x, weight)
     elif mode == 'ridge':                                            # :28-29 (utils.py:28-40)
