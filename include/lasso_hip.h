@@ -661,6 +661,53 @@ int lasso_patches_reconstruct(const void* patches_dev, int64_t ld, const float* 
                               int64_t N, int64_t C, int64_t H, int64_t W, int ph, int pw, int sh, int sw,
                               void* stream);
 
+/* ---- GPSR-Basic: replaces gpsr_basic(), lasso/linear/solvers/gpsr.py:209-365 (sparse_encode.py:56-59) --------
+ * Gradient projection on the split z = u - v, u, v >= 0 (Figueiredo, Nowak, Wright 2007) over the whole batch: every
+ * inner product is a sum over all n rows, so the step size, the line search and the stop criterion are one decision per
+ * iteration (csrc/gpsr.hip).  The dictionary W [d][k] takes the place of the reference's A / AT callables.
+ *   options : the reference's arguments; stop_criterion 0..4 (else LASSO_ERR_BAD_ARG), init 0 (zeros) or 2 (x W) when
+ *             z0_dev is NULL (init 1, a random start, is the caller's to draw and pass as z0_dev: LASSO_ERR_UNSUPPORTED);
+ *             first_tau_factor <= 0 means "not given".
+ *   result  : n_iter (debias steps included, like the reference's counter), the final objective, flags (below),
+ *             the figures of the reference's verbose summaries, and -- trace non-NULL -- per-iteration host arrays of
+ *             the caller (capacity entries are written at most; every array of a non-NULL trace must be non-NULL).
+ * Continuation and debias run inside the call.  One extension: a line search whose objective is not finite, or that
+ * has reduced lambda 100 times, ends the solve (LASSO_GPSR_LINESEARCH_FAILED) with the last accepted z -- the
+ * reference would loop for ever.  z0_dev is only read; z_out_dev may not alias x or W.
+ * The call blocks: the host reads the control block once per outer iteration.  LASSO_F32 only (else
+ * LASSO_ERR_UNSUPPORTED); any n >= 0, d, k >= 1; n = 0 writes nothing. */
+typedef struct lasso_gpsr_options {
+  int32_t stop_criterion, maxiter, miniter, init;
+  int32_t continuation, debias, cont_steps, maxiter_debias, miniter_debias, reserved;
+  double tol, mu, lambda_backtrack, first_tau_factor, tol_debias;
+} lasso_gpsr_options;
+typedef struct lasso_gpsr_trace {
+  int32_t capacity;                       /* iterations of the main phase the arrays below hold */
+  float* lambda; float* lambda0;          /* accepted step, first guess */
+  int32_t* trials; float* objective; float* criterion; int32_t* nz;
+  int32_t step_capacity;                  /* continuation steps */
+  double* step_tau; float* step_f0; int32_t* step_nz0; int32_t* step_end;   /* tau, start objective / nonzeros, n_iter at its end */
+  int32_t db_capacity;                    /* debias steps */
+  float* db_rr; float* db_conv;           /* |resid|^2, rTr / threshold */
+} lasso_gpsr_trace;
+#define LASSO_GPSR_ZERO_SOLUTION 1        /* tau >= max|x W|: z_out = 0 ("tau is too small; solution is zero vector") */
+#define LASSO_GPSR_TAU_FACTOR_CHANGED 2   /* "parameter FirstTauFactor too large; changing" */
+#define LASSO_GPSR_LINESEARCH_FAILED 4
+#define LASSO_GPSR_DEBIAS_NO_NONZEROS 8   /* "Debiasing requested but not performed. x has no nonzeros." */
+#define LASSO_GPSR_DEBIAS_TOO_MANY 16     /* "... There are too many nonzeros in x." */
+typedef struct lasso_gpsr_result {
+  int32_t n_iter, flags, steps, db_iters;
+  double objective;                       /* the final objective (after debias when it ran) */
+  double main_objective; float main_rr, main_l1; int32_t main_nz;   /* main phase: objective, |z W^T - x|^2, |z|_1, nonzeros */
+  float db_rr, db_l1; int32_t db_nz;      /* after debias */
+  lasso_gpsr_trace* trace;                /* nullable */
+} lasso_gpsr_result;
+size_t lasso_gpsr_workspace_bytes(int64_t n, int64_t d, int64_t k, int dtype);
+int lasso_gpsr_solve(const void* x_dev, int64_t ldx, const void* w_dev, int64_t ldw, const void* z0_dev, int64_t ldz0,
+                     void* z_out_dev, int64_t ldz, int64_t n, int64_t d, int64_t k, int dtype, double alpha,
+                     const lasso_gpsr_options* options, lasso_gpsr_result* result,
+                     void* workspace_dev, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

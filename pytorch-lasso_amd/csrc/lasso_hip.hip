@@ -3004,6 +3004,47 @@ int lasso_init_transpose(int64_t n, int64_t d, int64_t k, int dtype, const void*
   return LASSO_OK;
 }
 
+// ---- GPSR-Basic: gpsr_basic, gpsr.py:209-365 (csrc/gpsr.hip) ------------------------------------
+size_t lasso_gpsr_workspace_bytes(int64_t n, int64_t d, int64_t k, int dtype) {
+  if (dtype != LASSO_F32 || n < 0 || d <= 0 || k <= 0 || n > INT32_MAX || d > INT32_MAX || k > INT32_MAX) return 0;
+  return gpsr::workspace_bytes(n, d, k);
+}
+
+int lasso_gpsr_solve(const void* x_dev, int64_t ldx, const void* w_dev, int64_t ldw, const void* z0_dev, int64_t ldz0,
+                     void* z_out_dev, int64_t ldz, int64_t n, int64_t d, int64_t k, int dtype, double alpha,
+                     const lasso_gpsr_options* o, lasso_gpsr_result* res, void* workspace_dev, size_t workspace_bytes,
+                     void* stream) {
+  if (dtype != LASSO_F32) return fail(LASSO_ERR_UNSUPPORTED, "GPSR: dtype %d (fp32 tensors only)", dtype);
+  if (!o || !res) return fail(LASSO_ERR_BAD_ARG, "null options / result");
+  if (n < 0 || d <= 0 || k <= 0 || n > INT32_MAX || d > INT32_MAX || k > INT32_MAX)
+    return fail(LASSO_ERR_BAD_ARG, "bad shape");
+  if (o->stop_criterion < 0 || o->stop_criterion > 4) return fail(LASSO_ERR_BAD_ARG, "Unknown stopping criterion");
+  if (!z0_dev && o->init == 1) return fail(LASSO_ERR_UNSUPPORTED, "GPSR: init=1 (random start) is passed as z0");
+  if (!z0_dev && o->init != 0 && o->init != 2) return fail(LASSO_ERR_BAD_ARG, "Unknown initialization option");
+  if (o->continuation && o->cont_steps < 1) return fail(LASSO_ERR_BAD_ARG, "cont_steps < 1");
+  if (!(o->lambda_backtrack > 0.0 && o->lambda_backtrack < 1.0)) return fail(LASSO_ERR_BAD_ARG, "lambda_backtrack outside (0, 1)");
+  if (const lasso_gpsr_trace* t = res->trace) {
+    if ((t->capacity > 0 && (!t->lambda || !t->lambda0 || !t->trials || !t->objective || !t->criterion || !t->nz)) ||
+        (t->step_capacity > 0 && (!t->step_tau || !t->step_f0 || !t->step_nz0 || !t->step_end)) ||
+        (t->db_capacity > 0 && (!t->db_rr || !t->db_conv)) || t->capacity < 0 || t->step_capacity < 0 || t->db_capacity < 0)
+      return fail(LASSO_ERR_BAD_ARG, "trace with a null array");
+  }
+  res->n_iter = res->flags = res->steps = res->db_iters = 0;
+  res->objective = res->main_objective = 0.0;
+  res->main_rr = res->main_l1 = res->db_rr = res->db_l1 = 0.0f;
+  res->main_nz = res->db_nz = 0;
+  if (n == 0) return LASSO_OK;
+  if (!x_dev || !w_dev || !z_out_dev || !workspace_dev) return fail(LASSO_ERR_BAD_ARG, "null pointer");
+  if (ldx < d || ldw < k || ldz < k || (z0_dev && ldz0 < k)) return fail(LASSO_ERR_BAD_ARG, "leading dimension too small");
+  if (workspace_bytes < lasso_gpsr_workspace_bytes(n, d, k, dtype))
+    return fail(LASSO_ERR_WORKSPACE, "need %zu bytes", lasso_gpsr_workspace_bytes(n, d, k, dtype));
+  char msg[400] = "";
+  if (int s = gpsr::solve((const float*)x_dev, ldx, (const float*)w_dev, ldw, (const float*)z0_dev, ldz0, (float*)z_out_dev,
+                          ldz, n, d, k, alpha, *o, res, workspace_dev, static_cast<hipStream_t>(stream), msg, sizeof(msg)))
+    return fail(s, "%s", msg);
+  return LASSO_OK;
+}
+
 // ---- unconstrained M-step: update_dict_ridge, dict_learning.py:106-123 ---------------------
 size_t lasso_ridge_workspace_bytes(int64_t d, int64_t k) {
   if (d <= 0 || k <= 0 || k > 4096) return 0;

@@ -8,6 +8,9 @@
 #include <math.h>
 #include <algorithm>
 
+struct lasso_gpsr_options;
+struct lasso_gpsr_result;
+
 namespace lasso {
 
 constexpr int kTileM = 16;          // batch rows per workgroup (one MFMA M-block)
@@ -494,5 +497,13 @@ int objective(const double* x, int64_t ldx, const double* w, int64_t ldw, const 
 int init_transpose(const double* x, int64_t ldx, const double* w, int64_t ldw, double* z0, int64_t ldz, int64_t n,
                    int64_t d, int64_t k, hipStream_t st, char* err, size_t errlen);
 }  // namespace f64
+
+// GPSR-Basic (gpsr.hip): the driver behind lasso_gpsr_solve; returns a lasso_status, failure text in err[errlen]
+namespace gpsr {
+size_t workspace_bytes(int64_t n, int64_t d, int64_t k);
+int solve(const float* x, int64_t ldx, const float* w, int64_t ldw, const float* z0, int64_t ldz0, float* zout, int64_t ldz,
+          int64_t n, int64_t d, int64_t k, double alpha, const lasso_gpsr_options& o, lasso_gpsr_result* res, void* workspace,
+          hipStream_t st, char* err, size_t errlen);
+}  // namespace gpsr
 
 }  // namespace lasso

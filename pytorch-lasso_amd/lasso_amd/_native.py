@@ -25,6 +25,8 @@ SOLVE_SHARDED = 0x8000
 SOLVE_STATUS_MAPPED = 0x20000       # iters_out = four words of pinned (device-writable) host memory
 SOLVE_DEFER_VERDICT = 0x40000       # the verdict's launch is left to lasso_fista_solve_verdict_deferred (another stream)
 LR_AUTO = -1.0
+GPSR_ZERO_SOLUTION, GPSR_TAU_FACTOR_CHANGED, GPSR_LINESEARCH_FAILED = 1, 2, 4
+GPSR_DEBIAS_NO_NONZEROS, GPSR_DEBIAS_TOO_MANY = 8, 16
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = None
@@ -39,6 +41,30 @@ _LIB_PATH = os.path.join(_HERE, "liblasso_hip.so")
 
 def lib_path():
     return _LIB_PATH
+
+
+class GpsrOptions(C.Structure):
+    """lasso_gpsr_options (include/lasso_hip.h)"""
+    _fields_ = [(name, C.c_int32) for name in ('stop_criterion', 'maxiter', 'miniter', 'init', 'continuation', 'debias',
+                                               'cont_steps', 'maxiter_debias', 'miniter_debias', 'reserved')] + \
+               [(name, C.c_double) for name in ('tol', 'mu', 'lambda_backtrack', 'first_tau_factor', 'tol_debias')]
+
+
+class GpsrTrace(C.Structure):
+    """lasso_gpsr_trace: host arrays of the caller"""
+    _pf, _pi = C.POINTER(C.c_float), C.POINTER(C.c_int32)
+    _fields_ = [('capacity', C.c_int32), ('lambda_', _pf), ('lambda0', _pf), ('trials', _pi), ('objective', _pf),
+                ('criterion', _pf), ('nz', _pi), ('step_capacity', C.c_int32), ('step_tau', C.POINTER(C.c_double)),
+                ('step_f0', _pf), ('step_nz0', _pi), ('step_end', _pi), ('db_capacity', C.c_int32), ('db_rr', _pf),
+                ('db_conv', _pf)]
+
+
+class GpsrResult(C.Structure):
+    """lasso_gpsr_result"""
+    _fields_ = [('n_iter', C.c_int32), ('flags', C.c_int32), ('steps', C.c_int32), ('db_iters', C.c_int32),
+                ('objective', C.c_double), ('main_objective', C.c_double), ('main_rr', C.c_float), ('main_l1', C.c_float),
+                ('main_nz', C.c_int32), ('db_rr', C.c_float), ('db_l1', C.c_float), ('db_nz', C.c_int32),
+                ('trace', C.POINTER(GpsrTrace))]
 
 
 # int (*lasso_allreduce_fn)(void* ctx, double* sums, int count)   (include/lasso_hip.h)
@@ -212,6 +238,11 @@ def _declare(lib):
     lib.lasso_patches_extract.argtypes = [vp, vp, i64, vp, i64, i64, i64, i64, i32, i32, i32, i32, i32, vp]
     lib.lasso_patches_reconstruct.restype = i32
     lib.lasso_patches_reconstruct.argtypes = [vp, i64, vp, vp, i64, i64, i64, i64, i32, i32, i32, i32, vp]
+    lib.lasso_gpsr_workspace_bytes.restype = sz
+    lib.lasso_gpsr_workspace_bytes.argtypes = [i64, i64, i64, i32]
+    lib.lasso_gpsr_solve.restype = i32
+    lib.lasso_gpsr_solve.argtypes = [vp, i64, vp, i64, vp, i64, vp, i64, i64, i64, i64, i32, dbl,
+                                     C.POINTER(GpsrOptions), C.POINTER(GpsrResult), vp, sz, vp]
     lib.lasso_cd_solve.restype = i32
     lib.lasso_cd_solve.argtypes = [vp, i64, vp, i64, vp, i64, vp, i64, i64, i64, i64, i32, dbl, i32,
                                    dbl, pi32, pi32, vp, sz, vp]

@@ -1,11 +1,11 @@
 """Mirror of lasso/linear/sparse_encode.py:8-73 for the 'ista' arm."""
 import torch
 
-from .solvers import ista, coord_descent
+from .solvers import ista, coord_descent, gpsr_basic
 
 _init_defaults = {'ista': 'zero'}                                   # sparse_encode.py:8-16
 
-_OFF_PATH_ALGOS = ('gpsr', 'iter-ridge', 'interior-point', 'split-bregman', 'own')
+_OFF_PATH_ALGOS = ('iter-ridge', 'interior-point', 'split-bregman', 'own')
 
 
 def _engine_for(x, weight):
@@ -128,7 +128,7 @@ def initialize_code(x, weight, alpha, mode):
 def sparse_encode(x, weight, alpha=1.0, z0=None, algorithm='ista', init=None,
                   **kwargs):
     """Same call surface as lasso.linear.sparse_encode (sparse_encode.py:38-73);
-    ``algorithm='ista'`` and ``'cd'`` run on the HIP engine, the other solver names raise
+    ``algorithm='ista'``, ``'cd'`` and ``'gpsr'`` run on the HIP engine, the other solver names raise
     NotImplementedError (they are outside the accelerated path), anything else
     raises ValueError like the reference (:71)."""
     n_samples = x.size(0)
@@ -138,7 +138,9 @@ def sparse_encode(x, weight, alpha=1.0, z0=None, algorithm='ista', init=None,
     else:
         if init is None:
             init = _init_defaults.get(algorithm, 'zero')             # :47-48
-        if init == 'zero' and algorithm == 'ista' and kwargs.get('maxiter', 10) != 0 and n_samples * n_components > 1:
+        if init == 'zero' and algorithm == 'gpsr':
+            z0 = None                                                # :22-23: the solver starts from its own zeros (init=0)
+        elif init == 'zero' and algorithm == 'ista' and kwargs.get('maxiter', 10) != 0 and n_samples * n_components > 1:
             from .solvers.ista import lazy_zeros
             z0 = lazy_zeros(x, n_samples, n_components)              # :22-23 without the n*k fill (and read)
         else:
@@ -147,9 +149,11 @@ def sparse_encode(x, weight, alpha=1.0, z0=None, algorithm='ista', init=None,
         z = ista(x, z0, weight, alpha, **kwargs)                     # :62-63
     elif algorithm == 'cd':
         z = coord_descent(x, weight, z0, alpha, **kwargs)            # :54-55
+    elif algorithm == 'gpsr':
+        z = gpsr_basic(x, weight, tau=alpha, x0=z0, **kwargs)        # :56-59 (the dictionary in place of A / AT)
     elif algorithm in _OFF_PATH_ALGOS:
         raise NotImplementedError(
-            "lasso_amd accelerates algorithm='ista' and 'cd'; %r is not on the HIP path" % algorithm)
+            "lasso_amd accelerates algorithm='ista', 'cd' and 'gpsr'; %r is not on the HIP path" % algorithm)
     else:
         raise ValueError("invalid algorithm parameter '{}'.".format(algorithm))  # :71
     return z
