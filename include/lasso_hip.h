@@ -506,6 +506,45 @@ int lasso_ridge_solve(const float* a_dev, const float* b_dev, void* v_dev, int64
                       int64_t d, int64_t k, int dtype, double lambda_n, int32_t* info_out,
                       void* workspace_dev, size_t workspace_bytes, void* stream);
 
+/* ---- float64 M-step: update_dict / update_dict_ridge (dict_learning.py:56-123) on float64 tensors ----------------
+ * The M-step entry points above keep answering LASSO_ERR_UNSUPPORTED to LASSO_F64 (their A and B are float*); these
+ * are their siblings with double matrices and no dtype argument (csrc/mstep_f64.hip).  Every product runs on the
+ * fp64 MFMA, every value, norm, pivot and comparison is an IEEE double, no sum uses atomics: two calls with the same
+ * arguments give the same bits.  Null pointers and non-positive sizes answer LASSO_ERR_BAD_ARG before any HIP call.
+ * lasso_gram_accumulate_f64: A = Z^T Z [k][k] (ld k, symmetric bit for bit), B = Z^T X [k][d] (ld d) of the n >= 1
+ *   rows; any d, k, ldz >= k, ldx >= d.  The workspace (optional, may be NULL) holds the partial products of the row
+ *   slabs a large n is split into; they are summed in slab order.
+ * lasso_dict_sweep_f64: the Gauss-Seidel atom sweep of lasso_dict_sweep on (A, B), D [d][k] (ldd) updated in place;
+ *   d <= 1024, k <= 4096 (LASSO_ERR_UNSUPPORTED beyond, the workspace query returns 0).  An atom with ||u|| < eps is
+ *   flagged in degenerate_dev [k] (int32, every word written) and leaves the model (its column of D is zero until
+ *   lasso_dict_fill_degenerate_f64 replaces it -- the deferred form only: there is no pool argument).  ndeg_out
+ *   (HOST, nullable) receives the count of flagged atoms and, when non-NULL, makes the call synchronise `stream`.
+ * lasso_dict_fill_degenerate_f64: the i-th flagged atom (atom order) becomes row i of pool_dev [pool_rows][d]
+ *   (ld pool_ld, double), clamped at 0 if `positive`, divided by its norm (:93-96).
+ * lasso_zero_columns_f64: Z[:, j] = 0 where degenerate_dev[j] != 0 (:98).
+ * lasso_ridge_solve_f64: V [d][k] (ldv) = ((A + lambda_n I)^-1 B)^T by a blocked Cholesky factorisation with B^T
+ *   carried along and a back substitution; k <= 4096 (lasso_ridge_f64_workspace_bytes returns 0 beyond).  A and B are
+ *   not modified.  info_out (HOST, nullable): 0, or 1 + the index of the first pivot that is not positive (then
+ *   LASSO_ERR_BAD_ARG); a non-NULL info_out makes the call synchronise `stream`. */
+size_t lasso_gram_f64_workspace_bytes(int64_t n, int64_t d, int64_t k);
+int lasso_gram_accumulate_f64(const double* z_dev, int64_t ldz, const double* x_dev, int64_t ldx,
+                              int64_t n, int64_t d, int64_t k, double* a_dev, double* b_dev,
+                              void* workspace_dev, size_t workspace_bytes, void* stream);
+size_t lasso_dict_sweep_f64_workspace_bytes(int64_t d, int64_t k);
+int lasso_dict_sweep_f64(const double* a_dev, const double* b_dev, double* d_dev, int64_t ldd,
+                         int64_t d, int64_t k, double eps, int positive,
+                         int32_t* degenerate_dev, int32_t* ndeg_out,
+                         void* workspace_dev, size_t workspace_bytes, void* stream);
+int lasso_dict_fill_degenerate_f64(double* d_dev, int64_t ldd, int64_t d, int64_t k,
+                                   const int32_t* degenerate_dev, const double* pool_dev, int64_t pool_rows,
+                                   int64_t pool_ld, int positive, void* stream);
+int lasso_zero_columns_f64(double* z_dev, int64_t ldz, int64_t n, int64_t k,
+                           const int32_t* degenerate_dev, void* stream);
+size_t lasso_ridge_f64_workspace_bytes(int64_t d, int64_t k);
+int lasso_ridge_solve_f64(const double* a_dev, const double* b_dev, double* v_dev, int64_t ldv,
+                          int64_t d, int64_t k, double lambda_n, int32_t* info_out,
+                          void* workspace_dev, size_t workspace_bytes, void* stream);
+
 /* ---- greedy coordinate descent: replaces coord_descent(),
  *      lasso/linear/solvers/coordinate_descent.py:5-54 (sparse_encode.py:54-55) --------
  * Per row: b = x W (:19, independent of z0), tracked z = z0 or 0 (:10-14); per step

@@ -363,6 +363,14 @@ int start_state(const double* z0, int64_t ldz0, double* zout, int64_t ldz, doubl
 
 }  // namespace
 
+// C = C0 - A B^T for the float64 M-step (mstep_f64.hip); b_t = 0: B [nn][kk], else B [kk][nn].  C may be C0: a
+// workgroup loads its block of C0 in front of its first store, and no other workgroup touches that block.
+hipError_t launch_gemm_sub(const double* A, int64_t lda, const double* B, int64_t ldb, int b_t, const double* C0,
+                           int64_t ldc0, double* C, int64_t ldc, int m, int nn, int kk, hipStream_t st) {
+  GemmArgs g{A, lda, B, ldb, C0, ldc0, C, ldc, nullptr, 0, 0.0, 0.0, 0.0, nullptr, m, nn, kk};
+  return b_t ? launch_gemm<EPI_SUB, true>(g, st) : launch_gemm<EPI_SUB, false>(g, st);
+}
+
 size_t solve_workspace_bytes(int64_t n, int64_t d, int64_t k, int maxiter, double tol, int stop_mode, int backtrack) {
   const bool with_state = !backtrack && tol > 0.0 && (stop_mode & 0xFF) != LASSO_STOP_NONE && maxiter > 0;
   return carve(nullptr, n, d, k, backtrack != 0, with_state).bytes;

@@ -3092,6 +3092,94 @@ int lasso_zero_columns(void* z_dev, int64_t ldz, int64_t n, int64_t k, int dtype
   return LASSO_OK;
 }
 
+// ---- float64 M-step (mstep_f64.hip): the entry points above with double matrices; see include/lasso_hip.h ----------
+size_t lasso_gram_f64_workspace_bytes(int64_t n, int64_t d, int64_t k) {
+  if (n <= 0 || d <= 0 || k <= 0) return 0;
+  return f64::gram_workspace_bytes(n, d, k) + 256;
+}
+
+int lasso_gram_accumulate_f64(const double* z_dev, int64_t ldz, const double* x_dev, int64_t ldx, int64_t n, int64_t d,
+                              int64_t k, double* a_dev, double* b_dev, void* workspace_dev, size_t workspace_bytes,
+                              void* stream) {
+  if (!z_dev || !x_dev || !a_dev || !b_dev || n <= 0 || d <= 0 || k <= 0 || ldz < k || ldx < d)
+    return fail(LASSO_ERR_BAD_ARG, "bad argument");
+  if (n > INT32_MAX - 64 || (k + 63) / 64 > 65535 || (d + 63) / 64 > 65535) return fail(LASSO_ERR_UNSUPPORTED, "shape too large");
+  // optional scratch for the row slabs' partial products (NULL or too small: one pass)
+  double* scratch = (workspace_dev && workspace_bytes >= lasso_gram_f64_workspace_bytes(n, d, k)) ? (double*)workspace_dev
+                                                                                                  : nullptr;
+  const int splits = scratch ? f64::gram_splits(n, d, k, device_cus()) : 1;
+  LASSO_HIP_TRY(f64::launch_gram(z_dev, ldz, x_dev, ldx, (int)n, (int)d, (int)k, a_dev, b_dev, scratch, splits,
+                                 (hipStream_t)stream));
+  return LASSO_OK;
+}
+
+size_t lasso_dict_sweep_f64_workspace_bytes(int64_t d, int64_t k) {
+  if (d <= 0 || k <= 0 || d > kSweepMaxD || k > kSweepMaxK) return 0;
+  return f64::sweep_workspace_bytes(d, k);
+}
+
+int lasso_dict_sweep_f64(const double* a_dev, const double* b_dev, double* d_dev, int64_t ldd, int64_t d, int64_t k,
+                         double eps, int positive, int32_t* degenerate_dev, int32_t* ndeg_out, void* workspace_dev,
+                         size_t workspace_bytes, void* stream) {
+  if (!a_dev || !b_dev || !d_dev || !degenerate_dev || !workspace_dev || d <= 0 || k <= 0 || ldd < k)
+    return fail(LASSO_ERR_BAD_ARG, "bad argument");
+  if (d > kSweepMaxD || k > kSweepMaxK)
+    return fail(LASSO_ERR_UNSUPPORTED, "atom sweep: d=%lld k=%lld (d <= %d, k <= %d)", (long long)d, (long long)k,
+                kSweepMaxD, kSweepMaxK);
+  if (workspace_bytes < lasso_dict_sweep_f64_workspace_bytes(d, k))
+    return fail(LASSO_ERR_WORKSPACE, "need %zu bytes", lasso_dict_sweep_f64_workspace_bytes(d, k));
+  hipStream_t st = (hipStream_t)stream;
+  LASSO_HIP_TRY(f64::launch_sweep(a_dev, b_dev, d_dev, ldd, (int)d, (int)k, eps, positive, degenerate_dev, workspace_dev, st));
+  if (ndeg_out) {
+    LASSO_HIP_TRY(hipMemcpyAsync(ndeg_out, (char*)workspace_dev + f64::sweep_count_offset(d, k), sizeof(int),
+                                 hipMemcpyDeviceToHost, st));
+    LASSO_HIP_TRY(hipStreamSynchronize(st));
+  }
+  return LASSO_OK;
+}
+
+int lasso_dict_fill_degenerate_f64(double* d_dev, int64_t ldd, int64_t d, int64_t k, const int32_t* degenerate_dev,
+                                   const double* pool_dev, int64_t pool_rows, int64_t pool_ld, int positive,
+                                   void* stream) {
+  if (!d_dev || !degenerate_dev || !pool_dev || d <= 0 || k <= 0 || ldd < k || pool_rows <= 0 || pool_ld < d)
+    return fail(LASSO_ERR_BAD_ARG, "bad argument");
+  if (d > INT32_MAX || k > INT32_MAX || pool_rows > INT32_MAX) return fail(LASSO_ERR_UNSUPPORTED, "shape too large");
+  LASSO_HIP_TRY(f64::launch_fill_degenerate(d_dev, ldd, (int)d, (int)k, degenerate_dev, pool_dev, (int)pool_rows, pool_ld,
+                                            positive, (hipStream_t)stream));
+  return LASSO_OK;
+}
+
+int lasso_zero_columns_f64(double* z_dev, int64_t ldz, int64_t n, int64_t k, const int32_t* degenerate_dev, void* stream) {
+  if (!z_dev || !degenerate_dev || n <= 0 || k <= 0 || ldz < k) return fail(LASSO_ERR_BAD_ARG, "bad argument");
+  if (k > INT32_MAX) return fail(LASSO_ERR_UNSUPPORTED, "shape too large");
+  LASSO_HIP_TRY(f64::launch_zero_columns(z_dev, ldz, n, (int)k, degenerate_dev, (hipStream_t)stream));
+  return LASSO_OK;
+}
+
+size_t lasso_ridge_f64_workspace_bytes(int64_t d, int64_t k) {
+  const size_t s = f64::ridge_workspace_bytes(d, k);
+  return s ? s + 256 : 0;
+}
+
+int lasso_ridge_solve_f64(const double* a_dev, const double* b_dev, double* v_dev, int64_t ldv, int64_t d, int64_t k,
+                          double lambda_n, int32_t* info_out, void* workspace_dev, size_t workspace_bytes, void* stream) {
+  if (!a_dev || !b_dev || !v_dev || !workspace_dev || d <= 0 || k <= 0 || ldv < k)
+    return fail(LASSO_ERR_BAD_ARG, "bad argument");
+  if (k > 4096 || d > INT32_MAX - 4096) return fail(LASSO_ERR_UNSUPPORTED, "ridge solve: k=%lld > 4096", (long long)k);
+  if (workspace_bytes < lasso_ridge_f64_workspace_bytes(d, k))
+    return fail(LASSO_ERR_WORKSPACE, "need %zu bytes", lasso_ridge_f64_workspace_bytes(d, k));
+  hipStream_t st = (hipStream_t)stream;
+  int* const info_dev = (int*)((char*)workspace_dev + f64::ridge_workspace_bytes(d, k));
+  LASSO_HIP_TRY(f64::launch_ridge_solve(a_dev, b_dev, v_dev, ldv, (int)d, (int)k, lambda_n, workspace_dev, info_dev, st));
+  if (info_out) {
+    LASSO_HIP_TRY(hipMemcpyAsync(info_out, info_dev, sizeof(int), hipMemcpyDeviceToHost, st));
+    LASSO_HIP_TRY(hipStreamSynchronize(st));
+    if (*info_out != 0)
+      return fail(LASSO_ERR_BAD_ARG, "Z^T Z + lambd*n*I is not positive definite (pivot %d)", *info_out);
+  }
+  return LASSO_OK;
+}
+
 // ---- greedy coordinate descent: coordinate_descent.py:5-54 -------------------------
 size_t lasso_cd_workspace_bytes(int64_t n, int64_t d, int64_t k, int dtype) {
   (void)dtype;

@@ -496,6 +496,26 @@ int objective(const double* x, int64_t ldx, const double* w, int64_t ldw, const 
               size_t ws_bytes, hipStream_t st, char* err, size_t errlen);
 int init_transpose(const double* x, int64_t ldx, const double* w, int64_t ldw, double* z0, int64_t ldz, int64_t n,
                    int64_t d, int64_t k, hipStream_t st, char* err, size_t errlen);
+// C = C0 - A B^T on gemm_f64_nt_kernel; b_t = 0: B [nn][kk], else B [kk][nn]; C may be C0 (gemm_f64.hip)
+hipError_t launch_gemm_sub(const double* A, int64_t lda, const double* B, int64_t ldb, int b_t, const double* C0,
+                           int64_t ldc0, double* C, int64_t ldc, int m, int nn, int kk, hipStream_t st);
+// float64 M-step (mstep_f64.hip): Gram products, atom sweep, ridge solve in double on the fp64 MFMA
+constexpr int kGramF64MaxSplits = 16;
+int gram_splits(int64_t n, int64_t d, int64_t k, int cus);      // row splits of both products (1: no partial slabs)
+size_t gram_workspace_bytes(int64_t n, int64_t d, int64_t k);
+hipError_t launch_gram(const double* Z, int64_t ldz, const double* X, int64_t ldx, int n, int d, int k, double* A,
+                       double* B, double* scratch, int splits, hipStream_t st);
+size_t sweep_workspace_bytes(int64_t d, int64_t k);
+// ndeg_dev: one int32 behind the workspace's matrices (sweep_count_offset) holds the count of flagged atoms
+size_t sweep_count_offset(int64_t d, int64_t k);
+hipError_t launch_sweep(const double* A, const double* B, double* D, int64_t ldd, int d, int k, double eps, int positive,
+                        int* degenerate, void* workspace, hipStream_t st);
+hipError_t launch_fill_degenerate(double* D, int64_t ldd, int d, int k, const int* degenerate, const double* pool,
+                                  int pool_rows, int64_t pool_ld, int positive, hipStream_t st);
+hipError_t launch_zero_columns(double* Z, int64_t ldz, int64_t n, int k, const int* degenerate, hipStream_t st);
+size_t ridge_workspace_bytes(int64_t d, int64_t k);             // the working matrix; the info word sits behind it
+hipError_t launch_ridge_solve(const double* A, const double* B, double* V, int64_t ldv, int d, int k, double lam,
+                              void* workspace, int* info_dev, hipStream_t st);
 }  // namespace f64
 
 // GPSR-Basic (gpsr.hip): the driver behind lasso_gpsr_solve; returns a lasso_status, failure text in err[errlen]

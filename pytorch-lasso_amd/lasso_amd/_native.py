@@ -196,6 +196,23 @@ def _declare(lib):
     lib.lasso_zero_columns.restype = i32
     lib.lasso_zero_columns.argtypes = [vp, i64, i64, i64, i32, vp, vp]
     pi32 = C.POINTER(C.c_int32)
+    # float64 M-step: double matrices, no dtype argument
+    lib.lasso_gram_f64_workspace_bytes.restype = sz
+    lib.lasso_gram_f64_workspace_bytes.argtypes = [i64, i64, i64]
+    lib.lasso_gram_accumulate_f64.restype = i32
+    lib.lasso_gram_accumulate_f64.argtypes = [vp, i64, vp, i64, i64, i64, i64, vp, vp, vp, sz, vp]
+    lib.lasso_dict_sweep_f64_workspace_bytes.restype = sz
+    lib.lasso_dict_sweep_f64_workspace_bytes.argtypes = [i64, i64]
+    lib.lasso_dict_sweep_f64.restype = i32
+    lib.lasso_dict_sweep_f64.argtypes = [vp, vp, vp, i64, i64, i64, dbl, i32, vp, pi32, vp, sz, vp]
+    lib.lasso_dict_fill_degenerate_f64.restype = i32
+    lib.lasso_dict_fill_degenerate_f64.argtypes = [vp, i64, i64, i64, vp, vp, i64, i64, i32, vp]
+    lib.lasso_zero_columns_f64.restype = i32
+    lib.lasso_zero_columns_f64.argtypes = [vp, i64, i64, i64, vp, vp]
+    lib.lasso_ridge_f64_workspace_bytes.restype = sz
+    lib.lasso_ridge_f64_workspace_bytes.argtypes = [i64, i64]
+    lib.lasso_ridge_solve_f64.restype = i32
+    lib.lasso_ridge_solve_f64.argtypes = [vp, vp, vp, i64, i64, i64, dbl, pi32, vp, sz, vp]
     lib.lasso_cd_workspace_bytes.restype = sz
     lib.lasso_cd_workspace_bytes.argtypes = [i64, i64, i64, i32]
     lib.lasso_cd_prepare.restype = i32

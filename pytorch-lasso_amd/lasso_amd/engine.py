@@ -391,14 +391,36 @@ class HipEngine:
         return loss, sums
 
     # -- M-step --------------------------------------------------------------------
+    @staticmethod
+    def _all_f64(what, *tensors):
+        """True: every tensor is float64 (the double entry points); False: none is.  A mix raises before any launch
+        (the reference's matmul raises there too)."""
+        f64 = [t.dtype == torch.float64 for t in tensors if t is not None]
+        if any(f64) and not all(f64):
+            raise RuntimeError("%s: expected tensors of one dtype, got %s"
+                               % (what, ", ".join(str(t.dtype) for t in tensors if t is not None)))
+        return bool(f64) and all(f64)
+
     def gram(self, Z, X, out, started=None):
-        """out: flat fp32 buffer of k*k + k*d (+extra) floats; A and B are written at its
+        """out: flat fp32 buffer of k*k + k*d (+extra) floats (float64 tensors: doubles); A and B are written at its
         start so one all-reduce covers both.  ``started``: (int32 device tensor, value) -- the product's first launch
         writes the value there as it starts (lasso_gram_accumulate_signal: a start signal for another stream)."""
         n, k = Z.shape
         d = X.shape[1]
         A = out[:k * k].view(k, k)
         B = out[k * k:k * k + k * d].view(k, d)
+        if self._all_f64("gram", Z, X, out):         # float64 tensors: a double buffer, lasso_gram_accumulate_f64
+            if started is not None:
+                raise NotImplementedError("gram: float64 tensors have no start signal (one-stream EM loop only)")
+            if n == 0:
+                out[:k * k + k * d].zero_()
+                return A, B
+            with torch.cuda.device(self.device):
+                ws = self._ws(self.lib.lasso_gram_f64_workspace_bytes(n, d, k), "gram_f64")
+                nat.check(self.lib.lasso_gram_accumulate_f64(nat.ptr(Z), Z.stride(0), nat.ptr(X), X.stride(0), n, d, k,
+                                                             nat.ptr(A), nat.ptr(B), nat.ptr(ws), ws.numel(),
+                                                             self._stream()))
+            return A, B
         with torch.cuda.device(self.device):
             ws = self._ws(self.lib.lasso_gram_workspace_bytes(n, d, k), "gram")
             if started is None:
@@ -417,6 +439,18 @@ class HipEngine:
         ndeg python int)."""
         d, k = D.shape
         L = self.lib
+        if self._all_f64("sweep", A, B, D):          # float64 tensors: lasso_dict_sweep_f64 (deferred replacement only)
+            if pool is not None:
+                raise NotImplementedError("sweep: float64 tensors take their replacement directions through "
+                                          "fill_degenerate, not a pool")
+            with torch.cuda.device(self.device):
+                ws = self._ws(L.lasso_dict_sweep_f64_workspace_bytes(d, k), "sweep_f64")
+                mask = torch.zeros(k, dtype=torch.int32, device=self.device)
+                ndeg = C.c_int32(0)
+                nat.check(L.lasso_dict_sweep_f64(nat.ptr(A), nat.ptr(B), nat.ptr(D), D.stride(0), d, k, float(eps),
+                                                 int(bool(positive)), nat.ptr(mask), C.byref(ndeg), nat.ptr(ws),
+                                                 ws.numel(), self._stream()))
+            return mask, ndeg.value
         with torch.cuda.device(self.device):
             ws = self._ws(L.lasso_dict_sweep_workspace_bytes(d, k), "sweep")
             mask = torch.zeros(k, dtype=torch.int32, device=self.device)
@@ -434,6 +468,12 @@ class HipEngine:
         """The i-th flagged atom of D becomes pool row i, normalised (dict_learning.py:93-96)."""
         d, k = D.shape
         pool = pool.to(self.device).contiguous()
+        if self._all_f64("fill_degenerate", D, pool):
+            with torch.cuda.device(self.device):
+                nat.check(self.lib.lasso_dict_fill_degenerate_f64(
+                    nat.ptr(D), D.stride(0), d, k, nat.ptr(mask), nat.ptr(pool), pool.shape[0], pool.stride(0),
+                    int(bool(positive)), self._stream()))
+            return
         with torch.cuda.device(self.device):
             nat.check(self.lib.lasso_dict_fill_degenerate(
                 nat.ptr(D), D.stride(0), d, k, nat.LASSO_F32, nat.ptr(mask), nat.ptr(pool), pool.shape[0],
@@ -441,6 +481,11 @@ class HipEngine:
 
     def zero_columns(self, Z, mask):
         n, k = Z.shape
+        if Z.dtype == torch.float64:
+            if n > 0:
+                with torch.cuda.device(self.device):
+                    nat.check(self.lib.lasso_zero_columns_f64(nat.ptr(Z), Z.stride(0), n, k, nat.ptr(mask), self._stream()))
+            return
         with torch.cuda.device(self.device):
             nat.check(self.lib.lasso_zero_columns(nat.ptr(Z), Z.stride(0), n, k, nat.LASSO_F32,
                                                   nat.ptr(mask), self._stream()))
@@ -464,6 +509,25 @@ class HipEngine:
         (the kernels' limit) the k x k factorisation goes to torch.linalg on the device."""
         k, d = B.shape
         L = self.lib
+        if self._all_f64("ridge", A, B):             # float64 tensors: lasso_ridge_solve_f64, the same scheme in double
+            nbytes = L.lasso_ridge_f64_workspace_bytes(d, k)
+            if nbytes == 0:
+                M = A.clone()
+                M.diagonal().add_(lam_n)
+                return torch.cholesky_solve(B, torch.linalg.cholesky(M)).T.contiguous()
+            with torch.cuda.device(self.device):
+                ws = self._ws(nbytes, "ridge_f64")
+                V = torch.empty((d, k), dtype=torch.float64, device=self.device)
+                info = C.c_int32(0)
+                status = L.lasso_ridge_solve_f64(nat.ptr(A), nat.ptr(B), nat.ptr(V), V.stride(0), d, k, float(lam_n),
+                                                 C.byref(info) if check else None, nat.ptr(ws), ws.numel(),
+                                                 self._stream())
+                if info.value != 0:
+                    raise torch.linalg.LinAlgError(
+                        "linalg.cholesky: The factorization could not be completed because the input is not "
+                        "positive-definite (the leading minor of order %d is not positive-definite)." % info.value)
+                nat.check(status)
+            return V
         nbytes = L.lasso_ridge_workspace_bytes(d, k)
         if nbytes == 0:
             M = A.clone()

@@ -6,7 +6,7 @@ import torch.nn.functional as F
 
 from .. import _native as nat
 from ..engine import HipEngine
-from ..parallel import em_loop, constrained_mstep
+from ..parallel import em_loop, _em_loop_f64, constrained_mstep
 from .sparse_encode import sparse_encode
 
 
@@ -15,6 +15,15 @@ def _engine_for(*tensors, device=None):
         if t is not None and t.is_cuda:
             return HipEngine(t.device)
     return HipEngine(device)
+
+
+def _float64(what, *tensors):
+    """True when every tensor is float64 (the double M-step), False when none is; a mix of float64 with anything else
+    raises before any launch, as the reference's matmul would."""
+    f64 = [t.dtype == torch.float64 for t in tensors]
+    if any(f64) and not all(f64):
+        raise RuntimeError("%s: expected tensors of one dtype, got %s" % (what, ", ".join(str(t.dtype) for t in tensors)))
+    return all(f64)
 
 
 def lasso_loss(X, Z, weight, alpha=1.0):
@@ -38,12 +47,13 @@ def update_dict(dictionary, X, Z, random_seed=None, positive=False, eps=1e-10):
     updates ``dictionary`` AND ``Z`` in place (degenerate atoms get a fresh random
     direction drawn from torch's CPU generator and their codes are zeroed) and returns
     ``dictionary``."""
+    f64 = _float64("update_dict", dictionary, X, Z)
     if random_seed is not None:
         torch.manual_seed(random_seed)                               # :78-79
     eng = _engine_for(dictionary, X, Z)
     Dg, Xg, Zg = eng.to_device(dictionary), eng.to_device(X), eng.to_device(Z)
     d, k = Dg.shape
-    buf = torch.empty(k * k + k * d, dtype=torch.float32, device=eng.device)
+    buf = torch.empty(k * k + k * d, dtype=torch.float64 if f64 else torch.float32, device=eng.device)
     A, B = eng.gram(Zg, Xg, buf)
     mask = constrained_mstep(eng, A, B, Dg, eps=eps, positive=positive)
     if mask is not None:
@@ -57,12 +67,13 @@ def update_dict(dictionary, X, Z, random_seed=None, positive=False, eps=1e-10):
 
 def update_dict_ridge(x, z, lambd=1e-4):
     """Unconstrained M-step V = ((Z^T Z + lambd*n*I)^-1 Z^T X)^T (dict_learning.py:106-123)."""
+    f64 = _float64("update_dict_ridge", x, z)
     eng = _engine_for(x, z)
     out_device = x.device
     xg, zg = eng.to_device(x), eng.to_device(z)
     n, d = xg.shape
     k = zg.shape[1]
-    buf = torch.empty(k * k + k * d, dtype=torch.float32, device=eng.device)
+    buf = torch.empty(k * k + k * d, dtype=torch.float64 if f64 else torch.float32, device=eng.device)
     A, B = eng.gram(zg, xg, buf)
     return eng.ridge(A, B, lambd * n, check=True).to(out_device)
 
@@ -75,12 +86,18 @@ def dict_learning(X, n_components, alpha=1.0, constrained=True, persist=False,
     ``device`` names where the RESULT lives (reference default 'cpu'); the arithmetic
     always runs on the current HIP device.  The initial dictionary is drawn exactly like
     the reference (orthogonal_ + column normalisation on ``device``, :28-31) unless
-    ``init_weight`` (extension) is given.  Returns ``(weight [d,k], losses [steps])``."""
+    ``init_weight`` (extension) is given.  Returns ``(weight [d,k], losses [steps])``.
+    float64 ``X`` (an ``init_weight`` must then be float64 too): the whole loop runs in double -- dictionary drawn in
+    float64, float64 ``ista`` E-step, fp64-MFMA Gram product, atom sweep / Cholesky solve -- and ``losses`` is float64."""
     nat.require_gpu()
     n_samples, n_features = X.shape
     out_device = torch.device(device)
+    f64 = _float64("dict_learning", X, *([init_weight] if init_weight is not None else []))
     if init_weight is None:
-        weight = torch.empty(n_features, n_components, device=out_device)   # :28
+        # float64 X: the dictionary is drawn in X's dtype -- the reference's own draw whenever it can run at all
+        # (its torch.empty takes the default dtype, which must then be float64)
+        weight = torch.empty(n_features, n_components, device=out_device,
+                             **(dict(dtype=X.dtype) if f64 else {}))        # :28
         nn.init.orthogonal_(weight)                                         # :29
         if constrained:
             weight = F.normalize(weight, dim=0)                             # :30-31
@@ -88,6 +105,11 @@ def dict_learning(X, n_components, alpha=1.0, constrained=True, persist=False,
         weight = init_weight.detach().clone()
     eng = _engine_for(X if X.is_cuda else None,
                       device=out_device if out_device.type == 'cuda' else None)
+    if f64:          # the plain one-stream loop in double (parallel._em_loop_f64)
+        weight, losses = _em_loop_f64(eng, eng.to_device(X), eng.to_device(weight).clone(), alpha,
+                                      constrained=constrained, persist=persist, lambd=lambd, steps=steps,
+                                      progbar=progbar, solver_kwargs=solver_kwargs)
+        return weight.to(out_device), losses.to(out_device)
     weight, losses = em_loop(eng, eng.to_device(X), eng.to_device(weight).clone(), alpha,
                              constrained=constrained, persist=persist, lambd=lambd, steps=steps,
                              progbar=progbar, solver_kwargs=solver_kwargs)

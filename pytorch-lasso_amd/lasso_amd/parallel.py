@@ -72,13 +72,14 @@ def _broadcast(t, group):
     return t
 
 
-def draw_directions(d, count):
+def draw_directions(d, count, dtype=torch.float32):
     """`count` replacement directions for degenerate atoms, drawn the way the reference does
     (``dictionary[:, k].normal_()`` on a CPU tensor, dict_learning.py:93): same generator,
-    same non-contiguous-view code path, one draw per degenerate atom in atom order."""
-    buf = torch.empty(d, 2)
+    same non-contiguous-view code path, one draw per degenerate atom in atom order.  ``dtype``: the dictionary's
+    (a float64 column view consumes the generator differently from a float32 one)."""
+    buf = torch.empty(d, 2, dtype=dtype)
     col = buf[:, 0]
-    out = torch.empty(count, d)
+    out = torch.empty(count, d, dtype=dtype)
     for i in range(count):
         col.normal_()
         out[i] = col
@@ -96,7 +97,7 @@ def constrained_mstep(engine, A, B, D, eps=1e-10, positive=False, group=None):
     mask, ndeg = engine.sweep(A, B, D, None, eps, positive)
     if ndeg == 0:
         return None
-    cand = draw_directions(D.shape[0], ndeg).to(D.device)      # every rank advances its generator alike
+    cand = draw_directions(D.shape[0], ndeg, D.dtype).to(D.device)      # every rank advances its generator alike
     if _sharded(group):   # every rank must use rank 0's directions
         _broadcast(cand, group)
     engine.fill_degenerate(D, mask, cand, positive)
@@ -240,6 +241,9 @@ def em_loop(engine, X, weight, alpha, constrained=True, persist=False, lambd=1e-
     """The EM loop of dict_learning.py:35-53 on this rank's row shard ``X`` [n_local, d].
     ``weight`` [d,k] must be identical on every rank.  Returns (weight, losses[steps])."""
     solver_kwargs = dict(solver_kwargs or {})
+    if X.dtype == torch.float64 or weight.dtype == torch.float64:
+        raise NotImplementedError("em_loop: float64 tensors run the one-stream loop of dict_learning on one GPU "
+                                  "(parallel._em_loop_f64); the sharded / two-stream forms are float32 only")
     world, rank = _world(group)
     multi = _sharded(group)          # (world > 1, or one rank with LASSO_FORCE_COLLECTIVES=1: the same code paths)
     n_local, d = X.shape
@@ -433,6 +437,50 @@ def em_loop(engine, X, weight, alpha, constrained=True, persist=False, lambd=1e-
         mask, ndeg = deferred()
         if ndeg:
             repair(mask, ndeg, Zlast)
+    if bar is not None:
+        bar.close()
+    return weight, losses
+
+
+def _em_loop_f64(engine, X, weight, alpha, constrained=True, persist=False, lambd=1e-2, steps=60, progbar=False,
+                 solver_kwargs=None):
+    """The EM loop of dict_learning.py:35-53 for float64 tensors on one GPU: one stream, every step in the
+    reference's order with one host wait behind the sweep (its count of degenerate atoms) -- E-step (the float64
+    ``ista`` path), objective BEFORE the M-step, ``Z0 = Z`` if ``persist``, Gram product, then the atom sweep (an
+    atom that degenerated: draw, fill, zero the columns of Z, which a persisting Z0 aliases, :98) or the ridge solve.
+    Returns (weight, losses[steps] float64)."""
+    solver_kwargs = dict(solver_kwargs or {})
+    tensors = (X, weight)
+    if any(t.dtype != torch.float64 for t in tensors):
+        raise RuntimeError("_em_loop_f64: expected float64 X and weight, got %s and %s" % (X.dtype, weight.dtype))
+    algorithm = solver_kwargs.get('algorithm', 'ista')
+    if algorithm != 'ista':
+        raise NotImplementedError("dict_learning: algorithm=%r has no float64 form on the HIP path (float64 tensors "
+                                  "take the E-step algorithm='ista')" % (algorithm,))
+    n, d = X.shape
+    k = weight.shape[1]
+    losses = torch.zeros(steps, dtype=torch.float64, device=X.device)               # :34
+    buf = torch.empty(k * k + k * d, dtype=torch.float64, device=X.device)
+    Z0 = None
+    bar = None
+    if progbar:
+        from tqdm import tqdm
+        bar = tqdm(total=steps)
+    for i in range(steps):
+        Z = engine.encode(X, weight, alpha, Z0, **solver_kwargs)                    # :38
+        engine.objective_sums(X, Z, weight, alpha, loss_out=losses[i])              # :39
+        if persist:
+            Z0 = Z                                                                  # :40-41
+        A, B = engine.gram(Z, X, buf)
+        if constrained:
+            mask = constrained_mstep(engine, A, B, weight)                          # :44-45
+            if mask is not None:
+                engine.zero_columns(Z, mask)                                        # :98
+        else:
+            weight = engine.ridge(A, B, lambd * n, check=True)                      # :46-47
+        if bar is not None:
+            bar.set_postfix(loss=losses[i].item())                                  # :50
+            bar.update(1)
     if bar is not None:
         bar.close()
     return weight, losses
@@ -726,6 +774,9 @@ def dict_learning_sharded(X_shard, n_components, alpha=1.0, constrained=True, pe
     per GPU).  The initial dictionary is drawn on rank 0 exactly like the reference
     (orthogonal_ + normalisation on the CPU generator) and broadcast."""
     from .engine import HipEngine
+    if X_shard.dtype == torch.float64 or (init_weight is not None and init_weight.dtype == torch.float64):
+        raise NotImplementedError("dict_learning_sharded: float64 tensors are not supported by the multi-GPU driver "
+                                  "(its messages and kernels are float32); use dict_learning on one GPU")
     engine = engine or HipEngine()
     world, rank = _world(group)
     d = X_shard.shape[1]
