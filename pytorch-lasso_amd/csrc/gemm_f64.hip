@@ -23,7 +23,6 @@
 // the 160 KB LDS.
 #include <hip/hip_runtime.h>
 #include <math.h>
-#include <stdarg.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <algorithm>
@@ -31,6 +30,7 @@
 
 #include "../../include/lasso_hip.h"
 #include "lasso_kernels.h"
+#include "host_util.hpp"
 
 namespace lasso {
 namespace f64 {
@@ -300,8 +300,6 @@ __global__ __launch_bounds__(256) void objective_finish_kernel(const double* __r
   }
 }
 
-inline size_t align_up(size_t v, size_t a = 256) { return (v + a - 1) / a * a; }
-
 struct Workspace {
   double* Y; double* NR; double* G; double* dpart; double* delta;
   double* C; double* part; double* sums;          // line search only
@@ -311,53 +309,32 @@ struct Workspace {
 
 Workspace carve(void* base, int64_t n, int64_t d, int64_t k, bool backtrack, bool with_state) {
   Workspace w;
-  char* p = static_cast<char*>(base);
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    char* r = p ? p + off : nullptr;
-    off += align_up(bytes);
-    return reinterpret_cast<double*>(r);
-  };
-  w.Y = take((size_t)n * k * 8);
-  w.NR = take((size_t)n * d * 8);
-  w.G = (backtrack || with_state) ? take((size_t)n * k * 8) : nullptr;
-  w.dpart = take((size_t)std::max<int64_t>(kGrid, prox_parts(n, k)) * 8);
-  w.delta = take(64 * 8);
+  Arena a(base);
+  w.Y = a.take<double>((size_t)n * k * 8);
+  w.NR = a.take<double>((size_t)n * d * 8);
+  w.G = (backtrack || with_state) ? a.take<double>((size_t)n * k * 8) : nullptr;
+  w.dpart = a.take<double>((size_t)std::max<int64_t>(kGrid, prox_parts(n, k)) * 8);
+  w.delta = a.take<double>(64 * 8);
   w.C = w.part = w.sums = nullptr;
   if (backtrack) {
-    w.C = take((size_t)n * k * 8);
-    w.part = take((size_t)5 * kGrid * 8);
-    w.sums = take(256);
+    w.C = a.take<double>((size_t)n * k * 8);
+    w.part = a.take<double>((size_t)5 * kGrid * 8);
+    w.sums = a.take<double>(256);
   }
-  w.Yc = with_state ? take((size_t)n * k * 8) : nullptr;
-  w.bytes = off;
+  w.Yc = with_state ? a.take<double>((size_t)n * k * 8) : nullptr;
+  w.bytes = a.bytes();
   return w;
 }
 
-int fail(char* err, size_t errlen, int status, const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  if (err && errlen) vsnprintf(err, errlen, fmt, ap);
-  va_end(ap);
-  return status;
-}
-
-#define F64_TRY(expr)                                                                                   \
-  do {                                                                                                  \
-    hipError_t e_ = (expr);                                                                             \
-    if (e_ != hipSuccess)                                                                               \
-      return fail(err, errlen, LASSO_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_));           \
-  } while (0)
-
 int start_state(const double* z0, int64_t ldz0, double* zout, int64_t ldz, double* Y, int64_t n, int64_t k,
-                hipStream_t st, char* err, size_t errlen) {
+                hipStream_t st) {
   if (z0) {
     if (z0 != zout || ldz0 != ldz)
-      F64_TRY(hipMemcpy2DAsync(zout, ldz * 8, z0, ldz0 * 8, k * 8, n, hipMemcpyDeviceToDevice, st));
+      LASSO_HIP_TRY(hipMemcpy2DAsync(zout, ldz * 8, z0, ldz0 * 8, k * 8, n, hipMemcpyDeviceToDevice, st));
   } else {
-    F64_TRY(hipMemset2DAsync(zout, ldz * 8, 0, k * 8, n, st));
+    LASSO_HIP_TRY(hipMemset2DAsync(zout, ldz * 8, 0, k * 8, n, st));
   }
-  F64_TRY(hipMemcpy2DAsync(Y, k * 8, zout, ldz * 8, k * 8, n, hipMemcpyDeviceToDevice, st));
+  LASSO_HIP_TRY(hipMemcpy2DAsync(Y, k * 8, zout, ldz * 8, k * 8, n, hipMemcpyDeviceToDevice, st));
   return LASSO_OK;
 }
 
@@ -387,15 +364,14 @@ const char* solve_kernel_name(int backtrack) {
 // kernels sum in a fixed order, so the replay is bitwise the state the reference stops in.
 int solve(const double* x, int64_t ldx, const double* w, int64_t ldw, const double* z0, int64_t ldz0, double* zout,
           int64_t ldz, int64_t n, int64_t d, int64_t k, double alpha, double lr, int fast, int maxiter, double tol,
-          int32_t* iters_out, double* last_delta_out, void* workspace, size_t ws_bytes, hipStream_t st, char* err,
-          size_t errlen) {
+          int32_t* iters_out, double* last_delta_out, void* workspace, size_t ws_bytes, hipStream_t st) {
   const bool stop = tol > 0.0 && maxiter > 0;
   const Workspace ws = carve(workspace, n, d, k, false, stop);
-  if (ws_bytes < ws.bytes) return fail(err, errlen, LASSO_ERR_WORKSPACE, "workspace %zu < %zu bytes", ws_bytes, ws.bytes);
+  if (ws_bytes < ws.bytes) return fail(LASSO_ERR_WORKSPACE, "workspace %zu < %zu bytes", ws_bytes, ws.bytes);
   if (n > INT32_MAX - kBM || d > INT32_MAX - kBN || k > INT32_MAX - kBN || (k + kBN - 1) / kBN > 65535 ||
       (d + kBN - 1) / kBN > 65535)
-    return fail(err, errlen, LASSO_ERR_UNSUPPORTED, "shape too large");
-  if (int s = start_state(z0, ldz0, zout, ldz, ws.Y, n, k, st, err, errlen)) return s;
+    return fail(LASSO_ERR_UNSUPPORTED, "shape too large");
+  if (int s = start_state(z0, ldz0, zout, ldz, ws.Y, n, k, st)) return s;
   const double budget = (double)n * (double)k * tol;                       // z0.numel() * tol (ista.py:64)
   const double lam = alpha * lr;
   const int64_t parts = prox_parts(n, k);
@@ -404,13 +380,13 @@ int solve(const double* x, int64_t ldx, const double* w, int64_t ldw, const doub
     const double t_next = (1.0 + sqrt(1.0 + 4.0 * t_mom * t_mom)) / 2.0;    // :99
     const double coef = fast ? (t_mom - 1.0) / t_next : 0.0;
     // NR = x - y W^T (= -r);  the gradient r W = -(NR W) stays in the second product's accumulators
-    F64_TRY(gemm_sub(ws.Y, k, w, ldw, x, ldx, ws.NR, d, (int)n, (int)d, (int)k, st));
+    LASSO_HIP_TRY(gemm_sub(ws.Y, k, w, ldw, x, ldx, ws.NR, d, (int)n, (int)d, (int)k, st));
     GemmArgs g{ws.NR, d, w, ldw, nullptr, 0, zout, ldz, ws.Y, k, lr, lam, coef, ws.dpart, (int)n, (int)k, (int)d};
-    F64_TRY((launch_gemm<EPI_PROX, true>(g, st)));
+    LASSO_HIP_TRY((launch_gemm<EPI_PROX, true>(g, st)));
     t_mom = t_next;
     if (delta_slot) {
       hipLaunchKernelGGL(reduce_sets_kernel, dim3(1), dim3(256), 0, st, ws.dpart, parts, delta_slot);
-      F64_TRY(hipGetLastError());
+      LASSO_HIP_TRY(hipGetLastError());
     }
     return LASSO_OK;
   };
@@ -427,13 +403,13 @@ int solve(const double* x, int64_t ldx, const double* w, int64_t ldw, const doub
       const int c = std::min(chunk, maxiter - it);
       const double t_head = t_mom;
       if (c > 1) {
-        F64_TRY(hipMemcpy2DAsync(ws.G, k * 8, zout, ldz * 8, k * 8, n, hipMemcpyDeviceToDevice, st));
-        F64_TRY(hipMemcpyAsync(ws.Yc, ws.Y, (size_t)n * k * 8, hipMemcpyDeviceToDevice, st));
+        LASSO_HIP_TRY(hipMemcpy2DAsync(ws.G, k * 8, zout, ldz * 8, k * 8, n, hipMemcpyDeviceToDevice, st));
+        LASSO_HIP_TRY(hipMemcpyAsync(ws.Yc, ws.Y, (size_t)n * k * 8, hipMemcpyDeviceToDevice, st));
       }
       for (int j = 0; j < c; ++j)
         if (int s = iterate(ws.delta + j)) return s;
-      F64_TRY(hipMemcpyAsync(deltas, ws.delta, sizeof(double) * c, hipMemcpyDeviceToHost, st));
-      F64_TRY(hipStreamSynchronize(st));
+      LASSO_HIP_TRY(hipMemcpyAsync(deltas, ws.delta, sizeof(double) * c, hipMemcpyDeviceToHost, st));
+      LASSO_HIP_TRY(hipStreamSynchronize(st));
       int hit = -1;
       for (int j = 0; j < c && hit < 0; ++j)
         if (deltas[j] <= budget) hit = j;
@@ -446,8 +422,8 @@ int solve(const double* x, int64_t ldx, const double* w, int64_t ldw, const doub
       }
       last = deltas[hit];
       if (hit < c - 1) {
-        F64_TRY(hipMemcpy2DAsync(zout, ldz * 8, ws.G, k * 8, k * 8, n, hipMemcpyDeviceToDevice, st));
-        F64_TRY(hipMemcpyAsync(ws.Y, ws.Yc, (size_t)n * k * 8, hipMemcpyDeviceToDevice, st));
+        LASSO_HIP_TRY(hipMemcpy2DAsync(zout, ldz * 8, ws.G, k * 8, k * 8, n, hipMemcpyDeviceToDevice, st));
+        LASSO_HIP_TRY(hipMemcpyAsync(ws.Y, ws.Yc, (size_t)n * k * 8, hipMemcpyDeviceToDevice, st));
         t_mom = t_head;
         for (int j = 0; j <= hit; ++j)
           if (int s = iterate(nullptr)) return s;
@@ -468,13 +444,13 @@ int solve_backtracking(const double* x, int64_t ldx, const double* w, int64_t ld
                        double* zout, int64_t ldz, int64_t n, int64_t d, int64_t k, double alpha, double lr0, int fast,
                        int maxiter, double tol, double eta, int32_t* iters_out, double* last_delta_out,
                        int32_t* trials_out, double* accepted_lr_out, double* accepted_f_out, void* workspace,
-                       size_t ws_bytes, hipStream_t st, char* err, size_t errlen) {
+                       size_t ws_bytes, hipStream_t st) {
   const Workspace ws = carve(workspace, n, d, k, true, false);
-  if (ws_bytes < ws.bytes) return fail(err, errlen, LASSO_ERR_WORKSPACE, "workspace %zu < %zu bytes", ws_bytes, ws.bytes);
+  if (ws_bytes < ws.bytes) return fail(LASSO_ERR_WORKSPACE, "workspace %zu < %zu bytes", ws_bytes, ws.bytes);
   if (n > INT32_MAX - kBM || d > INT32_MAX - kBN || k > INT32_MAX - kBN || (k + kBN - 1) / kBN > 65535 ||
       (d + kBN - 1) / kBN > 65535)
-    return fail(err, errlen, LASSO_ERR_UNSUPPORTED, "shape too large");
-  if (int s = start_state(z0, ldz0, zout, ldz, ws.Y, n, k, st, err, errlen)) return s;
+    return fail(LASSO_ERR_UNSUPPORTED, "shape too large");
+  if (int s = start_state(z0, ldz0, zout, ldz, ws.Y, n, k, st)) return s;
   const double budget = (double)n * (double)k * tol;
   bool warned = false;
   double t_mom = 1.0, last = NAN;
@@ -483,10 +459,10 @@ int solve_backtracking(const double* x, int64_t ldx, const double* w, int64_t ld
     const double t_next = (1.0 + sqrt(1.0 + 4.0 * t_mom * t_mom)) / 2.0;             // :98
     const double coef = fast ? (t_mom - 1.0) / t_next : 0.0;                          // :99 (ISTA: y == z)
     // NR = x - p W^T (= -r0, :22);  G = r0 W (:24);  part[0 ..) = sum r0^2 (:23)
-    F64_TRY(gemm_sub(ws.Y, k, w, ldw, x, ldx, ws.NR, d, (int)n, (int)d, (int)k, st));
+    LASSO_HIP_TRY(gemm_sub(ws.Y, k, w, ldw, x, ldx, ws.NR, d, (int)n, (int)d, (int)k, st));
     {
       GemmArgs g{ws.NR, d, w, ldw, nullptr, 0, ws.G, k, nullptr, 0, 0.0, 0.0, 0.0, nullptr, (int)n, (int)k, (int)d};
-      F64_TRY((launch_gemm<EPI_SUB, true>(g, st)));
+      LASSO_HIP_TRY((launch_gemm<EPI_SUB, true>(g, st)));
     }
     hipLaunchKernelGGL(sumsq_kernel, dim3(kGrid), dim3(256), 0, st, ws.NR, n * d, ws.part);
     double lr = lr0, f_acc = NAN, lr_acc = lr0;
@@ -496,14 +472,14 @@ int solve_backtracking(const double* x, int64_t ldx, const double* w, int64_t ld
       const double lr_t = give_up ? lr0 : lr;                                           // :48-52
       hipLaunchKernelGGL(trial_kernel, dim3(kGrid), dim3(256), 0, st, ws.Y, ws.G, ws.C, n * k, lr_t, alpha * lr_t,
                          ws.part + 2 * kGrid);                                          // :40, :31-35
-      F64_TRY(hipGetLastError());
-      F64_TRY(gemm_sub(ws.C, k, w, ldw, x, ldx, ws.NR, d, (int)n, (int)d, (int)k, st));  // :27
+      LASSO_HIP_TRY(hipGetLastError());
+      LASSO_HIP_TRY(gemm_sub(ws.C, k, w, ldw, x, ldx, ws.NR, d, (int)n, (int)d, (int)k, st));  // :27
       hipLaunchKernelGGL(sumsq_kernel, dim3(kGrid), dim3(256), 0, st, ws.NR, n * d, ws.part + kGrid);
       hipLaunchKernelGGL(reduce_sets_kernel, dim3(5), dim3(256), 0, st, ws.part, (int64_t)kGrid, ws.sums);
-      F64_TRY(hipGetLastError());
+      LASSO_HIP_TRY(hipGetLastError());
       double hs[5];                                     // {sum r0^2, sum r1^2, sum |z1|, sum dz g, sum dz^2}
-      F64_TRY(hipMemcpyAsync(hs, ws.sums, sizeof(hs), hipMemcpyDeviceToHost, st));
-      F64_TRY(hipStreamSynchronize(st));
+      LASSO_HIP_TRY(hipMemcpyAsync(hs, ws.sums, sizeof(hs), hipMemcpyDeviceToHost, st));
+      LASSO_HIP_TRY(hipStreamSynchronize(st));
       const double f0 = 0.5 * hs[0];                                                    // :23
       const double F = 0.5 * hs[1] + alpha * hs[2];                                     // :28
       const double Q = f0 + hs[3] + (0.5 / lr_t) * hs[4] + alpha * hs[2];               // :32-35
@@ -518,9 +494,9 @@ int solve_backtracking(const double* x, int64_t ldx, const double* w, int64_t ld
     }
     hipLaunchKernelGGL(finish_kernel, dim3(kGrid), dim3(256), 0, st, zout, ldz, ws.Y, ws.C, n, k, coef, ws.dpart);
     hipLaunchKernelGGL(reduce_sets_kernel, dim3(1), dim3(256), 0, st, ws.dpart, (int64_t)kGrid, ws.delta);
-    F64_TRY(hipGetLastError());
-    F64_TRY(hipMemcpyAsync(&last, ws.delta, sizeof(double), hipMemcpyDeviceToHost, st));
-    F64_TRY(hipStreamSynchronize(st));
+    LASSO_HIP_TRY(hipGetLastError());
+    LASSO_HIP_TRY(hipMemcpyAsync(&last, ws.delta, sizeof(double), hipMemcpyDeviceToHost, st));
+    LASSO_HIP_TRY(hipStreamSynchronize(st));
     if (trials_out) trials_out[it] = trials;
     if (accepted_lr_out) accepted_lr_out[it] = lr_acc;
     if (accepted_f_out) accepted_f_out[it] = f_acc;
@@ -529,7 +505,7 @@ int solve_backtracking(const double* x, int64_t ldx, const double* w, int64_t ld
   }
   if (iters_out) *iters_out = it;
   if (last_delta_out) *last_delta_out = last;
-  return warned ? fail(err, errlen, LASSO_WARN_LINESEARCH, "backtracking line search failed; reverted to lr0") : LASSO_OK;
+  return warned ? fail(LASSO_WARN_LINESEARCH, "backtracking line search failed; reverted to lr0") : LASSO_OK;
 }
 
 size_t objective_workspace_bytes(int64_t n, int64_t d, int64_t k) {
@@ -540,32 +516,32 @@ size_t objective_workspace_bytes(int64_t n, int64_t d, int64_t k) {
 // loss = (0.5 ||x - z W^T||^2 + alpha ||z||_1) / n_total in double; sums (nullable) = {sum r^2, sum |z|}
 int objective(const double* x, int64_t ldx, const double* w, int64_t ldw, const double* z, int64_t ldz, int64_t n,
               int64_t d, int64_t k, double alpha, double* loss64, float* loss32, double* sums, void* workspace,
-              size_t ws_bytes, hipStream_t st, char* err, size_t errlen) {
+              size_t ws_bytes, hipStream_t st) {
   if (ws_bytes < objective_workspace_bytes(n, d, k))
-    return fail(err, errlen, LASSO_ERR_WORKSPACE, "need %zu bytes", objective_workspace_bytes(n, d, k));
+    return fail(LASSO_ERR_WORKSPACE, "need %zu bytes", objective_workspace_bytes(n, d, k));
   if (n > INT32_MAX - kBM || d > INT32_MAX - kBN || k > INT32_MAX - kBN || (d + kBN - 1) / kBN > 65535)
-    return fail(err, errlen, LASSO_ERR_UNSUPPORTED, "shape too large");
+    return fail(LASSO_ERR_UNSUPPORTED, "shape too large");
   if (n == 0) return LASSO_OK;
   char* base = static_cast<char*>(workspace);
   double* R = reinterpret_cast<double*>(base);
   double* part = reinterpret_cast<double*>(base + align_up((size_t)n * d * 8));
   double* own = part + 2 * kGrid;
-  F64_TRY(gemm_sub(z, ldz, w, ldw, x, ldx, R, d, (int)n, (int)d, (int)k, st));
+  LASSO_HIP_TRY(gemm_sub(z, ldz, w, ldw, x, ldx, R, d, (int)n, (int)d, (int)k, st));
   hipLaunchKernelGGL(sumsq_kernel, dim3(kGrid), dim3(256), 0, st, R, n * d, part);
   hipLaunchKernelGGL(sumabs_kernel, dim3(kGrid), dim3(256), 0, st, z, ldz, n, k, part + kGrid);
   hipLaunchKernelGGL(objective_finish_kernel, dim3(1), dim3(256), 0, st, part, (int64_t)kGrid, alpha, (double)n,
                      sums ? sums : own, loss64, loss32);
-  F64_TRY(hipGetLastError());
+  LASSO_HIP_TRY(hipGetLastError());
   return LASSO_OK;
 }
 
 // z0 [n][k] = x [n][d] W [d][k]   (init='transpose', sparse_encode.py:24-25)
 int init_transpose(const double* x, int64_t ldx, const double* w, int64_t ldw, double* z0, int64_t ldz, int64_t n,
-                   int64_t d, int64_t k, hipStream_t st, char* err, size_t errlen) {
+                   int64_t d, int64_t k, hipStream_t st) {
   if (n > INT32_MAX - kBM || d > INT32_MAX - kBN || k > INT32_MAX - kBN || (k + kBN - 1) / kBN > 65535)
-    return fail(err, errlen, LASSO_ERR_UNSUPPORTED, "shape too large");
+    return fail(LASSO_ERR_UNSUPPORTED, "shape too large");
   GemmArgs g{x, ldx, w, ldw, nullptr, 0, z0, ldz, nullptr, 0, 0.0, 0.0, 0.0, nullptr, (int)n, (int)k, (int)d};
-  F64_TRY((launch_gemm<EPI_PLAIN, true>(g, st)));
+  LASSO_HIP_TRY((launch_gemm<EPI_PLAIN, true>(g, st)));
   return LASSO_OK;
 }
 

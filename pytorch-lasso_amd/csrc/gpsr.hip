@@ -24,6 +24,7 @@
 
 #include "../../include/lasso_hip.h"
 #include "lasso_kernels.h"
+#include "host_util.hpp"
 #include "gemm_mainloop.hpp"
 
 namespace lasso {
@@ -597,8 +598,6 @@ hipError_t launch_gemm(const float* A, int64_t lda, const float* B, int64_t ldb,
   return launch_one<64, false, false, MODE>(A, lda, B, ldb, m, nn, kk, ep, rungs, st);
 }
 
-inline size_t align_up(size_t v, size_t a = 256) { return (v + a - 1) / a * a; }
-
 struct Space {
   float *Wt, *Ay, *U, *V, *Z, *T, *C, *Zc, *RB;
   double *part_g, *part_q, *part_t, *part_r, *part_e;
@@ -608,44 +607,28 @@ struct Space {
 
 Space carve(void* base, int64_t n, int64_t d, int64_t k) {
   Space w;
-  char* p = static_cast<char*>(base);
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    char* r = p ? p + off : nullptr;
-    off += align_up(bytes);
-    return r;
-  };
+  Arena a(base);
   const size_t nk = (size_t)n * k * 4, nd = (size_t)n * d * 4;
-  w.Wt = (float*)take((size_t)k * d * 4);
-  w.Ay = (float*)take(nk);
-  w.U = (float*)take(nk);
-  w.V = (float*)take(nk);
-  w.Z = (float*)take(nk);
-  w.T = (float*)take(nk);
-  w.C = (float*)take(nk);
-  w.Zc = (float*)take(nk * kLadder);
-  w.RB = (float*)take(nd * (kLadder + 1));
+  w.Wt = a.take((size_t)k * d * 4);
+  w.Ay = a.take(nk);
+  w.U = a.take(nk);
+  w.V = a.take(nk);
+  w.Z = a.take(nk);
+  w.T = a.take(nk);
+  w.C = a.take(nk);
+  w.Zc = a.take(nk * kLadder);
+  w.RB = a.take(nd * (kLadder + 1));
   // block partials: 64 x 64 blocks give the most
   const size_t pk = (size_t)gemm_parts((int)n, (int)k, 64) * kPart * 8, pd = (size_t)gemm_parts((int)n, (int)d, 64) * kPart * 8;
-  w.part_g = (double*)take(pk);
-  w.part_q = (double*)take(pd);
-  w.part_r = (double*)take(pd * kLadder);
-  w.part_t = (double*)take((size_t)kEwBlocks * kPart * 8 * kLadder);
-  w.part_e = (double*)take((size_t)kEwBlocks * kPart * 8);
-  w.ctl = (Ctl*)take(sizeof(Ctl));
-  w.bytes = off;
+  w.part_g = a.take<double>(pk);
+  w.part_q = a.take<double>(pd);
+  w.part_r = a.take<double>(pd * kLadder);
+  w.part_t = a.take<double>((size_t)kEwBlocks * kPart * 8 * kLadder);
+  w.part_e = a.take<double>((size_t)kEwBlocks * kPart * 8);
+  w.ctl = a.take<Ctl>(sizeof(Ctl));
+  w.bytes = a.bytes();
   return w;
 }
-
-int failf(char* err, size_t errlen, int status, const char* fmt, const char* what, hipError_t e) {
-  snprintf(err, errlen, fmt, what, hipGetErrorString(e));
-  return status;
-}
-#define GPSR_TRY(expr)                                                                                       \
-  do {                                                                                                       \
-    hipError_t e_ = (expr);                                                                                  \
-    if (e_ != hipSuccess) return failf(err, errlen, LASSO_ERR_HIP, "%s failed: %s", #expr, e_);              \
-  } while (0)
 
 }  // namespace
 
@@ -653,7 +636,7 @@ size_t workspace_bytes(int64_t n, int64_t d, int64_t k) { return carve(nullptr, 
 
 int solve(const float* x, int64_t ldx, const float* w, int64_t ldw, const float* z0, int64_t ldz0, float* zout, int64_t ldz,
           int64_t n64, int64_t d64, int64_t k64, double alpha, const lasso_gpsr_options& o, lasso_gpsr_result* res,
-          void* workspace, hipStream_t st, char* err, size_t errlen) {
+          void* workspace, hipStream_t st) {
   const int n = (int)n64, d = (int)d64, k = (int)k64;
   const int64_t nk = (int64_t)n * k, nd = (int64_t)n * d;
   const Space ws = carve(workspace, n, d, k);
@@ -661,8 +644,7 @@ int solve(const float* x, int64_t ldx, const float* w, int64_t ldw, const float*
   const int side_k = block_side(n, k, std::max<int64_t>({(int64_t)d, (int64_t)k, ldx}), cus);      // products [n,k]
   const int side_d = block_side(n, d, std::max<int64_t>({(int64_t)d, (int64_t)k, ldx, ldw}), cus);  // products [n,d]
   if (std::max<int64_t>({(int64_t)d, (int64_t)k, ldx, ldw}) * 64 * 4 >= ((int64_t)1 << 31)) {
-    snprintf(err, errlen, "row pitch beyond the 32-bit offsets of a 64-row block");
-    return LASSO_ERR_UNSUPPORTED;
+    return fail(LASSO_ERR_UNSUPPORTED, "row pitch beyond the 32-bit offsets of a 64-row block");
   }
   const int pk = gemm_parts(n, k, side_k), pd = gemm_parts(n, d, side_d);
   const int gk = ew_grid(nk);
@@ -679,20 +661,20 @@ int solve(const float* x, int64_t ldx, const float* w, int64_t ldw, const float*
   res->objective = 0.0;
 
   // ---- set-up: Wt, Ay = y W, max |Ay| ----
-  GPSR_TRY(hipMemsetAsync(ws.ctl, 0, sizeof(Ctl), st));
-  GPSR_TRY(launch_transpose_pad(w, ldw, d, k, ws.Wt, d, k, d, st));
+  LASSO_HIP_TRY(hipMemsetAsync(ws.ctl, 0, sizeof(Ctl), st));
+  LASSO_HIP_TRY(launch_transpose_pad(w, ldw, d, k, ws.Wt, d, k, d, st));
   Epi e0 = {};
   e0.Out = ws.Ay; e0.ldo = k;
-  GPSR_TRY(launch_gemm<EPI_STORE>(x, ldx, ws.Wt, d, n, k, d, e0, side_k, 1, st));
+  LASSO_HIP_TRY(launch_gemm<EPI_STORE>(x, ldx, ws.Wt, d, n, k, d, e0, side_k, 1, st));
   hipLaunchKernelGGL(absstat_kernel, dim3(gk), dim3(256), 0, st, ws.Ay, nk, (float*)nullptr, ws.part_e);
   hipLaunchKernelGGL(stat_kernel, dim3(1), dim3(256), 0, st, ws.part_e, gk, (const double*)nullptr, 0, ws.ctl);
-  GPSR_TRY(hipGetLastError());
-  GPSR_TRY(fetch());
+  LASSO_HIP_TRY(hipGetLastError());
+  LASSO_HIP_TRY(fetch());
   const double max_tau = (double)h.absmax;
   if (alpha >= max_tau) {                                   // gpsr.py:276-279: the solution is the zero vector
     res->flags |= LASSO_GPSR_ZERO_SOLUTION;
     hipLaunchKernelGGL(copy_out_kernel, dim3(gk), dim3(256), 0, st, ws.Z, zout, ldz, n, k, 1);
-    GPSR_TRY(hipGetLastError());
+    LASSO_HIP_TRY(hipGetLastError());
     return LASSO_OK;
   }
   // ---- continuation factors (gpsr.py:282-295) ----
@@ -730,23 +712,23 @@ int solve(const float* x, int64_t ldx, const float* w, int64_t ldw, const float*
     // u, v of the START (the reference hands every continuation step the pair formed before the loop), rb, f
     hipLaunchKernelGGL(init_kernel, dim3(gk), dim3(256), 0, st, start, ld_start, ws.Z, ws.U, ws.V, n, k, step > 0 ? 1 : 0,
                        ws.part_e);
-    GPSR_TRY(hipGetLastError());
+    LASSO_HIP_TRY(hipGetLastError());
     Epi er = {};
     er.Y = x; er.ldy = ldx; er.Out = rb; er.ldo = d; er.part = ws.part_r;
-    GPSR_TRY(launch_gemm<EPI_RESID>(ws.Z, k, w, ldw, n, d, k, er, side_d, 1, st));
+    LASSO_HIP_TRY(launch_gemm<EPI_RESID>(ws.Z, k, w, ldw, n, d, k, er, side_d, 1, st));
     hipLaunchKernelGGL(start_kernel, dim3(1), dim3(256), 0, st, ws.part_r, pd, ws.part_e, gk, tau, ws.ctl);
-    GPSR_TRY(hipGetLastError());
+    LASSO_HIP_TRY(hipGetLastError());
     bool have_start = false;
     while (true) {
       // gradient, curvature, lambda0
       Epi eg = {};
       eg.Ay = ws.Ay; eg.U = ws.U; eg.V = ws.V; eg.T = ws.T; eg.Cc = ws.C; eg.part = ws.part_g; eg.tau = tau;
-      GPSR_TRY(launch_gemm<EPI_GRAD>(rb, d, ws.Wt, d, n, k, d, eg, side_k, 1, st));
+      LASSO_HIP_TRY(launch_gemm<EPI_GRAD>(rb, d, ws.Wt, d, n, k, d, eg, side_k, 1, st));
       Epi eq = {};
       eq.part = ws.part_q;
-      GPSR_TRY(launch_gemm<EPI_SUMSQ>(ws.C, k, w, ldw, n, d, k, eq, side_d, 1, st));
+      LASSO_HIP_TRY(launch_gemm<EPI_SUMSQ>(ws.C, k, w, ldw, n, d, k, eq, side_d, 1, st));
       hipLaunchKernelGGL(lambda_kernel, dim3(1), dim3(256), 0, st, ws.part_g, pk, ws.part_q, pd, ws.ctl);
-      GPSR_TRY(hipGetLastError());
+      LASSO_HIP_TRY(hipGetLastError());
       // trials: rung 0 alone, then ladders of kLadder; the accept step and the criterion ride behind every batch
       int first = 0, accepted = -1;
       int slots[kLadder];
@@ -758,7 +740,7 @@ int solve(const float* x, int64_t ldx, const float* w, int64_t ldw, const float*
         }
         hipLaunchKernelGGL(trial_kernel, dim3(gk, count), dim3(256), 0, st, ws.U, ws.V, ws.T, ws.Z, ws.Zc, nk, tau, beta, first,
                            ws.ctl, ws.part_t);
-        GPSR_TRY(hipGetLastError());
+        LASSO_HIP_TRY(hipGetLastError());
         // (the rungs' slots are consecutive except around rb_slot: one launch per run of consecutive slots)
         for (int j = 0; j < count;) {
           int run = 1;
@@ -766,15 +748,15 @@ int solve(const float* x, int64_t ldx, const float* w, int64_t ldw, const float*
           Epi et = {};
           et.Y = x; et.ldy = ldx; et.Out = ws.RB + (int64_t)slots[j] * nd; et.ldo = d; et.out_stride = nd;
           et.a_stride = nk; et.part = ws.part_r + (int64_t)j * pd * kPart;
-          GPSR_TRY(launch_gemm<EPI_RESID>(ws.Zc + (int64_t)j * nk, k, w, ldw, n, d, k, et, side_d, run, st));
+          LASSO_HIP_TRY(launch_gemm<EPI_RESID>(ws.Zc + (int64_t)j * nk, k, w, ldw, n, d, k, et, side_d, run, st));
           j += run;
         }
         hipLaunchKernelGGL(decide_kernel, dim3(1), dim3(256), 0, st, ws.part_t, gk, ws.part_r, pd, first, count, tau, mu, beta,
                            ws.ctl);
         hipLaunchKernelGGL(finish_kernel, dim3(gk), dim3(256), 0, st, ws.U, ws.V, ws.T, ws.Z, nk, tau, ws.ctl, ws.part_e);
         hipLaunchKernelGGL(criterion_kernel, dim3(1), dim3(256), 0, st, ws.part_e, gk, crit_id, ws.ctl);
-        GPSR_TRY(hipGetLastError());
-        GPSR_TRY(fetch());                                  // the one host wait of an iteration whose first trial holds
+        LASSO_HIP_TRY(hipGetLastError());
+        LASSO_HIP_TRY(fetch());                                  // the one host wait of an iteration whose first trial holds
         if (!have_start && tr && step < tr->step_capacity) {
           tr->step_f0[step] = h.f0;
           tr->step_nz0[step] = h.nz0;
@@ -815,14 +797,14 @@ int solve(const float* x, int64_t ldx, const float* w, int64_t ldw, const float*
     Epi er = {};
     er.Y = x; er.ldy = ldx; er.Out = ws.RB + (int64_t)(rb_slot == 0 ? 1 : 0) * nd; er.ldo = d; er.part = ws.part_r;
     // (after a failed search rb may belong to a rejected candidate: recompute from z)
-    GPSR_TRY(launch_gemm<EPI_RESID0>(ws.Z, k, w, ldw, n, d, k, er, side_d, 1, st));
+    LASSO_HIP_TRY(launch_gemm<EPI_RESID0>(ws.Z, k, w, ldw, n, d, k, er, side_d, 1, st));
     hipLaunchKernelGGL(absstat_kernel, dim3(gk), dim3(256), 0, st, ws.Z, nk, ws.U /* mask */, ws.part_e);
     hipLaunchKernelGGL(stat_kernel, dim3(1), dim3(256), 0, st, ws.part_e, gk, ws.part_r, pd, ws.ctl);
     const int gd = ew_grid(nd);
     hipLaunchKernelGGL(rb_sumsq_kernel, dim3(gd), dim3(256), 0, st, x, ldx, rb, n, d, ws.part_t);
     hipLaunchKernelGGL(rb_stat_kernel, dim3(1), dim3(256), 0, st, ws.part_t, gd, ws.ctl);
-    GPSR_TRY(hipGetLastError());
-    GPSR_TRY(fetch());
+    LASSO_HIP_TRY(hipGetLastError());
+    LASSO_HIP_TRY(fetch());
     res->main_rr = failed ? h.rr : h.rr_rb;
     res->main_l1 = h.l1;
     res->main_nz = h.nz_db;
@@ -841,24 +823,24 @@ int solve(const float* x, int64_t ldx, const float* w, int64_t ldw, const float*
     } else {
       Epi em = {};
       em.Mask = MASK; em.Out = R; em.P = P; em.part = ws.part_g;
-      GPSR_TRY(launch_gemm<EPI_MASK_R>(RES, d, ws.Wt, d, n, k, d, em, side_k, 1, st));
+      LASSO_HIP_TRY(launch_gemm<EPI_MASK_R>(RES, d, ws.Wt, d, n, k, d, em, side_k, 1, st));
       hipLaunchKernelGGL(cg_start_kernel, dim3(1), dim3(256), 0, st, ws.part_g, pk, (float)o.tol_debias, ws.ctl);
-      GPSR_TRY(hipGetLastError());
+      LASSO_HIP_TRY(hipGetLastError());
       int it = 0;
       const int ge = ew_grid(nk + nd);
       while (true) {
         Epi ew = {};
         ew.Out = WP; ew.ldo = d;
-        GPSR_TRY(launch_gemm<EPI_STORE>(P, k, w, ldw, n, d, k, ew, side_d, 1, st));
+        LASSO_HIP_TRY(launch_gemm<EPI_STORE>(P, k, w, ldw, n, d, k, ew, side_d, 1, st));
         Epi ea = {};
         ea.Mask = MASK; ea.Out = AP; ea.P = P; ea.part = ws.part_g;
-        GPSR_TRY(launch_gemm<EPI_MASK_AP>(WP, d, ws.Wt, d, n, k, d, ea, side_k, 1, st));
+        LASSO_HIP_TRY(launch_gemm<EPI_MASK_AP>(WP, d, ws.Wt, d, n, k, d, ea, side_k, 1, st));
         hipLaunchKernelGGL(cg_alpha_kernel, dim3(1), dim3(256), 0, st, ws.part_g, pk, ws.ctl);
         hipLaunchKernelGGL(cg_axpy_kernel, dim3(ge), dim3(256), 0, st, ws.Z, R, P, AP, nk, RES, WP, nd, ws.ctl, ws.part_e);
         hipLaunchKernelGGL(cg_beta_kernel, dim3(1), dim3(256), 0, st, ws.part_e, ge, tau, ws.ctl);
         hipLaunchKernelGGL(cg_dir_kernel, dim3(gk), dim3(256), 0, st, P, R, nk, ws.ctl);
-        GPSR_TRY(hipGetLastError());
-        GPSR_TRY(fetch());
+        LASSO_HIP_TRY(hipGetLastError());
+        LASSO_HIP_TRY(fetch());
         ++it;
         if (tr && it <= tr->db_capacity) {
           tr->db_rr[it - 1] = h.rr_db;
@@ -872,16 +854,16 @@ int solve(const float* x, int64_t ldx, const float* w, int64_t ldw, const float*
       res->n_iter = n_iter + it;
       hipLaunchKernelGGL(absstat_kernel, dim3(gk), dim3(256), 0, st, ws.Z, nk, (float*)nullptr, ws.part_e);
       hipLaunchKernelGGL(stat_kernel, dim3(1), dim3(256), 0, st, ws.part_e, gk, (const double*)nullptr, 0, ws.ctl);
-      GPSR_TRY(hipGetLastError());
-      GPSR_TRY(fetch());
+      LASSO_HIP_TRY(hipGetLastError());
+      LASSO_HIP_TRY(fetch());
       res->db_rr = h.rr_db;
       res->db_l1 = h.l1;
       res->db_nz = h.nz_db;
     }
   }
   hipLaunchKernelGGL(copy_out_kernel, dim3(gk), dim3(256), 0, st, ws.Z, zout, ldz, n, k, 0);
-  GPSR_TRY(hipGetLastError());
-  GPSR_TRY(hipStreamSynchronize(st));
+  LASSO_HIP_TRY(hipGetLastError());
+  LASSO_HIP_TRY(hipStreamSynchronize(st));
   return LASSO_OK;
 }
 

@@ -16,11 +16,11 @@
 
 #include "../../include/lasso_hip.h"
 #include "lasso_kernels.h"
+#include "host_util.hpp"
 
 namespace lasso {
-namespace {
 
-thread_local char g_err[512] = "";
+static thread_local char g_err[512] = "";
 
 int fail(int status, const char* fmt, ...) {
   va_list ap;
@@ -30,14 +30,7 @@ int fail(int status, const char* fmt, ...) {
   return status;
 }
 
-#define LASSO_HIP_TRY(expr)                                                         \
-  do {                                                                              \
-    hipError_t e_ = (expr);                                                         \
-    if (e_ != hipSuccess)                                                           \
-      return fail(LASSO_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_));    \
-  } while (0)
-
-inline size_t align_up(size_t v, size_t a = 256) { return (v + a - 1) / a * a; }
+namespace {
 
 int pad_k(int64_t k) {
   if (k <= 256) return 256;
@@ -74,35 +67,28 @@ struct Workspace {
 
 Workspace carve(void* base, int64_t n, int64_t k, int kp, int coef_cap, bool with_state) {
   Workspace w;
-  char* p = static_cast<char*>(base);
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    char* r = p ? p + off : nullptr;
-    off += align_up(bytes);
-    return reinterpret_cast<float*>(r);
-  };
+  Arena a(base);
   const int64_t ntiles = (n + kTileM - 1) / kTileM;
-  w.wp = take((size_t)kFistaD * kp * 4);
-  w.wtp = take((size_t)kp * kFistaD * 4);
-  w.coef = take((size_t)std::max(coef_cap, 1) * 4);
-  w.zeros = take((size_t)std::max(coef_cap, 1) * 4);
+  w.wp = a.take((size_t)kFistaD * kp * 4);
+  w.wtp = a.take((size_t)kp * kFistaD * 4);
+  w.coef = a.take((size_t)std::max(coef_cap, 1) * 4);
+  w.zeros = a.take((size_t)std::max(coef_cap, 1) * 4);
   const int members = kp / 128;                       // split-k: members per group
   // [kChunkMax][ntiles] of the tile kernel, then the split-k kernel's rows: one partial per
   // workgroup and round, rounds * groups * members <= (ntiles + 256) * members
-  w.partials = take((size_t)kChunkMax * ntiles * 4 + (size_t)kChunkMax * (ntiles + kSplitMaxParts) * members * 4);
-  w.delta = take((size_t)kChunkMax * 4);
-  w.gran = reinterpret_cast<unsigned long long*>(
-      take((size_t)kStopRing * std::max<int64_t>(ntiles, kSplitMaxParts) * 8));
-  w.stop_out = reinterpret_cast<int*>(take(256));
+  w.partials = a.take((size_t)kChunkMax * ntiles * 4 + (size_t)kChunkMax * (ntiles + kSplitMaxParts) * members * 4);
+  w.delta = a.take((size_t)kChunkMax * 4);
+  w.gran = a.take<unsigned long long>((size_t)kStopRing * std::max<int64_t>(ntiles, kSplitMaxParts) * 8);
+  w.stop_out = a.take<int>(256);
   // exchange payload of the split-k kernel: up to 256 workgroups x T tiles at once, T by batch size
   {
     const int64_t slots = (ntiles * members + kSplitMaxParts - 1) / kSplitMaxParts;   // tiles per group if all 256 CUs take part
     const int tmax = slots <= 1 ? 1 : slots <= 2 ? 2 : kSplitkMaxTiles;
-    w.xch = take(fista_splitk_exchange_bytes(kp, kSplitMaxParts / members, tmax));
+    w.xch = a.take(fista_splitk_exchange_bytes(kp, kSplitMaxParts / members, tmax));
   }
-  w.xflags = reinterpret_cast<unsigned*>(take(kSplitkFlagBytes));
-  for (int i = 0; i < 4; ++i) w.state[i] = with_state ? take((size_t)n * k * 4) : nullptr;
-  w.bytes = off;
+  w.xflags = a.take<unsigned>(kSplitkFlagBytes);
+  for (int i = 0; i < 4; ++i) w.state[i] = with_state ? a.take((size_t)n * k * 4) : nullptr;
+  w.bytes = a.bytes();
   return w;
 }
 
@@ -692,50 +678,44 @@ struct BtWorkspace {
 
 BtWorkspace carve_bt(void* base, int64_t n, int64_t k, int kp, bool half = false, int maxiter = 0) {
   BtWorkspace w;
-  char* p = static_cast<char*>(base);
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    char* r = p ? p + off : nullptr;
-    off += align_up(bytes);
-    return reinterpret_cast<float*>(r);
-  };
+  Arena a(base);
   const int64_t ntiles = (n + kTileM - 1) / kTileM;
-  w.wp = take((size_t)kFistaD * kp * 4);
-  w.wtp = take((size_t)kp * kFistaD * 4);
-  w.partials = take((size_t)5 * std::max<int64_t>(ntiles, 1) * 4);
-  w.partsM = take((size_t)kBtMultiMax * 4 * std::max<int64_t>(ntiles, 1) * 4);
-  w.dpart = take((size_t)kBtFinishGrid * 4);
-  w.dtile = take((size_t)std::max<int64_t>(ntiles, 1) * 4);
-  w.delta = take(256);
-  w.flags = reinterpret_cast<int*>(take(256));
-  w.fvals = take(256);
-  w.sums = reinterpret_cast<double*>(take((size_t)kBtMaxTrials * 5 * sizeof(double)));
-  w.G = take((size_t)n * k * 4);
-  w.C = take((size_t)n * k * 4);
-  w.Y = take((size_t)n * k * 4);
-  w.Zf = half ? take((size_t)n * k * 4) : nullptr;      // (wp / wtp hold the two bf16 packs then)
+  w.wp = a.take((size_t)kFistaD * kp * 4);
+  w.wtp = a.take((size_t)kp * kFistaD * 4);
+  w.partials = a.take((size_t)5 * std::max<int64_t>(ntiles, 1) * 4);
+  w.partsM = a.take((size_t)kBtMultiMax * 4 * std::max<int64_t>(ntiles, 1) * 4);
+  w.dpart = a.take((size_t)kBtFinishGrid * 4);
+  w.dtile = a.take((size_t)std::max<int64_t>(ntiles, 1) * 4);
+  w.delta = a.take(256);
+  w.flags = a.take<int>(256);
+  w.fvals = a.take(256);
+  w.sums = a.take<double>((size_t)kBtMaxTrials * 5 * sizeof(double));
+  w.G = a.take((size_t)n * k * 4);
+  w.C = a.take((size_t)n * k * 4);
+  w.Y = a.take((size_t)n * k * 4);
+  w.Zf = half ? a.take((size_t)n * k * 4) : nullptr;      // (wp / wtp hold the two bf16 packs then)
   w.pG = w.pZ0 = w.pgran = nullptr; w.pcoef = nullptr; w.pout = nullptr; w.ptrials = nullptr; w.plrs = w.pfvals = nullptr;
   if (half) {
     const int64_t nt64 = (n + 63) / 64;
     const int cap = std::max(maxiter, 1);
-    w.pG = take((size_t)nt64 * 64 * kp * 2);
-    w.pZ0 = take((size_t)n * k * 2);
-    w.pcoef = take((size_t)cap * 4 * 2);
-    w.pgran = take(bt16_persist_granule_bytes((int)std::max<int64_t>(nt64, 1)));
-    w.pout = reinterpret_cast<int*>(take(256));
-    w.ptrials = reinterpret_cast<int*>(take((size_t)cap * 4));
-    w.plrs = take((size_t)cap * 4);
-    w.pfvals = take((size_t)cap * 4);
+    w.pG = a.take((size_t)nt64 * 64 * kp * 2);
+    w.pZ0 = a.take((size_t)n * k * 2);
+    w.pcoef = a.take((size_t)cap * 4 * 2);
+    w.pgran = a.take(bt16_persist_granule_bytes((int)std::max<int64_t>(nt64, 1)));
+    w.pout = a.take<int>(256);
+    w.ptrials = a.take<int>((size_t)cap * 4);
+    w.plrs = a.take((size_t)cap * 4);
+    w.pfvals = a.take((size_t)cap * 4);
   }
   {   // line search enqueued without host waits: the per-iteration record and the control words
     const int cap = std::max(maxiter, 1);
-    w.rtrials = reinterpret_cast<int*>(take((size_t)cap * 4));
-    w.rlrs = take((size_t)cap * 4);
-    w.rfs = take((size_t)cap * 4);
-    w.ctl = reinterpret_cast<int*>(take(256));
-    w.rrec = take((size_t)cap * 16);
+    w.rtrials = a.take<int>((size_t)cap * 4);
+    w.rlrs = a.take((size_t)cap * 4);
+    w.rfs = a.take((size_t)cap * 4);
+    w.ctl = a.take<int>(256);
+    w.rrec = a.take((size_t)cap * 16);
   }
-  w.bytes = off;
+  w.bytes = a.bytes();
   return w;
 }
 
@@ -1276,31 +1256,25 @@ struct GenWorkspace { float* Wt; float* Y; float* NR; float* G; float* dpart; fl
 // (fixed-iteration solves paid n k words for a buffer they never touch)
 GenWorkspace carve_generic(void* base, int64_t n, int64_t d, int64_t k, bool backtrack = false, bool with_state = true) {
   GenWorkspace w;
-  char* p = static_cast<char*>(base);
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    char* r = p ? p + off : nullptr;
-    off += align_up(bytes);
-    return reinterpret_cast<float*>(r);
-  };
-  w.Wt = take((size_t)k * d * 4);
-  w.Wc = take((size_t)d * k * 4);             // (both dictionary copies first: their place does not depend on n)
-  w.Y = take((size_t)n * k * 4);
-  w.NR = take((size_t)n * d * 4);
-  w.G = take((size_t)n * k * 4);
+  Arena a(base);
+  w.Wt = a.take((size_t)k * d * 4);
+  w.Wc = a.take((size_t)d * k * 4);             // (both dictionary copies first: their place does not depend on n)
+  w.Y = a.take((size_t)n * k * 4);
+  w.NR = a.take((size_t)n * d * 4);
+  w.G = a.take((size_t)n * k * 4);
   // per-block sums of |z - z_next|: the fused GEMM-2 + prox launch writes one per 64 x 64 (or larger) block
-  w.dpart = take(std::max<size_t>((size_t)kGenGrid, (size_t)((n + 63) / 64) * (size_t)((k + 63) / 64)) * 4);
-  w.delta = take(256);
+  w.dpart = a.take(std::max<size_t>((size_t)kGenGrid, (size_t)((n + 63) / 64) * (size_t)((k + 63) / 64)) * 4);
+  w.delta = a.take(256);
   w.C = w.part = w.fvals = nullptr; w.flags = nullptr; w.sums = nullptr;
   if (backtrack) {
-    w.C = take((size_t)n * k * 4);
-    w.part = take((size_t)5 * kGenGrid * 4);
-    w.flags = reinterpret_cast<int*>(take(256));
-    w.fvals = take(256);
-    w.sums = reinterpret_cast<double*>(take(256));
+    w.C = a.take((size_t)n * k * 4);
+    w.part = a.take((size_t)5 * kGenGrid * 4);
+    w.flags = a.take<int>(256);
+    w.fvals = a.take(256);
+    w.sums = a.take<double>(256);
   }
-  w.Yc = with_state ? take((size_t)n * k * 4) : nullptr;
-  w.bytes = off;
+  w.Yc = with_state ? a.take((size_t)n * k * 4) : nullptr;
+  w.bytes = a.bytes();
   return w;
 }
 
@@ -1523,22 +1497,16 @@ struct CdWorkspace { float* S; float* Wt; float* B; float* Zt; int* active; int*
 
 CdWorkspace carve_cd(void* base, int64_t n, int64_t d, int kp) {
   CdWorkspace w;
-  char* p = static_cast<char*>(base);
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    char* r = p ? p + off : nullptr;
-    off += align_up(bytes);
-    return r;
-  };
-  w.S = (float*)take((size_t)kp * kp * 4);
-  w.Wt = (float*)take((size_t)kp * d * 4);
-  w.B = (float*)take((size_t)n * kp * 4);
-  w.Zt = (float*)take((size_t)n * kp * 4);
-  w.active = (int*)take((size_t)n * 4);
-  w.row_steps = (int*)take((size_t)n * 4);
-  w.counter = (int*)take(256);
-  w.info = (int*)take(256);
-  w.bytes = off;
+  Arena a(base);
+  w.S = a.take((size_t)kp * kp * 4);
+  w.Wt = a.take((size_t)kp * d * 4);
+  w.B = a.take((size_t)n * kp * 4);
+  w.Zt = a.take((size_t)n * kp * 4);
+  w.active = a.take<int>((size_t)n * 4);
+  w.row_steps = a.take<int>((size_t)n * 4);
+  w.counter = a.take<int>(256);
+  w.info = a.take<int>(256);
+  w.bytes = a.bytes();
   return w;
 }
 
@@ -1561,29 +1529,23 @@ struct ConvWorkspace { float* Wt; float* Wp; void* Wf; float* Zm; float* Ym; flo
 
 ConvWorkspace carve_conv(void* base, const ConvGeom& g) {
   ConvWorkspace w;
-  char* p = static_cast<char*>(base);
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    char* r = p ? p + off : nullptr;
-    off += align_up(std::max<size_t>(bytes, 4));
-    return r;
-  };
+  Arena a(base, 4);
   const size_t ckk = (size_t)g.C * g.kh * g.kw, M = (size_t)g.N * g.Hz * g.Wz;
   const size_t ldr = (ckk + 3) / 4 * 4;       // row stride of the pixel-major patch matrix
-  w.Wt = (float*)take(ckk * g.K * 4);
-  w.Wp = (float*)take(ldr * g.K * 4);
-  w.Wf = take(conv_fused_table_bytes());
-  w.Zm = (float*)take(M * g.K * 4);
-  w.Ym = (float*)take(M * g.K * 4);
-  w.G = (float*)take(M * g.K * 4);
-  w.PT = (float*)take(ldr * M * 4);
-  w.R = (float*)take((size_t)g.N * g.C * g.H * g.W * 4);
-  w.dpart = (float*)take((size_t)kConvDpart * 4);
-  w.delta = (float*)take(256);
-  w.sums = (double*)take(256);
-  w.Zc = (float*)take(M * g.K * 4);
-  w.Yc = (float*)take(M * g.K * 4);
-  w.bytes = off;
+  w.Wt = a.take(ckk * g.K * 4);
+  w.Wp = a.take(ldr * g.K * 4);
+  w.Wf = a.take(conv_fused_table_bytes());
+  w.Zm = a.take(M * g.K * 4);
+  w.Ym = a.take(M * g.K * 4);
+  w.G = a.take(M * g.K * 4);
+  w.PT = a.take(ldr * M * 4);
+  w.R = a.take((size_t)g.N * g.C * g.H * g.W * 4);
+  w.dpart = a.take((size_t)kConvDpart * 4);
+  w.delta = a.take(256);
+  w.sums = a.take<double>(256);
+  w.Zc = a.take(M * g.K * 4);
+  w.Yc = a.take(M * g.K * 4);
+  w.bytes = a.bytes();
   return w;
 }
 
@@ -1714,21 +1676,6 @@ static size_t solver_workspace_bytes(int64_t n, int64_t d, int64_t k, int dtype,
   return std::max(bytes, carve_generic(nullptr, n, d, k, false, with_state).bytes);
 }
 
-// region behind the solver's workspace that objective_out needs: the lasso_objective workspace,
-// a device float, and -- bf16 tensors -- fp32 copies of x, W and z
-static size_t objective_region_bytes(int64_t n, int64_t d, int64_t k, int dtype) {
-  size_t b = align_up(lasso_objective_workspace_bytes(n, d, k)) + 256;
-  if (dtype == LASSO_BF16)
-    b += align_up((size_t)n * d * 4) + align_up((size_t)d * k * 4) + align_up((size_t)n * k * 4);
-  return b;
-}
-
-// region behind that for lr = LASSO_LR_AUTO: the Lipschitz workspace, then {lr, alpha*lr} as floats
-static size_t lipschitz_region_bytes(int64_t d, int64_t k, int dtype) {
-  if (dtype != LASSO_F32 || std::min(d, k) > 2048) return 0;
-  return align_up(lipschitz_workspace_bytes(d, k)) + 256;
-}
-
 // {lr, alpha*lr} in fp32 from L (double) with the roundings of the host path: lr = 1/L in
 // double (ista.py:72-73), then the casts of run_impl()
 __global__ void step_from_lipschitz_kernel(const double* __restrict__ L, double alpha, float* __restrict__ out) {
@@ -1737,16 +1684,24 @@ __global__ void step_from_lipschitz_kernel(const double* __restrict__ L, double 
   out[1] = (float)(alpha * lr);
 }
 
-// LASSO_F64: the solver's workspace, then the objective's behind a 256-byte slot for the device double of the loss
-// (objective_out), then the Lipschitz computation's, whose first double is lambda_max (lr = LASSO_LR_AUTO; absent when
-// min(d, k) > 2048)
-struct F64Regions { size_t solver, objective, lipschitz, total; };
-static F64Regions f64_workspace(int64_t n, int64_t d, int64_t k, int maxiter, double tol, int stop_mode, int backtrack) {
-  F64Regions r;
-  r.solver = align_up(f64::solve_workspace_bytes(n, d, k, maxiter, tol, stop_mode, backtrack));
-  r.objective = align_up(f64::objective_workspace_bytes(n, d, k)) + 256;
-  r.lipschitz = std::min(d, k) > 2048 ? 0 : align_up(lipschitz_workspace_bytes(d, k));
-  r.total = r.solver + r.objective + r.lipschitz;
+// One solve's workspace, any dtype: solver | objective | lipschitz.
+//  objective (objective_out): a 256-byte slot for the device scalar of the loss, the objective's own workspace, and --
+//    bf16 tensors -- fp32 copies of x, W and z
+//  lipschitz (lr = LASSO_LR_AUTO; absent for bf16 tensors and when min(d, k) > 2048): the Lipschitz workspace, whose first
+//    double is lambda_max, and -- fp32 tensors -- a 256-byte slot for {lr, alpha*lr} as floats
+// fp32 / bf16 shapes without a solver (solver == 0) have no workspace: total == 0.
+struct SolveRegions { size_t solver, objective, lipschitz, total; };
+static SolveRegions solve_regions(int64_t n, int64_t d, int64_t k, int dtype, int maxiter, double tol, int stop_mode,
+                                  int backtrack) {
+  const bool dbl = dtype == LASSO_F64;
+  SolveRegions r;
+  r.solver = align_up(dbl ? f64::solve_workspace_bytes(n, d, k, maxiter, tol, stop_mode, backtrack)
+                          : solver_workspace_bytes(n, d, k, dtype, maxiter, tol, stop_mode, backtrack));
+  r.objective = align_up(dbl ? f64::objective_workspace_bytes(n, d, k) : lasso_objective_workspace_bytes(n, d, k)) + 256;
+  if (dtype == LASSO_BF16)
+    r.objective += align_up((size_t)n * d * 4) + align_up((size_t)d * k * 4) + align_up((size_t)n * k * 4);
+  r.lipschitz = (dtype == LASSO_BF16 || std::min(d, k) > 2048) ? 0 : align_up(lipschitz_workspace_bytes(d, k)) + (dbl ? 0 : 256);
+  r.total = (r.solver == 0 && !dbl) ? 0 : r.solver + r.objective + r.lipschitz;
   return r;
 }
 
@@ -1801,10 +1756,7 @@ const char* lasso_fista_kernel_name(int64_t n, int64_t d, int64_t k, int dtype, 
 size_t lasso_fista_workspace_bytes(int64_t n, int64_t d, int64_t k, int dtype, int maxiter,
                                    double tol, int stop_mode, int backtrack) {
   if (n < 0 || d <= 0 || k <= 0) return 0;
-  if (dtype == LASSO_F64) return f64_workspace(n, d, k, maxiter, tol, stop_mode, backtrack).total;
-  const size_t solver = solver_workspace_bytes(n, d, k, dtype, maxiter, tol, stop_mode, backtrack);
-  if (solver == 0) return 0;
-  return align_up(solver) + objective_region_bytes(n, d, k, dtype) + lipschitz_region_bytes(d, k, dtype);
+  return solve_regions(n, d, k, dtype, maxiter, tol, stop_mode, backtrack).total;
 }
 
 int lasso_fista_prepare(const void* w_dev, int64_t ldw, int64_t d, int64_t k, int dtype, int maxiter,
@@ -2170,7 +2122,7 @@ int lasso_fista_solve_f64(const void* x_dev, int64_t ldx, const void* w_dev, int
   if (maxiter < 0) return fail(LASSO_ERR_BAD_ARG, "maxiter < 0");
   if (backtrack && !(eta_backtrack > 1.0)) return fail(LASSO_ERR_BAD_ARG, "eta must be > 1.");     // ista.py:18-19
   if (stop_mode == LASSO_STOP_NONE) tol = 0.0;
-  const F64Regions reg = f64_workspace(n, d, k, maxiter, tol, stop_mode, backtrack);
+  const SolveRegions reg = solve_regions(n, d, k, LASSO_F64, maxiter, tol, stop_mode, backtrack);
   hipStream_t st = (hipStream_t)stream;
   if (lr == LASSO_LR_AUTO) {                            // lr = 1 / lambda_max(W^T W) (ista.py:59-63), one host round trip
     if (reg.lipschitz == 0) return fail(LASSO_ERR_UNSUPPORTED, "lr = LASSO_LR_AUTO: min(d,k) > 2048");
@@ -2187,28 +2139,24 @@ int lasso_fista_solve_f64(const void* x_dev, int64_t ldx, const void* w_dev, int
     if (last_delta_out) *last_delta_out = maxiter > 0 ? 0.0 : NAN;
     return LASSO_OK;
   }
-  char msg[400] = "";
   int status;
   if (backtrack)
     status = f64::solve_backtracking((const double*)x_dev, ldx, (const double*)w_dev, ldw, (const double*)z0_dev, ldz0,
                                      (double*)z_out_dev, ldz, n, d, k, alpha, lr, fast, maxiter, tol, eta_backtrack,
                                      iters_out, last_delta_out, trials_out, accepted_lr_out, accepted_f_out,
-                                     workspace_dev, std::min(workspace_bytes, reg.solver), st, msg, sizeof(msg));
+                                     workspace_dev, std::min(workspace_bytes, reg.solver), st);
   else
     status = f64::solve((const double*)x_dev, ldx, (const double*)w_dev, ldw, (const double*)z0_dev, ldz0,
                         (double*)z_out_dev, ldz, n, d, k, alpha, lr, fast, maxiter, tol, iters_out, last_delta_out,
-                        workspace_dev, std::min(workspace_bytes, reg.solver), st, msg, sizeof(msg));
-  if (status != LASSO_OK) fail(status, "%s", msg);
+                        workspace_dev, std::min(workspace_bytes, reg.solver), st);
   if ((status != LASSO_OK && status != LASSO_WARN_LINESEARCH) || !objective_out) return status;
   // objective_out: the mean objective of the RETURNED code, in double (ista.py:66-69)
   if (workspace_bytes < reg.solver + reg.objective)
     return fail(LASSO_ERR_WORKSPACE, "objective_out: workspace %zu < %zu bytes", workspace_bytes, reg.solver + reg.objective);
   double* const loss_dev = (double*)((char*)workspace_dev + reg.solver);
-  char msg2[400] = "";
   if (int s2 = f64::objective((const double*)x_dev, ldx, (const double*)w_dev, ldw, (const double*)z_out_dev, ldz, n, d,
-                              k, alpha, loss_dev, nullptr, nullptr, (char*)loss_dev + 256, reg.objective - 256, st, msg2,
-                              sizeof(msg2)))
-    return fail(s2, "%s", msg2);
+                              k, alpha, loss_dev, nullptr, nullptr, (char*)loss_dev + 256, reg.objective - 256, st))
+    return s2;
   LASSO_HIP_TRY(hipMemcpyAsync(objective_out, loss_dev, sizeof(double), hipMemcpyDeviceToHost, st));
   LASSO_HIP_TRY(hipStreamSynchronize(st));
   return status;
@@ -2270,16 +2218,15 @@ int lasso_fista_solve(const void* x_dev, int64_t ldx, const void* w_dev, int64_t
     // paths need the step size on the host (line-search bookkeeping, the unfused driver).
     if (dtype != LASSO_F32) return fail(LASSO_ERR_BAD_ARG, "lr = LASSO_LR_AUTO needs fp32 tensors (ista.py:12)");
     if (!x_dev || !w_dev || d <= 0 || k <= 0 || n < 0 || ldw < k) return fail(LASSO_ERR_BAD_ARG, "bad argument");
-    const size_t lip = lipschitz_region_bytes(d, k, dtype);
-    if (lip == 0) return fail(LASSO_ERR_UNSUPPORTED, "lr = LASSO_LR_AUTO: min(d,k) > 2048");
-    const size_t before = align_up(solver_workspace_bytes(n, d, k, dtype, maxiter, tol, stop_mode, backtrack)) +
-                          objective_region_bytes(n, d, k, dtype);
-    if (!workspace_dev || workspace_bytes < before + lip)
-      return fail(LASSO_ERR_WORKSPACE, "workspace %zu < %zu bytes", workspace_bytes, before + lip);
+    const SolveRegions reg = solve_regions(n, d, k, dtype, maxiter, tol, stop_mode, backtrack);
+    if (reg.lipschitz == 0) return fail(LASSO_ERR_UNSUPPORTED, "lr = LASSO_LR_AUTO: min(d,k) > 2048");
+    const size_t before = reg.solver + reg.objective;
+    if (!workspace_dev || workspace_bytes < before + reg.lipschitz)
+      return fail(LASSO_ERR_WORKSPACE, "workspace %zu < %zu bytes", workspace_bytes, before + reg.lipschitz);
     hipStream_t st = (hipStream_t)stream;
     char* const lip_ws = (char*)workspace_dev + before;
     if (fused_shape(d, k) && !backtrack && maxiter > 0 && n > 0) {
-      float* const slot = (float*)(lip_ws + align_up(lipschitz_workspace_bytes(d, k)));
+      float* const slot = (float*)(lip_ws + reg.lipschitz - 256);
       lip_dev = (const double*)lip_ws;                 // solve_impl enqueues the Lipschitz launches with its prepare blocks;
       lip_deferred = lip_ws;                           //   the launch that finishes lambda_max fills the slot
       lr_dev = slot;
@@ -2302,21 +2249,19 @@ int lasso_fista_solve(const void* x_dev, int64_t ldx, const void* w_dev, int64_t
   // (the verbose print of ista.py:66-69,80-81 for the final iterate; dict_learning.py:10-13)
   char saved[sizeof(g_err)];
   memcpy(saved, g_err, sizeof(saved));          // keep the line-search warning text
-  const size_t solver = align_up(solver_workspace_bytes(n, d, k, dtype, maxiter, tol, stop_mode, backtrack));
-  if (!workspace_dev || workspace_bytes < solver + objective_region_bytes(n, d, k, dtype))
+  const SolveRegions reg = solve_regions(n, d, k, dtype, maxiter, tol, stop_mode, backtrack);
+  if (!workspace_dev || workspace_bytes < reg.solver + reg.objective)
     return fail(LASSO_ERR_WORKSPACE, "objective_out: workspace %zu < %zu bytes", workspace_bytes,
-                solver + objective_region_bytes(n, d, k, dtype));
+                reg.solver + reg.objective);
   hipStream_t st = (hipStream_t)stream;
-  char* base = (char*)workspace_dev + solver;
-  float* loss_dev = (float*)base;
-  char* obj_ws = base + 256;
+  Arena a((char*)workspace_dev + reg.solver);
+  float* loss_dev = a.take(256);
   const size_t obj_bytes = align_up(lasso_objective_workspace_bytes(n, d, k));
+  char* obj_ws = a.take<char>(obj_bytes);
   const void* xo = x_dev; const void* wo = w_dev; const void* zo = z_out_dev;
   int64_t ldxo = ldx, ldwo = ldw, ldzo = ldz;
   if (dtype == LASSO_BF16) {
-    float* xf = (float*)(obj_ws + obj_bytes);
-    float* wf = (float*)((char*)xf + align_up((size_t)n * d * 4));
-    float* zf = (float*)((char*)wf + align_up((size_t)d * k * 4));
+    float* xf = a.take((size_t)n * d * 4), * wf = a.take((size_t)d * k * 4), * zf = a.take((size_t)n * k * 4);
     LASSO_HIP_TRY(launch_cvt_bf16(x_dev, ldx, xf, d, (int)n, (int)d, 1, st));
     LASSO_HIP_TRY(launch_cvt_bf16(w_dev, ldw, wf, k, (int)d, (int)k, 1, st));
     LASSO_HIP_TRY(launch_cvt_bf16(z_out_dev, ldz, zf, k, (int)n, (int)k, 1, st));
@@ -2511,12 +2456,8 @@ static int objective_f64_impl(const void* x_dev, int64_t ldx, const void* w_dev,
                                               (long long)d, (long long)k);
   if (!x_dev || !w_dev || !z_dev || !workspace_dev) return fail(LASSO_ERR_BAD_ARG, "null pointer");
   if (ldx < d || ldw < k || ldz < k) return fail(LASSO_ERR_BAD_ARG, "leading dimension too small");
-  char msg[400] = "";
-  if (int s = f64::objective((const double*)x_dev, ldx, (const double*)w_dev, ldw, (const double*)z_dev, ldz, n, d, k,
-                             alpha, loss_dev, loss32_dev, sums_dev, workspace_dev, workspace_bytes, (hipStream_t)stream,
-                             msg, sizeof(msg)))
-    return fail(s, "%s", msg);
-  return LASSO_OK;
+  return f64::objective((const double*)x_dev, ldx, (const double*)w_dev, ldw, (const double*)z_dev, ldz, n, d, k, alpha,
+                        loss_dev, loss32_dev, sums_dev, workspace_dev, workspace_bytes, (hipStream_t)stream);
 }
 
 int lasso_objective_f64(const void* x_dev, int64_t ldx, const void* w_dev, int64_t ldw, const void* z_dev, int64_t ldz,
@@ -2990,13 +2931,8 @@ int lasso_init_transpose(int64_t n, int64_t d, int64_t k, int dtype, const void*
     return fail(LASSO_ERR_WORKSPACE, "need %zu bytes", lasso_init_transpose_workspace_bytes(d, k));
   if (n == 0) return LASSO_OK;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (dtype == LASSO_F64) {                                 // reads W as it is: the workspace is not used
-    char msg[400] = "";
-    if (int s = f64::init_transpose((const double*)x_dev, ldx, (const double*)w_dev, ldw, (double*)z0_dev, ldz, n, d, k,
-                                    st, msg, sizeof(msg)))
-      return fail(s, "%s", msg);
-    return LASSO_OK;
-  }
+  if (dtype == LASSO_F64)                                   // reads W as it is: the workspace is not used
+    return f64::init_transpose((const double*)x_dev, ldx, (const double*)w_dev, ldw, (double*)z0_dev, ldz, n, d, k, st);
   float* const Wt = (float*)workspace_dev;                  // [k][d]: z0 = x Wt^T on the NT GEMM
   LASSO_HIP_TRY(launch_transpose_pad((const float*)w_dev, ldw, (int)d, (int)k, Wt, d, (int)k, (int)d, st));
   LASSO_HIP_TRY(launch_gemm_nt_sub((const float*)x_dev, ldx, Wt, d, nullptr, 0, (float*)z0_dev, ldz, (int)n, (int)k,
@@ -3038,11 +2974,8 @@ int lasso_gpsr_solve(const void* x_dev, int64_t ldx, const void* w_dev, int64_t 
   if (ldx < d || ldw < k || ldz < k || (z0_dev && ldz0 < k)) return fail(LASSO_ERR_BAD_ARG, "leading dimension too small");
   if (workspace_bytes < lasso_gpsr_workspace_bytes(n, d, k, dtype))
     return fail(LASSO_ERR_WORKSPACE, "need %zu bytes", lasso_gpsr_workspace_bytes(n, d, k, dtype));
-  char msg[400] = "";
-  if (int s = gpsr::solve((const float*)x_dev, ldx, (const float*)w_dev, ldw, (const float*)z0_dev, ldz0, (float*)z_out_dev,
-                          ldz, n, d, k, alpha, *o, res, workspace_dev, static_cast<hipStream_t>(stream), msg, sizeof(msg)))
-    return fail(s, "%s", msg);
-  return LASSO_OK;
+  return gpsr::solve((const float*)x_dev, ldx, (const float*)w_dev, ldw, (const float*)z0_dev, ldz0, (float*)z_out_dev,
+                     ldz, n, d, k, alpha, *o, res, workspace_dev, static_cast<hipStream_t>(stream));
 }
 
 // ---- unconstrained M-step: update_dict_ridge, dict_learning.py:106-123 ---------------------
@@ -3480,23 +3413,17 @@ struct ConvBwWorkspace {
 };
 ConvBwWorkspace carve_conv_bw(void* base, const ConvGeom& g, int cus) {
   ConvBwWorkspace w;
-  char* p = static_cast<char*>(base);
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    char* r = p ? p + off : nullptr;
-    off += align_up(std::max<size_t>(bytes, 4));
-    return reinterpret_cast<float*>(r);
-  };
+  Arena a(base, 4);
   const size_t ckk = (size_t)g.C * g.kh * g.kw, M = (size_t)g.N * g.Hz * g.Wz, ldr = (ckk + 3) / 4 * 4;
   const size_t mk = M * g.K * 4, img = (size_t)g.N * g.C * g.H * g.W * 4, kc = ckk * g.K * 4;
-  w.Wt = take(kc); w.Wp = take(ldr * g.K * 4);
-  w.zbA = take(mk); w.zbB = take(mk); w.yb = take(mk); w.ub = take(mk); w.gb = take(mk); w.y = take(mk);
-  w.R = take(img); w.RB = take(img);
-  w.PT = take(ldr * M * 4);
-  w.T1 = take(kc); w.T2 = take(kc); w.scratch = take(16 * kc);
+  w.Wt = a.take(kc); w.Wp = a.take(ldr * g.K * 4);
+  w.zbA = a.take(mk); w.zbB = a.take(mk); w.yb = a.take(mk); w.ub = a.take(mk); w.gb = a.take(mk); w.y = a.take(mk);
+  w.R = a.take(img); w.RB = a.take(img);
+  w.PT = a.take(ldr * M * 4);
+  w.T1 = a.take(kc); w.T2 = a.take(kc); w.scratch = a.take(16 * kc);
   w.splits = std::max(conv_wgrad_splits(g, cus), 1);
-  w.part = take((size_t)w.splits * kc);
-  w.bytes = off;
+  w.part = a.take((size_t)w.splits * kc);
+  w.bytes = a.bytes();
   return w;
 }
 }  // namespace
@@ -3632,20 +3559,14 @@ namespace {
 struct BwWorkspace { float* Wt; float* zbA; float* zbB; float* yb; float* ub; float* gb; float* y; float* nr; float* rb; float* T1; float* T2; float* scratch; size_t bytes; };
 BwWorkspace carve_bw(void* base, int64_t n, int64_t d, int64_t k) {
   BwWorkspace w;
-  char* p = static_cast<char*>(base);
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    char* r = p ? p + off : nullptr;
-    off += align_up(std::max<size_t>(bytes, 4));
-    return reinterpret_cast<float*>(r);
-  };
+  Arena a(base, 4);
   const size_t nk = (size_t)n * k * 4, nd = (size_t)n * d * 4, dk = (size_t)d * k * 4;
-  w.Wt = take(dk);
-  w.zbA = take(nk); w.zbB = take(nk); w.yb = take(nk); w.ub = take(nk); w.gb = take(nk); w.y = take(nk);
-  w.nr = take(nd); w.rb = take(nd);
-  w.T1 = take(dk); w.T2 = take(dk);
-  w.scratch = take(16 * dk);
-  w.bytes = off;
+  w.Wt = a.take(dk);
+  w.zbA = a.take(nk); w.zbB = a.take(nk); w.yb = a.take(nk); w.ub = a.take(nk); w.gb = a.take(nk); w.y = a.take(nk);
+  w.nr = a.take(nd); w.rb = a.take(nd);
+  w.T1 = a.take(dk); w.T2 = a.take(dk);
+  w.scratch = a.take(16 * dk);
+  w.bytes = a.bytes();
   return w;
 }
 }  // namespace

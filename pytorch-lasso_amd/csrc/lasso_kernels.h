@@ -477,25 +477,24 @@ hipError_t launch_lipschitz_f64(const double* W, int64_t ldw, int64_t d, int64_t
                                 hipStream_t stream);
 
 // float64 tensors (LASSO_F64, gemm_f64.hip): drivers of the fp64-MFMA general-GEMM path.  They return a lasso_status and
-// leave the detail text of a failure in err[errlen].
+// report the detail text of a failure through lasso::fail (host_util.hpp).
 namespace f64 {
 size_t solve_workspace_bytes(int64_t n, int64_t d, int64_t k, int maxiter, double tol, int stop_mode, int backtrack);
 const char* solve_kernel_name(int backtrack);
 int solve(const double* x, int64_t ldx, const double* w, int64_t ldw, const double* z0, int64_t ldz0, double* zout,
           int64_t ldz, int64_t n, int64_t d, int64_t k, double alpha, double lr, int fast, int maxiter, double tol,
-          int32_t* iters_out, double* last_delta_out, void* workspace, size_t ws_bytes, hipStream_t st, char* err,
-          size_t errlen);
+          int32_t* iters_out, double* last_delta_out, void* workspace, size_t ws_bytes, hipStream_t st);
 int solve_backtracking(const double* x, int64_t ldx, const double* w, int64_t ldw, const double* z0, int64_t ldz0,
                        double* zout, int64_t ldz, int64_t n, int64_t d, int64_t k, double alpha, double lr0, int fast,
                        int maxiter, double tol, double eta, int32_t* iters_out, double* last_delta_out,
                        int32_t* trials_out, double* accepted_lr_out, double* accepted_f_out, void* workspace,
-                       size_t ws_bytes, hipStream_t st, char* err, size_t errlen);
+                       size_t ws_bytes, hipStream_t st);
 size_t objective_workspace_bytes(int64_t n, int64_t d, int64_t k);
 int objective(const double* x, int64_t ldx, const double* w, int64_t ldw, const double* z, int64_t ldz, int64_t n,
               int64_t d, int64_t k, double alpha, double* loss64, float* loss32, double* sums, void* workspace,
-              size_t ws_bytes, hipStream_t st, char* err, size_t errlen);
+              size_t ws_bytes, hipStream_t st);
 int init_transpose(const double* x, int64_t ldx, const double* w, int64_t ldw, double* z0, int64_t ldz, int64_t n,
-                   int64_t d, int64_t k, hipStream_t st, char* err, size_t errlen);
+                   int64_t d, int64_t k, hipStream_t st);
 // C = C0 - A B^T on gemm_f64_nt_kernel; b_t = 0: B [nn][kk], else B [kk][nn]; C may be C0 (gemm_f64.hip)
 hipError_t launch_gemm_sub(const double* A, int64_t lda, const double* B, int64_t ldb, int b_t, const double* C0,
                            int64_t ldc0, double* C, int64_t ldc, int m, int nn, int kk, hipStream_t st);
@@ -518,12 +517,12 @@ hipError_t launch_ridge_solve(const double* A, const double* B, double* V, int64
                               void* workspace, int* info_dev, hipStream_t st);
 }  // namespace f64
 
-// GPSR-Basic (gpsr.hip): the driver behind lasso_gpsr_solve; returns a lasso_status, failure text in err[errlen]
+// GPSR-Basic (gpsr.hip): the driver behind lasso_gpsr_solve; returns a lasso_status, failure text through lasso::fail
 namespace gpsr {
 size_t workspace_bytes(int64_t n, int64_t d, int64_t k);
 int solve(const float* x, int64_t ldx, const float* w, int64_t ldw, const float* z0, int64_t ldz0, float* zout, int64_t ldz,
           int64_t n, int64_t d, int64_t k, double alpha, const lasso_gpsr_options& o, lasso_gpsr_result* res, void* workspace,
-          hipStream_t st, char* err, size_t errlen);
+          hipStream_t st);
 }  // namespace gpsr
 
 }  // namespace lasso

@@ -21,6 +21,7 @@
 #include <algorithm>
 #include <type_traits>
 #include "lasso_kernels.h"
+#include "host_util.hpp"
 #include "static_for.hpp"
 
 namespace lasso {
@@ -2234,7 +2235,7 @@ MstepPipePlan mstep_pipe_plan(int64_t n, int64_t d, int64_t k, int cus) {
   // the group boundaries (profiles/r06/pipe_stamps_4stage.txt).
   const int nb = (int)(k / kG3B), workers = (int)(k / kSweepBlock);
   const int head = (nb + 1) / 2;
-  size_t off = 0;
+  Arena scratch(nullptr);          // (offsets only: the stages' partial sums, one region each)
   int lo = 0;
   while (lo < nb) {
     const int hi = lo == 0 ? head : lo + 1, s = pl.nstages++;
@@ -2250,11 +2251,11 @@ MstepPipePlan mstep_pipe_plan(int64_t n, int64_t d, int64_t k, int cus) {
     rps = std::max(rps, 2 * kG3S);
     splits = (int)((n + rps - 1) / rps);
     pl.lo[s] = lo; pl.hi[s] = hi; pl.blocks[s] = blocks;
-    pl.splits[s] = splits; pl.rps[s] = rps; pl.scratch_off[s] = off;
-    off += ((size_t)splits * (hi - lo) * kG3B * (size_t)(k + d) * 4 + 255) & ~(size_t)255;
+    pl.splits[s] = splits; pl.rps[s] = rps; pl.scratch_off[s] = scratch.bytes();
+    scratch.take((size_t)splits * (hi - lo) * kG3B * (size_t)(k + d) * 4);
     lo = hi;
   }
-  pl.scratch_bytes = off;
+  pl.scratch_bytes = scratch.bytes();
   return pl;
 }
 

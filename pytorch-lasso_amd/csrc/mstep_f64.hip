@@ -28,6 +28,7 @@
 #include <algorithm>
 
 #include "lasso_kernels.h"
+#include "host_util.hpp"
 
 namespace lasso {
 namespace f64 {
@@ -388,14 +389,6 @@ __global__ __launch_bounds__(256) void ridge_back_f64_kernel(double* V, int64_t 
   }
 }
 
-inline size_t align_up(size_t v, size_t a = 256) { return (v + a - 1) / a * a; }
-
-#define F64M_TRY(expr)                  \
-  do {                                  \
-    hipError_t e_ = (expr);             \
-    if (e_ != hipSuccess) return e_;    \
-  } while (0)
-
 }  // namespace
 
 // Row slabs of the two products: none below kGramSplitMinRows rows; else enough to give every CU two workgroups of
@@ -461,16 +454,18 @@ hipError_t launch_sweep(const double* A, const double* B, double* D, int64_t ldd
   p.ndeg = reinterpret_cast<int*>(base + sweep_count_offset(d, k));
   p.k = k; p.d = d; p.eps = eps; p.positive = positive;
   // U[j][f] = B[j][f] - sum_i A[j][i] D[f][i]
-  F64M_TRY(launch_gemm_sub(A, k, D, ldd, 0, B, d, p.U, d, k, d, k, st));
+  if (hipError_t e = launch_gemm_sub(A, k, D, ldd, 0, B, d, p.U, d, k, d, k, st); e != hipSuccess) return e;
   for (int j0 = 0; j0 < k; j0 += kJB) {
     if (d <= 256) hipLaunchKernelGGL(sweep_block_f64_kernel<4>, dim3(1), dim3(256), 0, st, p, j0);
     else if (d <= 512) hipLaunchKernelGGL(sweep_block_f64_kernel<8>, dim3(1), dim3(512), 0, st, p, j0);
     else hipLaunchKernelGGL(sweep_block_f64_kernel<16>, dim3(1), dim3(1024), 0, st, p, j0);
-    F64M_TRY(hipGetLastError());
+    if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
     const int below = k - j0 - kJB;
     if (below > 0)       // U[j' >= j0 + 32] -= A[j', block] dD
-      F64M_TRY(launch_gemm_sub(A + (int64_t)(j0 + kJB) * k + j0, k, p.dD, d, 1, p.U + (int64_t)(j0 + kJB) * d, d,
-                               p.U + (int64_t)(j0 + kJB) * d, d, below, d, kJB, st));
+      if (hipError_t e = launch_gemm_sub(A + (int64_t)(j0 + kJB) * k + j0, k, p.dD, d, 1, p.U + (int64_t)(j0 + kJB) * d, d,
+                                         p.U + (int64_t)(j0 + kJB) * d, d, below, d, kJB, st);
+          e != hipSuccess)
+        return e;
   }
   return hipSuccess;
 }
@@ -503,26 +498,32 @@ hipError_t launch_ridge_solve(const double* A, const double* B, double* V, int64
   const int64_t total = (int64_t)(k + d) * k;
   hipLaunchKernelGGL(ridge_setup_f64_kernel, dim3((unsigned)std::min<int64_t>((total + 255) / 256, 4096)), dim3(256), 0, st,
                      A, B, S, k, d, lam, info_dev);
-  F64M_TRY(hipGetLastError());
+  if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
   for (int c0 = 0; c0 < k; c0 += kRB) {
     const int nb = std::min(kRB, k - c0), c1 = c0 + nb, below = k + d - c1;
     hipLaunchKernelGGL(chol_diag_f64_kernel, dim3(1), dim3(256), 0, st, S, ld, c0, nb, info_dev);
     hipLaunchKernelGGL(chol_panel_f64_kernel, dim3((unsigned)((below + 255) / 256)), dim3(256), 0, st, S, ld, c0, nb, c1,
                        k + d);
-    F64M_TRY(hipGetLastError());
+    if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
     if (c1 < k)          // S[c1.., c1..k) -= P P[0 .. k - c1)^T, P = S[c1.., c0..c1)
-      F64M_TRY(launch_gemm_sub(S + (int64_t)c1 * ld + c0, ld, S + (int64_t)c1 * ld + c0, ld, 0, S + (int64_t)c1 * ld + c1,
-                               ld, S + (int64_t)c1 * ld + c1, ld, below, k - c1, nb, st));
+      if (hipError_t e = launch_gemm_sub(S + (int64_t)c1 * ld + c0, ld, S + (int64_t)c1 * ld + c0, ld, 0,
+                                         S + (int64_t)c1 * ld + c1, ld, S + (int64_t)c1 * ld + c1, ld, below, k - c1, nb, st);
+          e != hipSuccess)
+        return e;
   }
   // rows k.. of S = Y^T = B^T L^-T; V L = Y^T, block columns from the last to the first
-  F64M_TRY(hipMemcpy2DAsync(V, (size_t)ldv * 8, S + (int64_t)k * ld, (size_t)ld * 8, (size_t)k * 8, (size_t)d,
-                            hipMemcpyDeviceToDevice, st));
+  if (hipError_t e = hipMemcpy2DAsync(V, (size_t)ldv * 8, S + (int64_t)k * ld, (size_t)ld * 8, (size_t)k * 8, (size_t)d,
+                                      hipMemcpyDeviceToDevice, st);
+      e != hipSuccess)
+    return e;
   for (int c0 = (k - 1) / kRB * kRB; c0 >= 0; c0 -= kRB) {
     const int nb = std::min(kRB, k - c0), c1 = c0 + nb;
     if (c1 < k)          // V[:, c0..c1) -= V[:, c1..k) L[c1..k, c0..c1)
-      F64M_TRY(launch_gemm_sub(V + c1, ldv, S + (int64_t)c1 * ld + c0, ld, 1, V + c0, ldv, V + c0, ldv, d, nb, k - c1, st));
+      if (hipError_t e = launch_gemm_sub(V + c1, ldv, S + (int64_t)c1 * ld + c0, ld, 1, V + c0, ldv, V + c0, ldv, d, nb, k - c1, st);
+          e != hipSuccess)
+        return e;
     hipLaunchKernelGGL(ridge_back_f64_kernel, dim3((unsigned)((d + 255) / 256)), dim3(256), 0, st, V, ldv, d, S, ld, c0, nb);
-    F64M_TRY(hipGetLastError());
+    if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
   }
   return hipSuccess;
 }

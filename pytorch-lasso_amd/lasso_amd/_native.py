@@ -307,6 +307,28 @@ def require_gpu():
                           "False); this package has no CPU fallback")
 
 
+DT = {torch.float32: LASSO_F32, torch.bfloat16: LASSO_BF16, torch.float64: LASSO_F64}
+
+
+def one_dtype(what, *tensors):
+    """True: every tensor is float64 (the double entry points); False: none is.  A mix raises before any launch
+    (the reference's matmul raises there too).  None entries are ignored."""
+    f64 = [t.dtype == torch.float64 for t in tensors if t is not None]
+    if any(f64) and not all(f64):
+        raise RuntimeError("%s: expected tensors of one dtype, got %s"
+                           % (what, ", ".join(str(t.dtype) for t in tensors if t is not None)))
+    return bool(f64) and all(f64)
+
+
+def pick_device(*tensors):
+    """The device a call runs on: that of the first tensor on a HIP device, else the current HIP device (tensors that
+    live on the CPU are staged through it)."""
+    for t in tensors:
+        if t is not None and t.is_cuda:
+            return t.device
+    return torch.device('cuda', torch.cuda.current_device())
+
+
 def stream_ptr(device):
     return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 

@@ -42,7 +42,7 @@ def conv_loss(x, z, weight, alpha, stride=1, padding=0):
     """(0.5*||x - conv_transpose2d(z, W)||^2 + alpha*||z||_1) / N on the GPU (ista.py:23-26)."""
     nat.require_gpu()
     geom = _geometry(x, z, weight, stride, padding)
-    dev = x.device if x.is_cuda else torch.device('cuda', torch.cuda.current_device())
+    dev = nat.pick_device(x)
     xg, zg, wg = (t.detach().to(dev).contiguous() for t in (x, z, weight))
     L = nat.lib()
     loss = torch.empty((), dtype=torch.float32, device=dev)
@@ -168,8 +168,7 @@ def ista_conv2d(x, z0, weight, alpha=1.0, stride=1, padding=0, fast=True,
     if maxiter == 0:
         return (z0, dict(iterations=0, last_delta=float('nan'))) if return_info else z0
     out_device = z0.device
-    dev = x.device if x.is_cuda else (weight.device if weight.is_cuda else
-                                      (z0.device if z0.is_cuda else torch.device('cuda', torch.cuda.current_device())))
+    dev = nat.pick_device(x, weight, z0)
     if wants_grad:
         # CPU inputs are staged through the device inside the graph: their gradients arrive on their own devices
         info = {}

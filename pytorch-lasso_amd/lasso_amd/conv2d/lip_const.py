@@ -25,7 +25,7 @@ def lip_bound_conv2d(kernel, padding, stride=1, sample=50, sqrt=False):
     if kernel.dtype != torch.float32:
         raise NotImplementedError("lasso_amd: lip_bound_conv2d is implemented for float32 kernels")
     out_device = kernel.device
-    dev = kernel.device if kernel.is_cuda else torch.device('cuda', torch.cuda.current_device())
+    dev = nat.pick_device(kernel)
     wg = kernel.detach().to(dev).contiguous()
     K, Cin, ks, _ = wg.shape
     L = nat.lib()

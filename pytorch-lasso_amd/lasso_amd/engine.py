@@ -13,6 +13,23 @@ import torch
 from . import _native as nat
 
 
+# Entry points of the objective and the M-step by precision: op -> float64 tensors? -> (entry point, its workspace
+# query, workspace cache tag).  HipEngine._entry resolves a row.
+_ENTRY = {
+    'objective': {False: ('lasso_objective_throttled', 'lasso_objective_workspace_bytes', 'obj'),
+                  True: ('lasso_objective_f64', 'lasso_objective_f64_workspace_bytes', 'obj')},
+    'gram': {False: ('lasso_gram_accumulate', 'lasso_gram_workspace_bytes', 'gram'),
+             True: ('lasso_gram_accumulate_f64', 'lasso_gram_f64_workspace_bytes', 'gram_f64')},
+    'sweep': {False: ('lasso_dict_sweep', 'lasso_dict_sweep_workspace_bytes', 'sweep'),
+              True: ('lasso_dict_sweep_f64', 'lasso_dict_sweep_f64_workspace_bytes', 'sweep_f64')},
+    'fill_degenerate': {False: ('lasso_dict_fill_degenerate', None, None),
+                        True: ('lasso_dict_fill_degenerate_f64', None, None)},
+    'zero_columns': {False: ('lasso_zero_columns', None, None), True: ('lasso_zero_columns_f64', None, None)},
+    'ridge': {False: ('lasso_ridge_solve', 'lasso_ridge_workspace_bytes', 'ridge'),
+              True: ('lasso_ridge_solve_f64', 'lasso_ridge_f64_workspace_bytes', 'ridge_f64')},
+}
+
+
 class HipEngine:
     name = "hip"
 
@@ -357,50 +374,40 @@ class HipEngine:
     # -- objective ---------------------------------------------------------------
     objective_loss_out = True      # objective_sums(..., loss_out=) exists (parallel.em_loop)
 
+    def _entry(self, op, f64):
+        """(entry point, its workspace query or None, workspace cache tag, dtype argument) of `op` for float32 / float64
+        tensors.  The dtype argument is spliced into the call: the fp32 entry points take one, the _f64 ones do not."""
+        fn, ws_fn, tag = _ENTRY[op][f64]
+        return getattr(self.lib, fn), ws_fn and getattr(self.lib, ws_fn), tag, () if f64 else (nat.LASSO_F32,)
+
     def objective_sums(self, X, Z, W, alpha, loss_out=None, max_workgroups=0):
         """-> (loss_local 0-d float tensor, sums double[2] = {sum r^2, sum |z|}) on device.
         ``loss_out``: an optional 0-d device tensor of the tensors' dtype (e.g. one slot of a loss history) the
         loss is written to directly.  float64 tensors: residual, sums and loss in double, a 0-d float64 loss
-        (lasso_objective_f64)."""
+        (lasso_objective_f64; no ``max_workgroups``)."""
         n, d = X.shape
         k = W.shape[1]
-        L = self.lib
         f64 = [t.dtype == torch.float64 for t in (X, Z, W)]
         if any(f64) and not all(f64):
             raise RuntimeError("expected X, Z, weight of one dtype")
+        f64 = all(f64)
+        fn, ws_fn, tag, dt = self._entry('objective', f64)
         with torch.cuda.device(self.device):
             sums = torch.empty(2, dtype=torch.float64, device=self.device)
-            if all(f64):
-                ws = self._ws(L.lasso_objective_f64_workspace_bytes(n, d, k), "obj")
-                if loss_out is not None and loss_out.dtype != torch.float64:
-                    raise RuntimeError("objective_sums: float64 tensors need a float64 loss_out, got %s" % loss_out.dtype)
-                loss = loss_out if loss_out is not None else torch.empty((), dtype=torch.float64, device=self.device)
-                if n == 0:      # an empty batch: nothing to launch, the reference's 0 / 0
-                    loss.fill_(float('nan'))
-                    return loss, sums.zero_()
-                nat.check(L.lasso_objective_f64(nat.ptr(X), X.stride(0), nat.ptr(W), W.stride(0), nat.ptr(Z), Z.stride(0),
-                                                n, d, k, float(alpha), nat.ptr(loss), nat.ptr(sums), nat.ptr(ws),
-                                                ws.numel(), self._stream()))
-                return loss, sums
-            ws = self._ws(L.lasso_objective_workspace_bytes(n, d, k), "obj")
-            loss = loss_out if loss_out is not None else torch.empty((), dtype=torch.float32, device=self.device)
-            nat.check(L.lasso_objective_throttled(nat.ptr(X), X.stride(0), nat.ptr(W), W.stride(0),
-                                                  nat.ptr(Z), Z.stride(0), n, d, k, nat.LASSO_F32, float(alpha),
-                                                  nat.ptr(loss), nat.ptr(sums), int(max_workgroups), nat.ptr(ws),
-                                                  ws.numel(), self._stream()))
+            ws = self._ws(ws_fn(n, d, k), tag)
+            if f64 and loss_out is not None and loss_out.dtype != torch.float64:
+                raise RuntimeError("objective_sums: float64 tensors need a float64 loss_out, got %s" % loss_out.dtype)
+            loss = loss_out if loss_out is not None else torch.empty((), dtype=torch.float64 if f64 else torch.float32,
+                                                                            device=self.device)
+            if f64 and n == 0:      # an empty batch: nothing to launch, the reference's 0 / 0
+                loss.fill_(float('nan'))
+                return loss, sums.zero_()
+            nat.check(fn(nat.ptr(X), X.stride(0), nat.ptr(W), W.stride(0), nat.ptr(Z), Z.stride(0), n, d, k, *dt,
+                         float(alpha), nat.ptr(loss), nat.ptr(sums), *(() if f64 else (int(max_workgroups),)),
+                         nat.ptr(ws), ws.numel(), self._stream()))
         return loss, sums
 
     # -- M-step --------------------------------------------------------------------
-    @staticmethod
-    def _all_f64(what, *tensors):
-        """True: every tensor is float64 (the double entry points); False: none is.  A mix raises before any launch
-        (the reference's matmul raises there too)."""
-        f64 = [t.dtype == torch.float64 for t in tensors if t is not None]
-        if any(f64) and not all(f64):
-            raise RuntimeError("%s: expected tensors of one dtype, got %s"
-                               % (what, ", ".join(str(t.dtype) for t in tensors if t is not None)))
-        return bool(f64) and all(f64)
-
     def gram(self, Z, X, out, started=None):
         """out: flat fp32 buffer of k*k + k*d (+extra) floats (float64 tensors: doubles); A and B are written at its
         start so one all-reduce covers both.  ``started``: (int32 device tensor, value) -- the product's first launch
@@ -409,28 +416,22 @@ class HipEngine:
         d = X.shape[1]
         A = out[:k * k].view(k, k)
         B = out[k * k:k * k + k * d].view(k, d)
-        if self._all_f64("gram", Z, X, out):         # float64 tensors: a double buffer, lasso_gram_accumulate_f64
+        f64 = nat.one_dtype("gram", Z, X, out)
+        if f64:
             if started is not None:
                 raise NotImplementedError("gram: float64 tensors have no start signal (one-stream EM loop only)")
             if n == 0:
                 out[:k * k + k * d].zero_()
                 return A, B
-            with torch.cuda.device(self.device):
-                ws = self._ws(self.lib.lasso_gram_f64_workspace_bytes(n, d, k), "gram_f64")
-                nat.check(self.lib.lasso_gram_accumulate_f64(nat.ptr(Z), Z.stride(0), nat.ptr(X), X.stride(0), n, d, k,
-                                                             nat.ptr(A), nat.ptr(B), nat.ptr(ws), ws.numel(),
-                                                             self._stream()))
-            return A, B
+        fn, ws_fn, tag, dt = self._entry('gram', f64)
         with torch.cuda.device(self.device):
-            ws = self._ws(self.lib.lasso_gram_workspace_bytes(n, d, k), "gram")
+            ws = self._ws(ws_fn(n, d, k), tag)
+            args = (nat.ptr(Z), Z.stride(0), nat.ptr(X), X.stride(0), n, d, k, *dt, nat.ptr(A), nat.ptr(B),
+                    nat.ptr(ws), ws.numel())
             if started is None:
-                nat.check(self.lib.lasso_gram_accumulate(nat.ptr(Z), Z.stride(0), nat.ptr(X), X.stride(0),
-                                                         n, d, k, nat.LASSO_F32, nat.ptr(A), nat.ptr(B),
-                                                         nat.ptr(ws), ws.numel(), self._stream()))
+                nat.check(fn(*args, self._stream()))
             else:
-                nat.check(self.lib.lasso_gram_accumulate_signal(nat.ptr(Z), Z.stride(0), nat.ptr(X), X.stride(0),
-                                                                n, d, k, nat.LASSO_F32, nat.ptr(A), nat.ptr(B),
-                                                                nat.ptr(ws), ws.numel(), nat.ptr(started[0]), int(started[1]),
+                nat.check(self.lib.lasso_gram_accumulate_signal(*args, nat.ptr(started[0]), int(started[1]),
                                                                 self._stream()))
         return A, B
 
@@ -438,57 +439,39 @@ class HipEngine:
         """In-place Gauss-Seidel atom sweep on D [d,k].  Returns (mask int32[k] on device,
         ndeg python int)."""
         d, k = D.shape
-        L = self.lib
-        if self._all_f64("sweep", A, B, D):          # float64 tensors: lasso_dict_sweep_f64 (deferred replacement only)
-            if pool is not None:
-                raise NotImplementedError("sweep: float64 tensors take their replacement directions through "
-                                          "fill_degenerate, not a pool")
-            with torch.cuda.device(self.device):
-                ws = self._ws(L.lasso_dict_sweep_f64_workspace_bytes(d, k), "sweep_f64")
-                mask = torch.zeros(k, dtype=torch.int32, device=self.device)
-                ndeg = C.c_int32(0)
-                nat.check(L.lasso_dict_sweep_f64(nat.ptr(A), nat.ptr(B), nat.ptr(D), D.stride(0), d, k, float(eps),
-                                                 int(bool(positive)), nat.ptr(mask), C.byref(ndeg), nat.ptr(ws),
-                                                 ws.numel(), self._stream()))
-            return mask, ndeg.value
+        f64 = nat.one_dtype("sweep", A, B, D)
+        if f64 and pool is not None:         # lasso_dict_sweep_f64: deferred replacement only
+            raise NotImplementedError("sweep: float64 tensors take their replacement directions through "
+                                      "fill_degenerate, not a pool")
+        fn, ws_fn, tag, dt = self._entry('sweep', f64)
         with torch.cuda.device(self.device):
-            ws = self._ws(L.lasso_dict_sweep_workspace_bytes(d, k), "sweep")
+            ws = self._ws(ws_fn(d, k), tag)
             mask = torch.zeros(k, dtype=torch.int32, device=self.device)
             ndeg = C.c_int32(0)
             pool_dev = pool.to(self.device).contiguous() if pool is not None else None
-            nat.check(L.lasso_dict_sweep(
-                nat.ptr(A), nat.ptr(B), nat.ptr(D), D.stride(0), d, k, nat.LASSO_F32, float(eps),
-                int(bool(positive)), nat.ptr(pool_dev),
-                pool_dev.shape[0] if pool_dev is not None else 0,
-                pool_dev.stride(0) if pool_dev is not None else 0, int(seed) & (2 ** 64 - 1),
-                nat.ptr(mask), C.byref(ndeg), nat.ptr(ws), ws.numel(), self._stream()))
+            pool_args = () if f64 else (nat.ptr(pool_dev), pool_dev.shape[0] if pool_dev is not None else 0,
+                                        pool_dev.stride(0) if pool_dev is not None else 0, int(seed) & (2 ** 64 - 1))
+            nat.check(fn(nat.ptr(A), nat.ptr(B), nat.ptr(D), D.stride(0), d, k, *dt, float(eps), int(bool(positive)),
+                         *pool_args, nat.ptr(mask), C.byref(ndeg), nat.ptr(ws), ws.numel(), self._stream()))
         return mask, ndeg.value
 
     def fill_degenerate(self, D, mask, pool, positive):
         """The i-th flagged atom of D becomes pool row i, normalised (dict_learning.py:93-96)."""
         d, k = D.shape
         pool = pool.to(self.device).contiguous()
-        if self._all_f64("fill_degenerate", D, pool):
-            with torch.cuda.device(self.device):
-                nat.check(self.lib.lasso_dict_fill_degenerate_f64(
-                    nat.ptr(D), D.stride(0), d, k, nat.ptr(mask), nat.ptr(pool), pool.shape[0], pool.stride(0),
-                    int(bool(positive)), self._stream()))
-            return
+        fn, _, _, dt = self._entry('fill_degenerate', nat.one_dtype("fill_degenerate", D, pool))
         with torch.cuda.device(self.device):
-            nat.check(self.lib.lasso_dict_fill_degenerate(
-                nat.ptr(D), D.stride(0), d, k, nat.LASSO_F32, nat.ptr(mask), nat.ptr(pool), pool.shape[0],
-                pool.stride(0), int(bool(positive)), self._stream()))
+            nat.check(fn(nat.ptr(D), D.stride(0), d, k, *dt, nat.ptr(mask), nat.ptr(pool), pool.shape[0],
+                         pool.stride(0), int(bool(positive)), self._stream()))
 
     def zero_columns(self, Z, mask):
         n, k = Z.shape
-        if Z.dtype == torch.float64:
-            if n > 0:
-                with torch.cuda.device(self.device):
-                    nat.check(self.lib.lasso_zero_columns_f64(nat.ptr(Z), Z.stride(0), n, k, nat.ptr(mask), self._stream()))
+        f64 = Z.dtype == torch.float64
+        if f64 and n == 0:
             return
+        fn, _, _, dt = self._entry('zero_columns', f64)
         with torch.cuda.device(self.device):
-            nat.check(self.lib.lasso_zero_columns(nat.ptr(Z), Z.stride(0), n, k, nat.LASSO_F32,
-                                                  nat.ptr(mask), self._stream()))
+            nat.check(fn(nat.ptr(Z), Z.stride(0), n, k, *dt, nat.ptr(mask), self._stream()))
 
     def init_transpose(self, X, W):
         """z0 = X W (sparse_encode.py:24-25) on the library's NT GEMM (fp32, or float64 tensors on the fp64-MFMA one)."""
@@ -504,42 +487,23 @@ class HipEngine:
 
     def ridge(self, A, B, lam_n, check=False):
         """V = ((A + lam_n I)^-1 B)^T  [d,k] (dict_learning.py:117-121): blocked Cholesky and
-        triangular solves of csrc/ridge.hip (lasso_ridge_solve).  `check` synchronises and raises
-        like torch.linalg.cholesky when the matrix is not positive definite.  Beyond k = 4096
-        (the kernels' limit) the k x k factorisation goes to torch.linalg on the device."""
+        triangular solves of csrc/ridge.hip (lasso_ridge_solve; float64 tensors: lasso_ridge_solve_f64, the same scheme
+        in double).  `check` synchronises and raises like torch.linalg.cholesky when the matrix is not positive
+        definite.  Beyond k = 4096 (the kernels' limit) the k x k factorisation goes to torch.linalg on the device."""
         k, d = B.shape
-        L = self.lib
-        if self._all_f64("ridge", A, B):             # float64 tensors: lasso_ridge_solve_f64, the same scheme in double
-            nbytes = L.lasso_ridge_f64_workspace_bytes(d, k)
-            if nbytes == 0:
-                M = A.clone()
-                M.diagonal().add_(lam_n)
-                return torch.cholesky_solve(B, torch.linalg.cholesky(M)).T.contiguous()
-            with torch.cuda.device(self.device):
-                ws = self._ws(nbytes, "ridge_f64")
-                V = torch.empty((d, k), dtype=torch.float64, device=self.device)
-                info = C.c_int32(0)
-                status = L.lasso_ridge_solve_f64(nat.ptr(A), nat.ptr(B), nat.ptr(V), V.stride(0), d, k, float(lam_n),
-                                                 C.byref(info) if check else None, nat.ptr(ws), ws.numel(),
-                                                 self._stream())
-                if info.value != 0:
-                    raise torch.linalg.LinAlgError(
-                        "linalg.cholesky: The factorization could not be completed because the input is not "
-                        "positive-definite (the leading minor of order %d is not positive-definite)." % info.value)
-                nat.check(status)
-            return V
-        nbytes = L.lasso_ridge_workspace_bytes(d, k)
+        f64 = nat.one_dtype("ridge", A, B)
+        fn, ws_fn, tag, dt = self._entry('ridge', f64)
+        nbytes = ws_fn(d, k)
         if nbytes == 0:
             M = A.clone()
             M.diagonal().add_(lam_n)
             return torch.cholesky_solve(B, torch.linalg.cholesky(M)).T.contiguous()
         with torch.cuda.device(self.device):
-            ws = self._ws(nbytes, "ridge")
-            V = torch.empty((d, k), dtype=torch.float32, device=self.device)
+            ws = self._ws(nbytes, tag)
+            V = torch.empty((d, k), dtype=torch.float64 if f64 else torch.float32, device=self.device)
             info = C.c_int32(0)
-            status = L.lasso_ridge_solve(nat.ptr(A), nat.ptr(B), nat.ptr(V), V.stride(0), d, k, nat.LASSO_F32,
-                                         float(lam_n), C.byref(info) if check else None, nat.ptr(ws), ws.numel(),
-                                         self._stream())
+            status = fn(nat.ptr(A), nat.ptr(B), nat.ptr(V), V.stride(0), d, k, *dt, float(lam_n),
+                        C.byref(info) if check else None, nat.ptr(ws), ws.numel(), self._stream())
             if info.value != 0:          # what torch.linalg.cholesky raises at dict_learning.py:120
                 raise torch.linalg.LinAlgError(
                     "linalg.cholesky: The factorization could not be completed because the input is not "

@@ -10,20 +10,9 @@ from ..parallel import em_loop, _em_loop_f64, constrained_mstep
 from .sparse_encode import sparse_encode
 
 
-def _engine_for(*tensors, device=None):
-    for t in tensors:
-        if t is not None and t.is_cuda:
-            return HipEngine(t.device)
-    return HipEngine(device)
-
-
-def _float64(what, *tensors):
-    """True when every tensor is float64 (the double M-step), False when none is; a mix of float64 with anything else
-    raises before any launch, as the reference's matmul would."""
-    f64 = [t.dtype == torch.float64 for t in tensors]
-    if any(f64) and not all(f64):
-        raise RuntimeError("%s: expected tensors of one dtype, got %s" % (what, ", ".join(str(t.dtype) for t in tensors)))
-    return all(f64)
+def _engine_for(*tensors):
+    nat.require_gpu()
+    return HipEngine(nat.pick_device(*tensors))
 
 
 def lasso_loss(X, Z, weight, alpha=1.0):
@@ -47,7 +36,7 @@ def update_dict(dictionary, X, Z, random_seed=None, positive=False, eps=1e-10):
     updates ``dictionary`` AND ``Z`` in place (degenerate atoms get a fresh random
     direction drawn from torch's CPU generator and their codes are zeroed) and returns
     ``dictionary``."""
-    f64 = _float64("update_dict", dictionary, X, Z)
+    f64 = nat.one_dtype("update_dict", dictionary, X, Z)
     if random_seed is not None:
         torch.manual_seed(random_seed)                               # :78-79
     eng = _engine_for(dictionary, X, Z)
@@ -67,7 +56,7 @@ def update_dict(dictionary, X, Z, random_seed=None, positive=False, eps=1e-10):
 
 def update_dict_ridge(x, z, lambd=1e-4):
     """Unconstrained M-step V = ((Z^T Z + lambd*n*I)^-1 Z^T X)^T (dict_learning.py:106-123)."""
-    f64 = _float64("update_dict_ridge", x, z)
+    f64 = nat.one_dtype("update_dict_ridge", x, z)
     eng = _engine_for(x, z)
     out_device = x.device
     xg, zg = eng.to_device(x), eng.to_device(z)
@@ -92,7 +81,7 @@ def dict_learning(X, n_components, alpha=1.0, constrained=True, persist=False,
     nat.require_gpu()
     n_samples, n_features = X.shape
     out_device = torch.device(device)
-    f64 = _float64("dict_learning", X, *([init_weight] if init_weight is not None else []))
+    f64 = nat.one_dtype("dict_learning", X, init_weight)
     if init_weight is None:
         # float64 X: the dictionary is drawn in X's dtype -- the reference's own draw whenever it can run at all
         # (its torch.empty takes the default dtype, which must then be float64)
@@ -103,8 +92,7 @@ def dict_learning(X, n_components, alpha=1.0, constrained=True, persist=False,
             weight = F.normalize(weight, dim=0)                             # :30-31
     else:
         weight = init_weight.detach().clone()
-    eng = _engine_for(X if X.is_cuda else None,
-                      device=out_device if out_device.type == 'cuda' else None)
+    eng = HipEngine(out_device if not X.is_cuda and out_device.type == 'cuda' else nat.pick_device(X))
     if f64:          # the plain one-stream loop in double (parallel._em_loop_f64)
         weight, losses = _em_loop_f64(eng, eng.to_device(X), eng.to_device(weight).clone(), alpha,
                                       constrained=constrained, persist=persist, lambd=lambd, steps=steps,

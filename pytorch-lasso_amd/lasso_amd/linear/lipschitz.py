@@ -14,7 +14,7 @@ def lipschitz_constant(weight):
     if weight.dtype not in (torch.float32, torch.float64):
         # the reference's bf16 + lr='auto' raises TypeError as well (ista.py:12)
         raise TypeError("lasso_amd: lr='auto' needs an fp32 or float64 dictionary, got %s" % weight.dtype)
-    dev = weight.device if weight.is_cuda else torch.device('cuda', torch.cuda.current_device())
+    dev = nat.pick_device(weight)
     w = weight.detach().to(dev).contiguous()
     d, k = w.shape
     L = nat.lib()

@@ -8,13 +8,6 @@ import torch
 from ... import _native as nat
 
 
-def _pick_device(*tensors):
-    for t in tensors:
-        if t is not None and t.is_cuda:
-            return t.device
-    return torch.device('cuda', torch.cuda.current_device())
-
-
 def coord_descent(x, W, z0=None, alpha=1.0, maxiter=1000, tol=1e-6, verbose=False,
                   return_info=False):
     """x [n,d], W [d,k], z0 [n,k] or None -> z [n,k] = S_alpha(b) (:52).
@@ -37,7 +30,7 @@ def coord_descent(x, W, z0=None, alpha=1.0, maxiter=1000, tol=1e-6, verbose=Fals
     if x.dtype != torch.float32 or W.dtype != torch.float32 or (z0 is not None and z0.dtype != torch.float32):
         raise NotImplementedError("lasso_amd: coord_descent is implemented for float32 tensors")
     out_device = x.device
-    dev = _pick_device(x, W, z0)
+    dev = nat.pick_device(x, W, z0)
     xg = x.detach().to(dev).contiguous()
     wg = W.detach().to(dev).contiguous()
     # the tracked z must land in the caller's z0 storage: work on it directly when it is a

@@ -12,13 +12,6 @@ _KW_DEFAULTS = dict(mu=0.1, lambda_backtrack=0.5, cont_steps=5, first_tau_factor
 _CRITERION_NAMES = ('d_nz', 'd_f', '||d_x|| / ||x||', 'LCP', 'f')
 
 
-def _pick_device(*tensors):
-    for t in tensors:
-        if t is not None and t.is_cuda:
-            return t.device
-    return torch.device('cuda', torch.cuda.current_device())
-
-
 def _f32(n):
     return (C.c_float * max(n, 1))()
 
@@ -91,7 +84,7 @@ def gpsr_basic(x, weight, tau, x0=None, stop_criterion=3, tol=1e-2, maxiter=1000
                                   "require grad (requires_grad=True) are not supported -- detach them")
     nat.require_gpu()
     out_device, out_dtype = x.device, x.dtype
-    dev = _pick_device(x, weight, x0)
+    dev = nat.pick_device(x, weight, x0)
     xg = x.detach().to(device=dev, dtype=torch.float32).contiguous()
     wg = weight.detach().to(device=dev, dtype=torch.float32).contiguous()
     if x0 is None and init == 1:

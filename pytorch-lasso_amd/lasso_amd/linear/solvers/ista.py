@@ -6,7 +6,7 @@ import torch
 
 from ... import _native as nat
 
-_DT = {torch.float32: nat.LASSO_F32, torch.bfloat16: nat.LASSO_BF16, torch.float64: nat.LASSO_F64}
+_DT = nat.DT
 # bf16 tensors (BASELINE config 3).  On the fused shapes bf16 x, W, z0 go to the native
 # bf16-MFMA kernels (csrc/bt_bf16.hip: bf16 operands, fp32 accumulation and state), with or
 # without the backtracking line search.  Everything else (fp16, larger shapes, verbose,
@@ -18,6 +18,16 @@ _UPCAST = (torch.bfloat16, torch.float16)
 
 def _to_device(t, device):
     return t if t.device == device else t.to(device)
+
+
+def _stage(x, z0, weight):
+    """-> (device, x, weight, z0) detached, contiguous and on the one HIP device the solve runs on; z0 is None for the
+    lazy_zeros sentinel (a NULL z0 = zeros, never materialised).  Tensors already there are not copied."""
+    dev = nat.pick_device(x, weight, z0)
+    xg = _to_device(x.detach(), dev).contiguous()
+    wg = _to_device(weight.detach(), dev).contiguous()
+    zg = None if _is_lazy_zeros(z0) else _to_device(z0.detach(), dev).contiguous()
+    return dev, xg, wg, zg
 
 
 def lazy_zeros(like, n, k):
@@ -202,7 +212,7 @@ def ista(x, z0, weight, alpha=1.0, fast=True, lr='auto', maxiter=10,
     """Solve min_z 0.5*||z W^T - x||^2 + alpha*||z||_1 on the GPU.
 
     x [n,d], z0 [n,k], weight [d,k] of one dtype -- float32, float64 (computed in double throughout on the
-    fp64 MFMA: _ista_f64), bfloat16 / float16 --; returns a NEW tensor z [n,k] with the
+    fp64 MFMA: lasso_fista_solve_f64), bfloat16 / float16 --; returns a NEW tensor z [n,k] with the
     dtype/device of z0 (``maxiter=0`` returns ``z0`` itself, ista.py:76,104).
     Inputs are never modified.  ``return_info`` (extension) additionally
     returns ``dict(iterations=..., last_delta=...)`` (plus ``trials`` / ``accepted_lr`` per
@@ -232,9 +242,9 @@ def ista(x, z0, weight, alpha=1.0, fast=True, lr='auto', maxiter=10,
                            % (tuple(x.shape), tuple(weight.shape), tuple(z0.shape)))
     if not (x.dtype == weight.dtype == z0.dtype):
         raise RuntimeError("expected x, weight, z0 of one dtype")
-    if x.dtype == torch.float64:
-        return _ista_f64(x, z0, weight, alpha, fast, lr, maxiter, tol, backtrack, eta_backtrack, verbose, return_info,
-                         stop_mode, kernel, begin, shard)
+    f64 = x.dtype == torch.float64
+    if f64:
+        _ista_f64(x, z0, weight, verbose, stop_mode, kernel, begin, shard)
     if x.dtype in _UPCAST:
         if lr == 'auto':
             # the reference raises here as well: `.numpy()` has no bf16 (ista.py:12)
@@ -271,19 +281,14 @@ def ista(x, z0, weight, alpha=1.0, fast=True, lr='auto', maxiter=10,
         return (z, dict(iterations=1, last_delta=0.0)) if return_info else z
 
     out_device = z0.device
-    dev = x.device if x.is_cuda else (weight.device if weight.is_cuda else
-                                      (z0.device if z0.is_cuda else torch.device('cuda', torch.cuda.current_device())))
-    xg = _to_device(x.detach(), dev).contiguous()
-    wg = _to_device(weight.detach(), dev).contiguous()
-    zg = None if _is_lazy_zeros(z0) else _to_device(z0.detach(), dev).contiguous()   # None: zeros, never materialised
+    dev, xg, wg, zg = _stage(x, z0, weight)
 
     wants_grad = torch.is_grad_enabled() and (x.requires_grad or weight.requires_grad or z0.requires_grad)
     if lr == 'auto':
-        if not wants_grad and not verbose and not backtrack and d <= 256 and k <= 1024:
+        if f64 or (not wants_grad and not verbose and not backtrack and d <= 256 and k <= 1024):
             # the fused fp32 kernels read the step from device memory: lambda_max and 1/L are
-            # computed on the stream inside lasso_fista_solve, no host round trip (ista.py:72-73)
-            if wg.dtype != torch.float32:
-                raise TypeError("lasso_amd: lr='auto' needs an fp32 dictionary, got %s" % wg.dtype)
+            # computed on the stream inside lasso_fista_solve, no host round trip (ista.py:72-73);
+            # float64 tensors: inside lasso_fista_solve_f64, for any d, k
             lr = nat.LR_AUTO
         else:
             from ..lipschitz import lipschitz_constant
@@ -326,11 +331,10 @@ def ista(x, z0, weight, alpha=1.0, fast=True, lr='auto', maxiter=10,
                          shard=shard)
 
 
-def _ista_f64(x, z0, weight, alpha, fast, lr, maxiter, tol, backtrack, eta_backtrack, verbose, return_info,
-              stop_mode, kernel, begin, shard):
-    """float64 tensors: lasso_fista_solve_f64 (csrc/gemm_f64.hip) -- the general-GEMM form of the solve on the fp64
+def _ista_f64(x, z0, weight, verbose, stop_mode, kernel, begin, shard):
+    """float64 tensors take lasso_fista_solve_f64 (csrc/gemm_f64.hip) -- the general-GEMM form of the solve on the fp64
     MFMA, every value, sum and comparison in IEEE double, for any d, k; fixed step or lr='auto', line search, stop
-    rule, z0 (or the lazy_zeros sentinel), return_info.  The fp32-only extensions are refused by name."""
+    rule, z0 (or the lazy_zeros sentinel), return_info.  The fp32-only extensions are refused here, by name."""
     if verbose:
         raise NotImplementedError("lasso_amd: verbose=True is not implemented for float64 tensors")
     if begin:
@@ -345,53 +349,6 @@ def _ista_f64(x, z0, weight, alpha, fast, lr, maxiter, tol, backtrack, eta_backt
     if torch.is_grad_enabled() and (x.requires_grad or weight.requires_grad or z0.requires_grad):
         raise NotImplementedError("lasso_amd: tensors with requires_grad=True: the differentiable path computes in "
                                   "float32; detach() float64 tensors or solve under torch.no_grad()")
-    n, d = x.shape
-    k = weight.shape[1]
-    if maxiter == 0:
-        if _is_lazy_zeros(z0):
-            z0 = z0.contiguous()
-        return (z0, dict(iterations=0, last_delta=float('nan'))) if return_info else z0
-    if n == 0:      # empty batch: nothing to solve (the reference's loop stops at once: 0 <= 0)
-        z = z0.clone()
-        return (z, dict(iterations=1, last_delta=0.0)) if return_info else z
-    out_device = z0.device
-    dev = x.device if x.is_cuda else (weight.device if weight.is_cuda else
-                                      (z0.device if z0.is_cuda else torch.device('cuda', torch.cuda.current_device())))
-    xg = _to_device(x.detach(), dev).contiguous()
-    wg = _to_device(weight.detach(), dev).contiguous()
-    zg = None if _is_lazy_zeros(z0) else _to_device(z0.detach(), dev).contiguous()     # None -> NULL z0 = zeros
-    L = nat.lib()
-    z = torch.empty((n, k), dtype=torch.float64, device=dev)
-    cap = max(int(maxiter), 1)
-    with torch.cuda.device(dev):
-        nbytes = L.lasso_fista_workspace_bytes(n, d, k, nat.LASSO_F64, int(maxiter), float(tol), _STOP[stop_mode],
-                                               int(bool(backtrack)))
-        ws = nat.workspace(dev, nbytes)
-        iters = C.c_int32(0)
-        last = C.c_double(float('nan'))
-        want_trace = bool(backtrack) and bool(return_info)
-        trials = (C.c_int32 * cap)() if want_trace else None
-        acc_lr = (C.c_double * cap)() if want_trace else None
-        acc_f = (C.c_double * cap)() if want_trace else None
-        obj = C.c_double(float('nan')) if return_info == 'objective' else None
-        nat.check(L.lasso_fista_solve_f64(
-            nat.ptr(xg), xg.stride(0), nat.ptr(wg), wg.stride(0), nat.ptr(zg), zg.stride(0) if zg is not None else 0,
-            nat.ptr(z), z.stride(0), n, d, k, float(alpha), nat.LR_AUTO if lr == 'auto' else float(lr), int(bool(fast)),
-            int(maxiter), float(tol), _STOP[stop_mode], int(bool(backtrack)), float(eta_backtrack),
-            C.byref(iters) if return_info else None, C.byref(last) if return_info else None, trials, acc_lr, acc_f,
-            C.byref(obj) if obj is not None else None, nat.ptr(ws), ws.numel(), nat.stream_ptr(dev)))
-    if z.device != out_device:
-        z = z.to(out_device)
-    if not return_info:
-        return z
-    info = dict(iterations=iters.value, last_delta=last.value)
-    if want_trace:
-        info['trials'] = list(trials[:iters.value])
-        info['accepted_lr'] = list(acc_lr[:iters.value])
-        info['accepted_f'] = list(acc_f[:iters.value])
-    if obj is not None:
-        info['objective'] = obj.value
-    return z, info
 
 
 _STOP = {'global': nat.STOP_GLOBAL, 'chunked': nat.STOP_GLOBAL_CHUNKED, 'none': nat.STOP_NONE,
@@ -408,42 +365,45 @@ _KERNEL = {'auto': nat.KERNEL_AUTO, 'tile': nat.KERNEL_TILE, 'splitk': nat.KERNE
 
 def _solve_native(x, z0, weight, alpha, fast, lr, maxiter, tol, backtrack, eta_backtrack, verbose,
                   return_info, out_device=None, stop_mode='global', kernel='auto', begin=False, shard=False):
-    """One call of lasso_fista_solve on tensors of one dtype (float32, or bfloat16 with the
-    line search)."""
+    """One call of lasso_fista_solve on tensors of one dtype (float32, or bfloat16 with the line search), or of
+    lasso_fista_solve_f64 on float64 tensors: the same arguments without the dtype, doubles in the out-arrays
+    (lasso_fista_solve(dtype=LASSO_F64) would round them to float)."""
     n, d = x.shape
     k = weight.shape[1]
     if out_device is None:
         out_device = z0.device
-    dev = x.device if x.is_cuda else (weight.device if weight.is_cuda else
-                                      (z0.device if z0.is_cuda else torch.device('cuda', torch.cuda.current_device())))
-    xg = _to_device(x.detach(), dev).contiguous()
-    wg = _to_device(weight.detach(), dev).contiguous()
-    zg = None if _is_lazy_zeros(z0) else _to_device(z0.detach(), dev).contiguous()     # None -> NULL z0 = zeros
+    dev, xg, wg, zg = _stage(x, z0, weight)
     L = nat.lib()
+    f64 = x.dtype == torch.float64
+    solve, real, dtype_arg = (L.lasso_fista_solve_f64, C.c_double, ()) if f64 else \
+        (L.lasso_fista_solve, C.c_float, (_DT[x.dtype],))
     z = torch.empty((n, k), dtype=x.dtype, device=dev)
     with torch.cuda.device(dev):
         nbytes = L.lasso_fista_workspace_bytes(n, d, k, _DT[x.dtype], int(maxiter), float(tol),
-                                               nat.STOP_GLOBAL, int(bool(backtrack)))
+                                               _STOP[stop_mode] if f64 else nat.STOP_GLOBAL, int(bool(backtrack)))
         ws = nat.workspace(dev, nbytes)
         want_async = bool(begin) and not backtrack and x.dtype == torch.float32
         iters = C.c_int32(0)
-        last = C.c_float(float('nan'))
+        last = real(float('nan'))
         want_host = bool(return_info) or bool(verbose)
         # asynchronous solves: the verdict kernel writes its four words straight into pinned host memory
         # (LASSO_SOLVE_STATUS_MAPPED) -- no copy launch behind it on the EM step's dependent chain
         status = _pinned_status(dev) if want_async and not shard else None
         want_trace = bool(backtrack) and bool(return_info)
         trials = (C.c_int32 * max(int(maxiter), 1))() if want_trace else None
-        acc_lr = (C.c_float * max(int(maxiter), 1))() if want_trace else None
-        acc_f = (C.c_float * max(int(maxiter), 1))() if (want_trace or (verbose and backtrack)) else None
-        obj = C.c_float(float('nan')) if return_info == 'objective' else None
-        st = L.lasso_fista_solve(
+        acc_lr = (real * max(int(maxiter), 1))() if want_trace else None
+        acc_f = (real * max(int(maxiter), 1))() if (want_trace or (verbose and backtrack)) else None
+        obj = real(float('nan')) if return_info == 'objective' else None
+        flags = _STOP[stop_mode]             # (float64 tensors: the stop rule alone, ista() refused everything else)
+        if not f64:
+            flags |= (_KERNEL[kernel] | (nat.SOLVE_ASYNC if want_async else 0) | (nat.SOLVE_SHARDED if shard else 0) |
+                      (nat.SOLVE_STATUS_MAPPED if status is not None else 0) |
+                      (nat.SOLVE_DEFER_VERDICT if (begin == 'defer' and status is not None and stop_mode == 'one-chunk')
+                       else 0))
+        st = solve(
             nat.ptr(xg), xg.stride(0), nat.ptr(wg), wg.stride(0), nat.ptr(zg), zg.stride(0) if zg is not None else 0,
-            nat.ptr(z), z.stride(0), n, d, k, _DT[x.dtype], float(alpha), lr, int(bool(fast)),
-            int(maxiter), float(tol), _STOP[stop_mode] | _KERNEL[kernel] | (nat.SOLVE_ASYNC if want_async else 0) |
-            (nat.SOLVE_SHARDED if shard else 0) | (nat.SOLVE_STATUS_MAPPED if status is not None else 0) |
-            (nat.SOLVE_DEFER_VERDICT if (begin == 'defer' and status is not None and stop_mode == 'one-chunk') else 0),
-            int(bool(backtrack)), float(eta_backtrack),
+            nat.ptr(z), z.stride(0), n, d, k, *dtype_arg, float(alpha), lr, int(bool(fast)),
+            int(maxiter), float(tol), flags, int(bool(backtrack)), float(eta_backtrack),
             C.cast(status.arm(), C.POINTER(C.c_int32)) if status is not None else
             (C.byref(iters) if want_host else None), C.byref(last) if want_host else None, trials, acc_lr, acc_f,
             C.byref(obj) if obj is not None else None, nat.ptr(ws), ws.numel(), nat.stream_ptr(dev))

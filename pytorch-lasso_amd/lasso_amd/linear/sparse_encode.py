@@ -12,7 +12,7 @@ def _engine_for(x, weight):
     from ..engine import HipEngine
     from .. import _native as nat
     nat.require_gpu()
-    return HipEngine(x.device if x.is_cuda else (weight.device if weight.is_cuda else None))
+    return HipEngine(nat.pick_device(x, weight))
 
 
 def _native_ok(x, weight):

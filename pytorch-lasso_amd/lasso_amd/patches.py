@@ -27,7 +27,7 @@ def extract_patches(images, patch_size, stride=1, center=True):
     N, C, H, W = images.shape
     if ph > H or pw > W:
         raise ValueError("patch larger than the image")
-    dev = images.device if images.is_cuda else torch.device('cuda', torch.cuda.current_device())
+    dev = nat.pick_device(images)
     img = images.detach().to(dev).contiguous()
     M = N * ((H - ph) // sh + 1) * ((W - pw) // sw + 1)
     X = torch.empty((M, C * ph * pw), dtype=torch.float32, device=dev)
@@ -49,7 +49,7 @@ def reconstruct_from_patches(patches, image_shape, patch_size, stride=1, means=N
     M = N * ((H - ph) // sh + 1) * ((W - pw) // sw + 1)
     if patches.dim() != 2 or patches.shape != (M, C * ph * pw) or patches.dtype != torch.float32:
         raise ValueError("patches must be float32 [%d, %d]" % (M, C * ph * pw))
-    dev = patches.device if patches.is_cuda else torch.device('cuda', torch.cuda.current_device())
+    dev = nat.pick_device(patches)
     P = patches.detach().to(dev).contiguous()
     mu = means.detach().to(dev).contiguous() if means is not None else None
     out = torch.empty((N, C, H, W), dtype=torch.float32, device=dev)
