@@ -375,15 +375,13 @@ int solve(const double* x, int64_t ldx, const double* w, int64_t ldw, const doub
   const double budget = (double)n * (double)k * tol;                       // z0.numel() * tol (ista.py:64)
   const double lam = alpha * lr;
   const int64_t parts = prox_parts(n, k);
-  double t_mom = 1.0;
+  Momentum64 mom;
   auto iterate = [&](double* delta_slot) -> int {
-    const double t_next = (1.0 + sqrt(1.0 + 4.0 * t_mom * t_mom)) / 2.0;    // :99
-    const double coef = fast ? (t_mom - 1.0) / t_next : 0.0;
+    const double coef = mom.next(fast);                                     // :98-99
     // NR = x - y W^T (= -r);  the gradient r W = -(NR W) stays in the second product's accumulators
     LASSO_HIP_TRY(gemm_sub(ws.Y, k, w, ldw, x, ldx, ws.NR, d, (int)n, (int)d, (int)k, st));
     GemmArgs g{ws.NR, d, w, ldw, nullptr, 0, zout, ldz, ws.Y, k, lr, lam, coef, ws.dpart, (int)n, (int)k, (int)d};
     LASSO_HIP_TRY((launch_gemm<EPI_PROX, true>(g, st)));
-    t_mom = t_next;
     if (delta_slot) {
       hipLaunchKernelGGL(reduce_sets_kernel, dim3(1), dim3(256), 0, st, ws.dpart, parts, delta_slot);
       LASSO_HIP_TRY(hipGetLastError());
@@ -401,7 +399,7 @@ int solve(const double* x, int64_t ldx, const double* w, int64_t ldw, const doub
     int chunk = 1;
     while (it < maxiter) {
       const int c = std::min(chunk, maxiter - it);
-      const double t_head = t_mom;
+      const Momentum64 head = mom;
       if (c > 1) {
         LASSO_HIP_TRY(hipMemcpy2DAsync(ws.G, k * 8, zout, ldz * 8, k * 8, n, hipMemcpyDeviceToDevice, st));
         LASSO_HIP_TRY(hipMemcpyAsync(ws.Yc, ws.Y, (size_t)n * k * 8, hipMemcpyDeviceToDevice, st));
@@ -424,7 +422,7 @@ int solve(const double* x, int64_t ldx, const double* w, int64_t ldw, const doub
       if (hit < c - 1) {
         LASSO_HIP_TRY(hipMemcpy2DAsync(zout, ldz * 8, ws.G, k * 8, k * 8, n, hipMemcpyDeviceToDevice, st));
         LASSO_HIP_TRY(hipMemcpyAsync(ws.Y, ws.Yc, (size_t)n * k * 8, hipMemcpyDeviceToDevice, st));
-        t_mom = t_head;
+        mom = head;
         for (int j = 0; j <= hit; ++j)
           if (int s = iterate(nullptr)) return s;
       }
@@ -453,11 +451,11 @@ int solve_backtracking(const double* x, int64_t ldx, const double* w, int64_t ld
   if (int s = start_state(z0, ldz0, zout, ldz, ws.Y, n, k, st)) return s;
   const double budget = (double)n * (double)k * tol;
   bool warned = false;
-  double t_mom = 1.0, last = NAN;
+  Momentum64 mom;
+  double last = NAN;
   int it = 0;
   for (; it < maxiter; ++it) {
-    const double t_next = (1.0 + sqrt(1.0 + 4.0 * t_mom * t_mom)) / 2.0;             // :98
-    const double coef = fast ? (t_mom - 1.0) / t_next : 0.0;                          // :99 (ISTA: y == z)
+    const double coef = mom.next(fast);                                               // :98-99 (ISTA: y == z)
     // NR = x - p W^T (= -r0, :22);  G = r0 W (:24);  part[0 ..) = sum r0^2 (:23)
     LASSO_HIP_TRY(gemm_sub(ws.Y, k, w, ldw, x, ldx, ws.NR, d, (int)n, (int)d, (int)k, st));
     {
@@ -465,11 +463,12 @@ int solve_backtracking(const double* x, int64_t ldx, const double* w, int64_t ld
       LASSO_HIP_TRY((launch_gemm<EPI_SUB, true>(g, st)));
     }
     hipLaunchKernelGGL(sumsq_kernel, dim3(kGrid), dim3(256), 0, st, ws.NR, n * d, ws.part);
-    double lr = lr0, f_acc = NAN, lr_acc = lr0;
+    StepLadder ladder{lr0, eta, alpha};
+    double f_acc = NAN, lr_acc = lr0;
     int t = 0, trials = 0;
     for (;;) {
       const bool give_up = t >= kMaxTrials;
-      const double lr_t = give_up ? lr0 : lr;                                           // :48-52
+      const double lr_t = give_up ? lr0 : ladder.lr;                                    // :48-52
       hipLaunchKernelGGL(trial_kernel, dim3(kGrid), dim3(256), 0, st, ws.Y, ws.G, ws.C, n * k, lr_t, alpha * lr_t,
                          ws.part + 2 * kGrid);                                          // :40, :31-35
       LASSO_HIP_TRY(hipGetLastError());
@@ -480,16 +479,14 @@ int solve_backtracking(const double* x, int64_t ldx, const double* w, int64_t ld
       double hs[5];                                     // {sum r0^2, sum r1^2, sum |z1|, sum dz g, sum dz^2}
       LASSO_HIP_TRY(hipMemcpyAsync(hs, ws.sums, sizeof(hs), hipMemcpyDeviceToHost, st));
       LASSO_HIP_TRY(hipStreamSynchronize(st));
-      const double f0 = 0.5 * hs[0];                                                    // :23
-      const double F = 0.5 * hs[1] + alpha * hs[2];                                     // :28
-      const double Q = f0 + hs[3] + (0.5 / lr_t) * hs[4] + alpha * hs[2];               // :32-35
+      const LineSearchVerdict<double> v = line_search_verdict<double>(hs, alpha, lr_t, give_up);   // :23, :28, :32-35
       if (give_up) warned = true;
-      if (give_up || F <= Q) {                                                          // :45
+      if (v.accepted) {                                                                 // :45
         trials = give_up ? kMaxTrials : t + 1;
-        f_acc = F; lr_acc = lr_t;
+        f_acc = v.F; lr_acc = lr_t;
         break;
       }
-      lr = lr / eta;                                                                    // :47
+      ladder.descend();                                                                 // :47
       ++t;
     }
     hipLaunchKernelGGL(finish_kernel, dim3(kGrid), dim3(256), 0, st, zout, ldz, ws.Y, ws.C, n, k, coef, ws.dpart);
@@ -500,7 +497,6 @@ int solve_backtracking(const double* x, int64_t ldx, const double* w, int64_t ld
     if (trials_out) trials_out[it] = trials;
     if (accepted_lr_out) accepted_lr_out[it] = lr_acc;
     if (accepted_f_out) accepted_f_out[it] = f_acc;
-    t_mom = t_next;
     if (tol > 0.0 && last <= budget) { ++it; break; }                                   // :93-95
   }
   if (iters_out) *iters_out = it;

@@ -139,13 +139,9 @@ __global__ void momentum_table_kernel(float* __restrict__ coef, float* __restric
 static const CoefHead& coef_head() {
   static const CoefHead head = [] {
     CoefHead h;
-    double t = 1.0;
-    for (int i = 0; i < kCoefHead; ++i) {
-      const double tn = (1.0 + sqrt(1.0 + 4.0 * (t * t))) / 2.0;
-      h.v[i] = (float)((t - 1.0) / tn);
-      t = tn;
-    }
-    h.t_next = t;
+    Momentum mom;
+    for (int i = 0; i < kCoefHead; ++i) h.v[i] = mom.next(true);
+    h.t_next = mom.t;
     return h;
   }();
   return head;
@@ -783,347 +779,352 @@ int solve_bf16_persistent(const void* x_dev, int64_t ldx, const void* w_dev, int
   return hout[3] ? fail(LASSO_WARN_LINESEARCH, "backtracking line search failed; reverted to lr0") : LASSO_OK;
 }
 
+// The start of a solve (ista.py:76-78): z = z0 in zout -- left alone where z0 IS zout, zeros without a z0 -- and then
+// y = z in Y (nullable: the caller has no y, or fills it from elsewhere).
+int seed_state(const float* z0, int64_t ldz0, float* zout, int64_t ldz, float* Y, int64_t n, int64_t k, hipStream_t st) {
+  if (!z0) LASSO_HIP_TRY(hipMemset2DAsync(zout, ldz * 4, 0, k * 4, n, st));
+  else if (z0 != zout) LASSO_HIP_TRY(hipMemcpy2DAsync(zout, ldz * 4, z0, ldz0 * 4, k * 4, n, hipMemcpyDeviceToDevice, st));
+  if (Y) LASSO_HIP_TRY(hipMemcpy2DAsync(Y, k * 4, zout, ldz * 4, k * 4, n, hipMemcpyDeviceToDevice, st));
+  return LASSO_OK;
+}
+
+struct BtTrace {             // the caller's per-iteration trace of a line search (each array nullable)
+  int32_t* trials; float* lr; float* f;
+  void record(int it, int ntrials, float lr_acc, float f_acc) const {
+    if (trials) trials[it] = ntrials;      // trials evaluated up to the accepted one
+    if (lr) lr[it] = lr_acc;               // the step the iteration used (ista.py:40,52)
+    if (f) f[it] = f_acc;                  // F(z_next) of the accepted trial (:28)
+  }
+};
+// The words bt_decide_kernel leaves in flags / fvals, decided on the host instead: a row shard, whose sums the caller's
+// callback has added over the ranks -- same float arithmetic (line_search_verdict<float>), same outcome on every rank.
+struct HostDecision {
+  int flags[4] = {0, 0, 0, 0}; float fvals[4] = {0.f, 0.f, 0.f, 0.f};
+  void take(const double* sums, double alpha, double lr_t, int idx, bool force) {
+    const LineSearchVerdict<float> v = line_search_verdict<float>(sums, alpha, lr_t, force);
+    fvals[0] = v.F; fvals[1] = v.Q; flags[1] = idx + 1;
+    if (v.accepted) { flags[0] = 1; flags[2] = idx; fvals[2] = (float)lr_t; fvals[3] = (float)(alpha * lr_t); }
+  }
+  int upload(int* flags_dev, float* fvals_dev, hipStream_t st) const {
+    LASSO_HIP_TRY(hipMemcpyAsync(flags_dev, flags, sizeof(flags), hipMemcpyHostToDevice, st));
+    LASSO_HIP_TRY(hipMemcpyAsync(fvals_dev, fvals, sizeof(fvals), hipMemcpyHostToDevice, st));
+    LASSO_HIP_TRY(hipStreamSynchronize(st));     // (the words live on the caller's stack frame)
+    return LASSO_OK;
+  }
+};
+
+// The three ways solve_backtracking runs a solve:
+//   Fused        fp32 tensors, one process, flat 16-byte-aligned state: one bt_iter launch per iteration, in windows;
+//   MultiLaunch  one process, flat state otherwise (bf16 tensors, k no multiple of 4, the A/B knobs bt_hint & 1: one trial
+//                per launch, bt_hint & 2: round 4's form): gradient, trials and accept as separate launches, in windows;
+//   Sync         a row shard (the decisions need the other ranks' sums) or a strided z_out: iteration by iteration, the
+//                host reads every decision.  Also the one iteration of a window whose search ran out of trials.
+enum class BtForm { Fused, MultiLaunch, Sync };
+enum class BtWindowEnd { RanThrough = 0, StopRule = 1, OutOfTrials = 2 };   // ctl[0] of the kernels that close an iteration
+constexpr int kBtWindow = 16;
+constexpr int kBtFirst = 5;          // trials of the first multi-trial launch of an iteration
+
+struct BtSolve {
+  // geometry and constants of the solve
+  BtWorkspace ws;
+  BtParams p;                // P / ldp: the point, y (fast) or z itself
+  bool half;                 // bf16 tensors: bt_bf16.hip kernels, 64-row tiles, state in ws.Zf
+  bool multi_trials;         // MultiLaunch: the trials of a batch as bt_trials_kernel launches (fp32, flat aligned state)
+  bool recompute;            // candidates stay on chip, the finish kernel recomputes the accepted one
+  bool zero_in_kernel;       // Fused with an all-zero start: the first launch writes the zeros of z and y itself
+  int kp, grid, fast, maxiter;
+  float* zout; int64_t ldz, nk;
+  double alpha, lr0, eta;
+  float stop_budget;         // n k tol (ista.py:64, over all ranks), -1 without the stop rule: no sum |dz| >= 0 is below it
+  BtTrace trace; lasso_allreduce_fn reduce; void* reduce_ctx; hipStream_t st;
+  // running state
+  int it = 0, prev_trials = kBtBatch - 1;
+  Momentum mom;              // ista.py:78
+  float last = NAN; bool warned = false;
+};
+
+// One trial of a search at step lr_t (bf16 tensors: the trial and its decision are two launches).
+int launch_trial(const BtSolve& c, const BtParams& p, double lr_t, int idx, int force, double* sums_dev) {
+  if (c.half) LASSO_HIP_TRY(launch_bt16_trial(p, c.kp, c.grid, (float)lr_t, (float)(c.alpha * lr_t), force, c.st));
+  LASSO_HIP_TRY(c.half ? launch_bt_decide(p, c.alpha, lr_t, idx, force, c.st, sums_dev)
+                       : launch_bt_trial(p, c.kp, c.grid, c.alpha, lr_t, idx, force, c.st, sums_dev));
+  return LASSO_OK;
+}
+
+// The end of a window: its control words -- and, `hrec` given, the fused form's per-iteration records, a second small
+// copy -- with ONE wait.  Says how the window ended and moves c.it (StopRule: the iteration the rule fired at, :93-95),
+// c.last and c.mom over the iterations it completed.
+int window_wait(BtSolve& c, int win0, int wlen, float* hrec, BtWindowEnd* end) {
+  int hctl[4] = {0, 0, 0, 0};
+  LASSO_HIP_TRY(hipMemcpyAsync(hctl, c.ws.ctl, sizeof(hctl), hipMemcpyDeviceToHost, c.st));
+  if (hrec) LASSO_HIP_TRY(hipMemcpyAsync(hrec, c.ws.rrec + 4 * (size_t)win0, (size_t)wlen * 16, hipMemcpyDeviceToHost, c.st));
+  LASSO_HIP_TRY(hipStreamSynchronize(c.st));
+  *end = (BtWindowEnd)hctl[0];
+  c.it = hctl[1] > 0 ? hctl[1] : win0;      // (ctl[1] = iterations completed, absolute; 0: none in this window)
+  if (c.it > win0) memcpy(&c.last, &hctl[2], sizeof(float));
+  c.mom.skip(c.it - win0);
+  return LASSO_OK;
+}
+
+// The whole solve is enqueued WITHOUT a host wait, in WINDOWS of kBtWindow outer iterations (all `maxiter`
+// iterations at once meant ~19 launches per remaining iteration of empty work after the rule fired -- maxiter = 1000
+// stopping at 20: ~19k no-op launches): once the stop rule fired on the device -- or a search needed more trials than
+// were enqueued -- the window's remaining launches are no-ops (*skip != 0).  The control words are read between windows;
+// a search that ran out of trials takes ONE iteration_sync from the untouched state of the iteration that needed them.
+// Round 5, fp32 tensors: ONE launch per outer iteration (bt_iter.hip: the accept step of the previous iteration, the
+// gradient and the first `n_first` trials per tile) + ONE decision launch that also closes the previous iteration;
+// decisions live in per-iteration slots of ws.flags / ws.fvals (kBtWindow slots of 4 words).  The trials beyond
+// n_first (old kernel, p and g re-read) are enqueued only after a search of THIS solve has run out of trials once
+// (`safety`); until then such a search costs one synchronous iteration.
+int window_fused(BtSolve& c, int& n_first_next, bool& safety, BtWindowEnd* end) {
+  const BtWorkspace& ws = c.ws; hipStream_t st = c.st;
+  const int win0 = c.it, wlen = std::min(kBtWindow, c.maxiter - c.it), n_first = n_first_next, ntiles = c.p.ntiles;
+  LASSO_HIP_TRY(hipMemsetAsync(ws.flags, 0, (size_t)kBtWindow * 4 * sizeof(int), st));
+  LASSO_HIP_TRY(hipMemsetAsync(ws.ctl, 0, 4 * sizeof(int), st));
+  BtIterParams q;
+  q.X = c.p.X; q.ldx = c.p.ldx; q.Wp = ws.wp; q.Wtp = ws.wtp; q.Z = c.zout; q.Y = ws.Y; q.G = ws.G;
+  q.partials = ws.partials; q.partsM = ws.partsM; q.dpart = ws.dtile; q.skip = ws.ctl;
+  q.n = c.p.n; q.d = c.p.d; q.k = c.p.k; q.ntiles = ntiles; q.fast = c.fast ? 1 : 0;
+  q.zero_start = (c.zero_in_kernel && c.it == 0) ? 1 : 0;
+  const float stop_budget = c.stop_budget;
+  Momentum mom = c.mom;
+  float coef_prev = 0.0f;
+  BtSteps steps;
+  for (int i = win0; i < win0 + wlen; ++i) {
+    const float coef = mom.next(c.fast);                                             // :98-99
+    const int slot = i - win0;
+    int* const cur_flags = ws.flags + 4 * slot;
+    float* const cur_fvals = ws.fvals + 4 * slot;
+    const int* const prev_flags = slot > 0 ? ws.flags + 4 * (slot - 1) : nullptr;
+    const float* const prev_fvals = slot > 0 ? ws.fvals + 4 * (slot - 1) : nullptr;
+    StepLadder ladder{c.lr0, c.eta, c.alpha};
+    ladder.fill(steps, n_first);                                                     // :47
+    q.acc_flags = prev_flags; q.acc_fvals = prev_fvals; q.coef = coef_prev; q.tail = 0; q.ntrials = n_first;
+    LASSO_HIP_TRY(launch_bt_iter(q, steps, c.kp, c.grid, st));
+    const bool more = safety && n_first < kBtBatch;
+    LASSO_HIP_TRY(launch_bt_iter_decide(ws.partials, ws.partsM, ntiles, c.alpha, steps, n_first, 0, more ? 0 : 1, cur_flags,
+                                        cur_fvals, prev_flags, prev_fvals, ws.dtile, i - 1, stop_budget, ws.ctl,
+                                        ws.rrec, st));
+    if (more) {
+      BtSteps rest;
+      const int nb = kBtBatch - n_first;
+      ladder.fill(rest, nb);
+      BtParams pb = c.p;
+      pb.flags = cur_flags; pb.fvals = cur_fvals; pb.skip = ws.ctl;
+      LASSO_HIP_TRY(launch_bt_trials_only(pb, c.kp, c.grid, rest, nb, ws.partsM, st));
+      LASSO_HIP_TRY(launch_bt_iter_decide(ws.partials, ws.partsM, ntiles, c.alpha, rest, nb, n_first, 1, cur_flags,
+                                          cur_fvals, nullptr, nullptr, nullptr, 0, -1.0f, ws.ctl, ws.rrec, st));
+    }
+    coef_prev = coef;
+  }
+  {   // the accept step of the window's last iteration, and its record
+    const int slot = wlen - 1;
+    q.acc_flags = ws.flags + 4 * slot; q.acc_fvals = ws.fvals + 4 * slot; q.coef = coef_prev; q.tail = 1; q.ntrials = 0;
+    LASSO_HIP_TRY(launch_bt_iter(q, steps, c.kp, c.grid, st));
+    LASSO_HIP_TRY(launch_bt_iter_decide(ws.partials, ws.partsM, ntiles, c.alpha, steps, 0, 0, 0, nullptr, nullptr,
+                                        ws.flags + 4 * slot, ws.fvals + 4 * slot, ws.dtile, win0 + wlen - 1,
+                                        stop_budget, ws.ctl, ws.rrec, st));
+  }
+  float hrec[kBtWindow * 4];
+  if (int s = window_wait(c, win0, wlen, hrec, end)) return s;
+  if (c.it > win0) {
+    int most = 1;
+    for (int i = 0; i < c.it - win0; ++i) {
+      int tr;
+      memcpy(&tr, &hrec[4 * i], sizeof(int));
+      c.trace.record(win0 + i, tr, hrec[4 * i + 1], hrec[4 * i + 2]);
+      most = std::max(most, tr);
+      c.prev_trials = tr;
+    }
+    // the next window computes as many trials per tile as this one's longest search took (every computed trial costs
+    // its GEMM whether it is needed or not; a search that outgrows the guess costs one synchronous iteration)
+    n_first_next = std::min(kBtBatch, std::max(2, most));
+    // a whole window without a search beyond its first batch: the second trial batch and its decision leave the
+    // windows again (two launches per iteration that did nothing; ADVICE r05: `safety` was never cleared)
+    if (*end != BtWindowEnd::OutOfTrials && most <= n_first) safety = false;
+  }
+  if (*end == BtWindowEnd::OutOfTrials) safety = true;
+  return LASSO_OK;
+}
+
+// A window of the multi-launch form (see window_fused for the windows): every outer iteration is the gradient,
+// kBtBatch trial launches with the step sequence lr0 / eta^t (a trial behind the accepted one returns at once), the
+// accept step and a one-block kernel that keeps the iteration's record and evaluates the stop rule on the device.
+int window_multi_launch(BtSolve& c, BtWindowEnd* end) {
+  const BtWorkspace& ws = c.ws; hipStream_t st = c.st;
+  const int win0 = c.it, wlen = std::min(kBtWindow, c.maxiter - c.it);
+  LASSO_HIP_TRY(hipMemsetAsync(ws.flags, 0, 4 * sizeof(int), st));
+  LASSO_HIP_TRY(hipMemsetAsync(ws.ctl, 0, 4 * sizeof(int), st));
+  BtParams p = c.p;
+  p.skip = ws.ctl;
+  Momentum mom = c.mom;
+  for (int i = win0; i < win0 + wlen; ++i) {
+    const float coef = mom.next(c.fast);                                             // :98-99
+    LASSO_HIP_TRY(c.half ? launch_bt16_grad(p, c.kp, c.grid, st) : launch_bt_grad(p, c.kp, c.grid, st));
+    StepLadder ladder{c.lr0, c.eta, c.alpha};
+    if (c.multi_trials) {
+      // fp32 tensors: the kBtBatch pre-enqueued trials as TWO launches -- trials 0 .. kBtFirst-1 (p and g of a tile
+      // read once, in registers for all of them) and the rest (a no-op once a trial of the first launch passed)
+      for (int b0 = 0; b0 < kBtBatch; b0 += kBtFirst) {
+        BtSteps steps;
+        const int nb = std::min(kBtFirst, kBtBatch - b0);
+        ladder.fill(steps, nb);                                                      // :47
+        LASSO_HIP_TRY(launch_bt_trials(p, c.kp, c.grid, c.alpha, steps, nb, b0, ws.partsM, st));
+      }
+    } else {
+      for (int b = 0; b < kBtBatch; ++b, ladder.descend())                           // :47
+        if (int s = launch_trial(c, p, ladder.lr, b, 0, nullptr)) return s;
+    }
+    LASSO_HIP_TRY(launch_bt_finish_recompute(c.zout, ws.Y, p.P, ws.G, c.nk, coef, ws.flags, ws.fvals, ws.dpart,
+                                             kBtFinishGrid, st, ws.ctl));
+    LASSO_HIP_TRY(launch_bt_iter_end(ws.dpart, kBtFinishGrid, ws.flags, ws.fvals, ws.ctl, i, c.stop_budget, ws.rtrials,
+                                     ws.rlrs, ws.rfs, st));
+  }
+  if (int s = window_wait(c, win0, wlen, nullptr, end)) return s;
+  if (c.it > win0) {
+    const int cnt = c.it - win0;
+    std::vector<int> ht(cnt);
+    std::vector<float> hl(cnt), hf(cnt);
+    LASSO_HIP_TRY(hipMemcpy(ht.data(), ws.rtrials + win0, (size_t)cnt * 4, hipMemcpyDeviceToHost));
+    LASSO_HIP_TRY(hipMemcpy(hl.data(), ws.rlrs + win0, (size_t)cnt * 4, hipMemcpyDeviceToHost));
+    LASSO_HIP_TRY(hipMemcpy(hf.data(), ws.rfs + win0, (size_t)cnt * 4, hipMemcpyDeviceToHost));
+    for (int i = 0; i < cnt; ++i) c.trace.record(win0 + i, ht[i], hl[i], hf[i]);
+    c.prev_trials = ht[cnt - 1];
+  }
+  return LASSO_OK;
+}
+
+// One outer iteration with the host in the loop: the trials are enqueued in batches and the host reads the decision
+// behind each batch.  On a row shard (c.reduce) the sums behind the two global decisions of an iteration -- F <= Q of
+// every trial (ista.py:23,28,32-35) and sum |z_next - z| <= n k tol (:93) -- are added over the ranks by the caller's
+// callback; every rank then takes the same decision from the same numbers.  *stop: the stop rule fired (:93-95).
+int iteration_sync(BtSolve& c, bool* stop) {
+  const BtWorkspace& ws = c.ws; const BtParams& p = c.p; hipStream_t st = c.st;
+  const float coef = c.mom.next(c.fast);                                             // :98-99
+  LASSO_HIP_TRY(hipMemsetAsync(ws.flags, 0, 4 * sizeof(int), st));
+  LASSO_HIP_TRY(c.half ? launch_bt16_grad(p, c.kp, c.grid, st) : launch_bt_grad(p, c.kp, c.grid, st));
+  StepLadder ladder{c.lr0, c.eta, c.alpha};
+  struct { int flags[4]; float fvals[4]; float delta; } host = {{0, 0, 0, 0}, {0.f, 0.f, 0.f, 0.f}, 0.f};
+  int t = 0; bool accepted = false;
+  while (!accepted) {
+    const bool give_up = t >= kBtMaxTrials;
+    // the first batch of an iteration is sized from the previous iteration's trial count
+    // (trials enqueued after the accepted one only cost their launch, but that adds up)
+    const int want = t == 0 ? std::min(kBtBatch, std::max(2, c.prev_trials + 1)) : kBtBatch / 2;
+    const int batch = give_up ? 1 : std::min(want, kBtMaxTrials - t), force = give_up ? 1 : 0;
+    double lr_batch[kBtBatch];
+    for (int b = 0; b < batch; ++b) {
+      const double lr_t = give_up ? c.lr0 : ladder.lr;      // ista.py:48-52: warn and revert to the initial step size
+      lr_batch[b] = lr_t;
+      if (int s = launch_trial(c, p, lr_t, t + b, force, c.reduce ? ws.sums + 5 * b : nullptr)) return s;
+      if (give_up) c.warned = true;
+      else ladder.descend();                                                         // :47
+    }
+    if (c.reduce) {
+      // the batch's sums: all ranks add theirs, then the decision of bt_decide_kernel on the host, trial by trial in order
+      double hsums[kBtBatch * 5];
+      LASSO_HIP_TRY(hipMemcpyAsync(hsums, ws.sums, (size_t)batch * 5 * sizeof(double), hipMemcpyDeviceToHost, st));
+      LASSO_HIP_TRY(hipStreamSynchronize(st));
+      if (c.reduce(c.reduce_ctx, hsums, batch * 5) != 0) return fail(LASSO_ERR_HIP, "all-reduce callback failed");
+      HostDecision dec;
+      for (int b = 0; b < batch && !dec.flags[0]; ++b) dec.take(hsums + 5 * b, c.alpha, lr_batch[b], t + b, give_up);
+      if (int s = dec.upload(ws.flags, ws.fvals, st)) return s;
+    }
+    t += batch;
+    if (c.recompute)   // P is Y (fast) or Z itself: element-wise in place is safe either way
+      LASSO_HIP_TRY(launch_bt_finish_recompute(c.zout, ws.Y, p.P, ws.G, c.nk, coef, ws.flags, ws.fvals, ws.dpart,
+                                               kBtFinishGrid, st));
+    else
+      LASSO_HIP_TRY(launch_bt_finish(c.zout, c.ldz, ws.Y, ws.C, p.n, p.k, coef, ws.flags, ws.dpart, kBtFinishGrid, st));
+    hipLaunchKernelGGL(reduce_partials_kernel, dim3(1), dim3(256), 0, st, ws.dpart, kBtFinishGrid, ws.delta);
+    LASSO_HIP_TRY(hipGetLastError());
+    LASSO_HIP_TRY(hipMemcpyAsync(host.flags, ws.flags, 4 * sizeof(int), hipMemcpyDeviceToHost, st));
+    LASSO_HIP_TRY(hipMemcpyAsync(&host.delta, ws.delta, sizeof(float), hipMemcpyDeviceToHost, st));
+    if (c.trace.lr || c.trace.f)
+      LASSO_HIP_TRY(hipMemcpyAsync(host.fvals, ws.fvals, 4 * sizeof(float), hipMemcpyDeviceToHost, st));
+    LASSO_HIP_TRY(hipStreamSynchronize(st));
+    accepted = host.flags[0] != 0;
+  }
+  if (c.reduce) {                                    // sum |z_next - z| over all ranks (:93)
+    double dsum = (double)host.delta;
+    if (c.reduce(c.reduce_ctx, &dsum, 1) != 0) return fail(LASSO_ERR_HIP, "all-reduce callback failed");
+    host.delta = (float)dsum;
+  }
+  c.prev_trials = host.flags[2] + 1;
+  c.trace.record(c.it, host.flags[2] + 1, host.fvals[2], host.fvals[0]);
+  c.last = host.delta;
+  ++c.it;
+  *stop = host.delta <= c.stop_budget;                                               // :93-95
+  return LASSO_OK;
+}
+
 int solve_backtracking(const void* x_any, int64_t ldx, const void* w_any, int64_t ldw, const void* z0_any,
                        int64_t ldz0, void* zout_any, int64_t ldz_any, int64_t n, int64_t d, int64_t k, int kp,
                        int dtype, double alpha, double lr0, int fast, int maxiter, double tol, double eta,
                        int32_t* iters_out, float* last_delta_out, int32_t* trials_out, float* accepted_lr_out,
                        float* accepted_f_out, void* workspace, size_t ws_bytes, hipStream_t st,
                        lasso_allreduce_fn reduce = nullptr, void* reduce_ctx = nullptr, int64_t n_global = 0,
-                       int bt_hint = 0 /* 1: single-trial launches also for fp32 tensors (A/B) */) {
-  // reduce != nullptr: this process holds a row shard.  The sums behind the two global decisions
-  // of an iteration -- F <= Q of every trial (ista.py:23,28,32-35) and sum |z_next - z| <= n k tol
-  // (:93) -- are added over the ranks by the caller's callback; every rank then takes the same
-  // decision from the same numbers.
+                       int bt_hint = 0 /* 1: single-trial launches also for fp32 tensors (A/B); 2: the multi-launch form */) {
+  // ---- validate and carve.  reduce != nullptr: this process holds a row shard (iteration_sync)
+  BtSolve c;
   const bool half = dtype == LASSO_BF16;      // bf16 tensors: bt_bf16.hip kernels, 64-row tiles
-  BtWorkspace ws = carve_bt(workspace, n, k, kp, half, maxiter);
+  c.ws = carve_bt(workspace, n, k, kp, half, maxiter);
+  const BtWorkspace& ws = c.ws;
   if (ws_bytes < ws.bytes) return fail(LASSO_ERR_WORKSPACE, "workspace %zu < %zu bytes", ws_bytes, ws.bytes);
   const int cus = device_cus();
   if (cus <= 0) return fail(LASSO_ERR_HIP, "no HIP device");
-  const int tile_rows = half ? 64 : kTileM;
-  const int ntiles = (int)((n + tile_rows - 1) / tile_rows);
-  const int grid = std::min(ntiles, cus);
-  const float* x = (const float*)x_any;
+  const int tile_rows = half ? 64 : kTileM, ntiles = (int)((n + tile_rows - 1) / tile_rows);
   float* zout = half ? ws.Zf : (float*)zout_any;
   const int64_t ldz = half ? k : ldz_any;
-  // fp32 tensors, one process, flat 16-byte-aligned state: the one-launch-per-iteration kernels (bt_iter.hip) run the
-  // solve; with an all-zero start (z0 == NULL) their first launch writes the zeros of z and y itself
-  const bool fused_form = !half && !reduce && ldz == k && (k & 3) == 0 && k >= 4 && (((uintptr_t)zout) & 15) == 0 &&
-                          (((uintptr_t)ws.Y) & 15) == 0 && (((uintptr_t)ws.G) & 15) == 0 && !(bt_hint & 3);
-  const bool zero_in_kernel = fused_form && !z0_any && maxiter > 0;
+  const bool recompute = half || ldz == k;     // a flat [n][k] state: always for bf16 tensors; fp32: unless z_out is strided
+  // ---- the form, chosen once (BtForm).  The multi-trial and one-launch-per-iteration kernels take fp32 tensors with a flat
+  // 16-byte-aligned point and gradient (flat: ldz == k, so a row pitch that is no multiple of 4 floats never reaches them)
+  const bool flat16 = !half && recompute && (k & 3) == 0 && k >= 4 && (((uintptr_t)zout) & 15) == 0 &&
+                      (((uintptr_t)ws.Y) & 15) == 0 && (((uintptr_t)ws.G) & 15) == 0;
+  const BtForm form = (reduce || !recompute) ? BtForm::Sync : (flat16 && !(bt_hint & 3)) ? BtForm::Fused : BtForm::MultiLaunch;
+  c.half = half; c.recompute = recompute; c.multi_trials = flat16 && !(bt_hint & 1);
+  c.zero_in_kernel = form == BtForm::Fused && !z0_any && maxiter > 0;
+  // ---- pack W and seed the state: z lives in zout, y in the workspace (y0 = z0, ista.py:76-78)
   if (half) {
     LASSO_HIP_TRY(launch_pack_w_bf16(w_any, ldw, (int)d, (int)k, kp, 1, ws.wp, ws.wtp, st));
     if (z0_any) LASSO_HIP_TRY(launch_cvt_bf16(z0_any, ldz0, zout, k, (int)n, (int)k, 1, st));
     else LASSO_HIP_TRY(hipMemsetAsync(zout, 0, (size_t)n * k * 4, st));
+    LASSO_HIP_TRY(hipMemcpy2DAsync(ws.Y, k * 4, zout, ldz * 4, k * 4, n, hipMemcpyDeviceToDevice, st));
   } else {
-    const float* z0 = (const float*)z0_any;
     hipLaunchKernelGGL(pack_w_kernel, dim3(kp / 32, kFistaD / 32), dim3(32, 8), 0, st, (const float*)w_any, ldw,
                        (int)d, (int)k, kp, ws.wp, ws.wtp);
     LASSO_HIP_TRY(hipGetLastError());
-    // working state: z lives in zout, y in the workspace (y0 = z0, ista.py:76-78)
-    if (z0) {
-      if (z0 != zout)
-        LASSO_HIP_TRY(hipMemcpy2DAsync(zout, ldz * 4, z0, ldz0 * 4, k * 4, n, hipMemcpyDeviceToDevice, st));
-    } else if (!zero_in_kernel) {
-      LASSO_HIP_TRY(hipMemset2DAsync(zout, ldz * 4, 0, k * 4, n, st));
-    }
+    if (!c.zero_in_kernel)
+      if (int s = seed_state((const float*)z0_any, ldz0, zout, ldz, ws.Y, n, k, st)) return s;
   }
-  if (!zero_in_kernel)
-    LASSO_HIP_TRY(hipMemcpy2DAsync(ws.Y, k * 4, zout, ldz * 4, k * 4, n, hipMemcpyDeviceToDevice, st));
-
-  BtParams p;
-  p.X = x; p.ldx = ldx; p.Wp = ws.wp; p.Wtp = ws.wtp;
-  p.Xh = x_any; p.Wq1 = ws.wp; p.Wq2 = ws.wtp;
-  // candidates stay on chip and the finish kernel recomputes the accepted one whenever the
-  // state is a flat [n][k] array (always for bf16 tensors; fp32: unless z_out is strided)
-  const bool recompute = half || ldz == k;
   if (reduce && !recompute) return fail(LASSO_ERR_UNSUPPORTED, "row-sharded line search needs ldz == k");
+  BtParams& p = c.p;
+  p.X = (const float*)x_any; p.ldx = ldx; p.Wp = ws.wp; p.Wtp = ws.wtp;
+  p.Xh = x_any; p.Wq1 = ws.wp; p.Wq2 = ws.wtp;
+  p.P = fast ? ws.Y : zout; p.ldp = fast ? k : ldz;
   p.G = ws.G; p.C = recompute ? nullptr : ws.C; p.partials = ws.partials; p.flags = ws.flags; p.fvals = ws.fvals;
-  p.n = (int)n; p.d = (int)d; p.k = (int)k; p.ntiles = ntiles;
-  p.skip = nullptr;
-  const float budget = (float)((double)(reduce ? n_global : n) * (double)k * tol);
-  bool warned = false;
-  double t_mom = 1.0;   // ista.py:78 (python int 1; same arithmetic in double)
-  double hsums[kBtMaxTrials * 5];
-  struct { int flags[4]; float fvals[4]; float delta; } host;
-  int it = 0, prev_trials = kBtBatch - 1;
-  float last = NAN;
-  // ---- the whole solve enqueued WITHOUT a host wait (one process, flat state): every outer iteration is the
-  // gradient, kBtBatch trial launches with the step sequence lr0 / eta^t (a trial behind the accepted one returns at
-  // once), the accept step and a one-block kernel that keeps the iteration's record and evaluates the stop rule on
-  // the device; once the rule fired -- or a search needed more than kBtBatch trials -- the remaining launches are
-  // no-ops (BtParams::skip).  ONE synchronisation at the end; only a search that ran out of trials is continued on
-  // the iteration-by-iteration path below, from the untouched state of the iteration that needed them.
-  // The solve is enqueued in WINDOWS of kBtWindow outer iterations (all `maxiter` iterations at once meant
-  // ~19 launches per remaining iteration of empty work after the rule fired -- maxiter = 1000 stopping at 20: ~19k
-  // no-op launches); the control words are read between windows, and after a search that ran out of pre-enqueued
-  // trials -- ONE iteration on the synchronous path below -- the next window is enqueued asynchronously again.
-  const bool can_async = !reduce && recompute;
-  constexpr int kBtWindow = 16;
-  constexpr int kBtFirst = 5;          // trials of the first multi-trial launch of an iteration
-  // multi-trial launches (bt_trials_kernel): fp32 tensors, flat 16-byte-aligned point and gradient
-  // (can_async implies ldz == k here, so a row pitch that is not a multiple of 4 floats never reaches them)
-  const bool multi = !half && can_async && (k & 3) == 0 && (ldz & 3) == 0 && k >= 4 && (((uintptr_t)zout) & 15) == 0 &&
-                     (((uintptr_t)ws.Y) & 15) == 0 && (((uintptr_t)ws.G) & 15) == 0 && !(bt_hint & 1);
-  // Round 5, fp32 tensors: ONE launch per outer iteration (bt_iter.hip: the accept step of the previous iteration, the
-  // gradient and the first `n_first` trials per tile) + ONE decision launch that also closes the previous iteration;
-  // decisions live in per-iteration slots of ws.flags / ws.fvals (kBtWindow slots of 4 words).  The trials beyond
-  // n_first (old kernel, p and g re-read) are enqueued only after a search of THIS solve has run out of trials once
-  // (`safety`); until then such a search costs one synchronous iteration.  bt_hint & 2: the multi-launch form (A/B).
-  const bool fusedit = multi && !(bt_hint & 2);      // (== fused_form above)
-  int n_first = kBtFirst;
-  bool safety = false;
-  while (it < maxiter) {
-  if (can_async && fusedit) {
-    const int win0 = it, wlen = std::min(kBtWindow, maxiter - it);
-    const int n_first_used = n_first;
-    LASSO_HIP_TRY(hipMemsetAsync(ws.flags, 0, (size_t)kBtWindow * 4 * sizeof(int), st));
-    LASSO_HIP_TRY(hipMemsetAsync(ws.ctl, 0, 4 * sizeof(int), st));
-    BtIterParams q;
-    q.X = x; q.ldx = ldx; q.Wp = ws.wp; q.Wtp = ws.wtp; q.Z = zout; q.Y = ws.Y; q.G = ws.G;
-    q.partials = ws.partials; q.partsM = ws.partsM; q.dpart = ws.dtile; q.skip = ws.ctl;
-    q.n = (int)n; q.d = (int)d; q.k = (int)k; q.ntiles = ntiles; q.fast = fast ? 1 : 0;
-    q.zero_start = (zero_in_kernel && it == 0) ? 1 : 0;
-    const float stop_budget = tol > 0.0 ? budget : -1.0f;
-    double tm = t_mom;
-    float coef_prev = 0.0f;
-    BtSteps steps;
-    for (int i = win0; i < win0 + wlen; ++i) {
-      const double t_next = (1.0 + sqrt(1.0 + 4.0 * tm * tm)) / 2.0;                 // :98
-      const float coef = fast ? (float)((tm - 1.0) / t_next) : 0.0f;                 // :99
-      const int slot = i - win0;
-      int* const cur_flags = ws.flags + 4 * slot;
-      float* const cur_fvals = ws.fvals + 4 * slot;
-      const int* const prev_flags = slot > 0 ? ws.flags + 4 * (slot - 1) : nullptr;
-      const float* const prev_fvals = slot > 0 ? ws.fvals + 4 * (slot - 1) : nullptr;
-      double lr = lr0;
-      for (int b = 0; b < n_first; ++b) {
-        steps.lr[b] = (float)lr; steps.lam[b] = (float)(alpha * lr); steps.hol[b] = (float)(0.5 / lr);
-        lr = lr / eta;                                                               // :47
-      }
-      q.acc_flags = prev_flags; q.acc_fvals = prev_fvals; q.coef = coef_prev; q.tail = 0; q.ntrials = n_first;
-      LASSO_HIP_TRY(launch_bt_iter(q, steps, kp, grid, st));
-      const bool more = safety && n_first < kBtBatch;
-      LASSO_HIP_TRY(launch_bt_iter_decide(ws.partials, ws.partsM, ntiles, alpha, steps, n_first, 0, more ? 0 : 1, cur_flags,
-                                          cur_fvals, prev_flags, prev_fvals, ws.dtile, i - 1, stop_budget, ws.ctl,
-                                          ws.rrec, st));
-      if (more) {
-        BtSteps rest;
-        const int nb = kBtBatch - n_first;
-        for (int b = 0; b < nb; ++b) {
-          rest.lr[b] = (float)lr; rest.lam[b] = (float)(alpha * lr); rest.hol[b] = (float)(0.5 / lr);
-          lr = lr / eta;
-        }
-        BtParams pb = p;
-        pb.P = fast ? ws.Y : zout; pb.ldp = k; pb.flags = cur_flags; pb.fvals = cur_fvals; pb.skip = ws.ctl;
-        LASSO_HIP_TRY(launch_bt_trials_only(pb, kp, grid, rest, nb, ws.partsM, st));
-        LASSO_HIP_TRY(launch_bt_iter_decide(ws.partials, ws.partsM, ntiles, alpha, rest, nb, n_first, 1, cur_flags,
-                                            cur_fvals, nullptr, nullptr, nullptr, 0, -1.0f, ws.ctl, ws.rrec, st));
-      }
-      coef_prev = coef;
-      tm = t_next;
+  p.n = (int)n; p.d = (int)d; p.k = (int)k; p.ntiles = ntiles; p.skip = nullptr;
+  c.kp = kp; c.grid = std::min(ntiles, cus); c.fast = fast; c.maxiter = maxiter; c.zout = zout; c.ldz = ldz; c.nk = n * k;
+  c.alpha = alpha; c.lr0 = lr0; c.eta = eta; c.reduce = reduce; c.reduce_ctx = reduce_ctx; c.st = st;
+  c.stop_budget = tol > 0.0 ? (float)((double)(reduce ? n_global : n) * (double)k * tol) : -1.0f;
+  c.trace = {trials_out, accepted_lr_out, accepted_f_out};
+  // ---- run a window; one whose search ran out of trials is followed by that one iteration on the synchronous path
+  int n_first = kBtFirst; bool safety = false;
+  while (c.it < maxiter) {
+    if (form != BtForm::Sync) {
+      BtWindowEnd end;
+      if (int s = form == BtForm::Fused ? window_fused(c, n_first, safety, &end) : window_multi_launch(c, &end)) return s;
+      if (end == BtWindowEnd::StopRule) break;
+      if (end != BtWindowEnd::OutOfTrials) continue;
     }
-    {   // the accept step of the window's last iteration, and its record
-      const int slot = wlen - 1;
-      q.acc_flags = ws.flags + 4 * slot; q.acc_fvals = ws.fvals + 4 * slot; q.coef = coef_prev; q.tail = 1; q.ntrials = 0;
-      LASSO_HIP_TRY(launch_bt_iter(q, steps, kp, grid, st));
-      LASSO_HIP_TRY(launch_bt_iter_decide(ws.partials, ws.partsM, ntiles, alpha, steps, 0, 0, 0, nullptr, nullptr,
-                                          ws.flags + 4 * slot, ws.fvals + 4 * slot, ws.dtile, win0 + wlen - 1,
-                                          stop_budget, ws.ctl, ws.rrec, st));
-    }
-    // the window's control words and its per-iteration records: two small copies, ONE wait
-    int hctl[4] = {0, 0, 0, 0};
-    float hrec[kBtWindow * 4];
-    LASSO_HIP_TRY(hipMemcpyAsync(hctl, ws.ctl, sizeof(hctl), hipMemcpyDeviceToHost, st));
-    LASSO_HIP_TRY(hipMemcpyAsync(hrec, ws.rrec + 4 * (size_t)win0, (size_t)wlen * 16, hipMemcpyDeviceToHost, st));
-    LASSO_HIP_TRY(hipStreamSynchronize(st));
-    const int done = hctl[1] > 0 ? hctl[1] : win0;
-    if (done > win0) {
-      const int cnt = done - win0;
-      int most = 1, last_trials = 1;
-      for (int i = 0; i < cnt; ++i) {
-        int tr;
-        memcpy(&tr, &hrec[4 * i], sizeof(int));
-        if (trials_out) trials_out[win0 + i] = tr;
-        if (accepted_lr_out) accepted_lr_out[win0 + i] = hrec[4 * i + 1];
-        if (accepted_f_out) accepted_f_out[win0 + i] = hrec[4 * i + 2];
-        most = std::max(most, tr);
-        last_trials = tr;
-      }
-      prev_trials = last_trials;
-      memcpy(&last, &hctl[2], sizeof(float));
-      for (int i = win0; i < done; ++i) t_mom = (1.0 + sqrt(1.0 + 4.0 * t_mom * t_mom)) / 2.0;
-      // the next window computes as many trials per tile as this one's longest search took (every computed trial costs
-      // its GEMM whether it is needed or not; a search that outgrows the guess costs one synchronous iteration)
-      n_first = std::min(kBtBatch, std::max(2, most));
-      // a whole window without a search beyond its first batch: the second trial batch and its decision leave the
-      // windows again (two launches per iteration that did nothing; ADVICE r05: `safety` was never cleared)
-      if (hctl[0] != 2 && most <= n_first_used) safety = false;
-    }
-    it = done;
-    if (hctl[0] == 1) break;     // the stop rule fired at iteration `done` (:93-95)
-    if (hctl[0] != 2) continue;  // the window ran through: next window
-    safety = true;               // a search ran out of trials: that iteration below, from its untouched state
-  } else if (can_async) {
-    const int win0 = it, wlen = std::min(kBtWindow, maxiter - it);
-    LASSO_HIP_TRY(hipMemsetAsync(ws.flags, 0, 4 * sizeof(int), st));
-    LASSO_HIP_TRY(hipMemsetAsync(ws.ctl, 0, 4 * sizeof(int), st));
-    p.skip = ws.ctl;
-    double tm = t_mom;
-    for (int i = win0; i < win0 + wlen; ++i) {
-      const double t_next = (1.0 + sqrt(1.0 + 4.0 * tm * tm)) / 2.0;                 // :98
-      const float coef = fast ? (float)((tm - 1.0) / t_next) : 0.0f;                 // :99
-      p.P = fast ? ws.Y : zout;
-      p.ldp = fast ? k : ldz;
-      if (half) LASSO_HIP_TRY(launch_bt16_grad(p, kp, grid, st));
-      else LASSO_HIP_TRY(launch_bt_grad(p, kp, grid, st));
-      double lr = lr0;
-      if (multi) {
-        // fp32 tensors: the kBtBatch pre-enqueued trials as TWO launches -- trials 0 .. kBtFirst-1 (p and g of a tile
-        // read once, in registers for all of them) and the rest (a no-op once a trial of the first launch passed)
-        for (int b0 = 0; b0 < kBtBatch; b0 += kBtFirst) {
-          BtSteps steps;
-          const int nb = std::min(kBtFirst, kBtBatch - b0);
-          for (int b = 0; b < nb; ++b) {
-            steps.lr[b] = (float)lr; steps.lam[b] = (float)(alpha * lr); steps.hol[b] = (float)(0.5 / lr);
-            lr = lr / eta;                                                             // :47
-          }
-          LASSO_HIP_TRY(launch_bt_trials(p, kp, grid, alpha, steps, nb, b0, ws.partsM, st));
-        }
-      } else
-      for (int b = 0; b < kBtBatch; ++b) {
-        if (half) {
-          LASSO_HIP_TRY(launch_bt16_trial(p, kp, grid, (float)lr, (float)(alpha * lr), 0, st));
-          LASSO_HIP_TRY(launch_bt_decide(p, alpha, lr, b, 0, st, nullptr));
-        } else {
-          LASSO_HIP_TRY(launch_bt_trial(p, kp, grid, alpha, lr, b, 0, st, nullptr));
-        }
-        lr = lr / eta;                                                                 // :47
-      }
-      LASSO_HIP_TRY(launch_bt_finish_recompute(zout, ws.Y, p.P, ws.G, n * k, coef, ws.flags, ws.fvals, ws.dpart,
-                                               kBtFinishGrid, st, ws.ctl));
-      LASSO_HIP_TRY(launch_bt_iter_end(ws.dpart, kBtFinishGrid, ws.flags, ws.fvals, ws.ctl, i,
-                                       tol > 0.0 ? budget : -1.0f, ws.rtrials, ws.rlrs, ws.rfs, st));
-      tm = t_next;
-    }
-    p.skip = nullptr;
-    int hctl[4] = {0, 0, 0, 0};
-    LASSO_HIP_TRY(hipMemcpyAsync(hctl, ws.ctl, sizeof(hctl), hipMemcpyDeviceToHost, st));
-    LASSO_HIP_TRY(hipStreamSynchronize(st));
-    const int done = hctl[1] > 0 ? hctl[1] : win0;      // (ctl[1] = iterations completed, absolute; 0: none in this window)
-    if (done > win0) {
-      const int cnt = done - win0;
-      std::vector<int> ht(cnt);
-      std::vector<float> hl(cnt), hf(cnt);
-      LASSO_HIP_TRY(hipMemcpy(ht.data(), ws.rtrials + win0, (size_t)cnt * 4, hipMemcpyDeviceToHost));
-      LASSO_HIP_TRY(hipMemcpy(hl.data(), ws.rlrs + win0, (size_t)cnt * 4, hipMemcpyDeviceToHost));
-      LASSO_HIP_TRY(hipMemcpy(hf.data(), ws.rfs + win0, (size_t)cnt * 4, hipMemcpyDeviceToHost));
-      for (int i = 0; i < cnt; ++i) {
-        if (trials_out) trials_out[win0 + i] = ht[i];
-        if (accepted_lr_out) accepted_lr_out[win0 + i] = hl[i];
-        if (accepted_f_out) accepted_f_out[win0 + i] = hf[i];
-      }
-      prev_trials = ht[cnt - 1];
-      memcpy(&last, &hctl[2], sizeof(float));
-      for (int i = win0; i < done; ++i) t_mom = (1.0 + sqrt(1.0 + 4.0 * t_mom * t_mom)) / 2.0;
-    }
-    it = done;
-    if (hctl[0] == 1) break;     // the stop rule fired at iteration `done` (:93-95)
-    if (hctl[0] != 2) continue;  // the window ran through: next window
-    // a search ran out of pre-enqueued trials at iteration `it`: that iteration below, from its untouched state
-  }
-  {
-    const double t_next = (1.0 + sqrt(1.0 + 4.0 * t_mom * t_mom)) / 2.0;             // :98
-    const float coef = fast ? (float)((t_mom - 1.0) / t_next) : 0.0f;                 // :99
-    p.P = fast ? ws.Y : zout;
-    p.ldp = fast ? k : ldz;
-    LASSO_HIP_TRY(hipMemsetAsync(ws.flags, 0, 4 * sizeof(int), st));
-    if (half) LASSO_HIP_TRY(launch_bt16_grad(p, kp, grid, st));
-    else LASSO_HIP_TRY(launch_bt_grad(p, kp, grid, st));
-    double lr = lr0;
-    int t = 0;
-    bool accepted = false;
-    while (!accepted) {
-      const bool give_up = t >= kBtMaxTrials;
-      // the first batch of an iteration is sized from the previous iteration's trial count
-      // (trials enqueued after the accepted one only cost their launch, but that adds up)
-      const int want = t == 0 ? std::min(kBtBatch, std::max(2, prev_trials + 1)) : kBtBatch / 2;
-      const int batch = give_up ? 1 : std::min(want, kBtMaxTrials - t);
-      double lr_batch[kBtMaxTrials];
-      for (int b = 0; b < batch; ++b) {
-        const double lr_t = give_up ? lr0 : lr;      // ista.py:48-52: warn and revert to the initial step size
-        const int idx = give_up ? t : t + b, force = give_up ? 1 : 0;
-        double* const sums_dev = reduce ? ws.sums + 5 * b : nullptr;
-        lr_batch[b] = lr_t;
-        if (half) {
-          LASSO_HIP_TRY(launch_bt16_trial(p, kp, grid, (float)lr_t, (float)(alpha * lr_t), force, st));
-          LASSO_HIP_TRY(launch_bt_decide(p, alpha, lr_t, idx, force, st, sums_dev));
-        } else {
-          LASSO_HIP_TRY(launch_bt_trial(p, kp, grid, alpha, lr_t, idx, force, st, sums_dev));
-        }
-        if (give_up) warned = true;
-        else lr = lr / eta;                                                            // :47
-      }
-      if (reduce) {
-        // the batch's sums: all ranks add theirs, then the decision of bt_decide_kernel on the host,
-        // trial by trial in order -- same float arithmetic, same outcome on every rank
-        LASSO_HIP_TRY(hipMemcpyAsync(hsums, ws.sums, (size_t)batch * 5 * sizeof(double), hipMemcpyDeviceToHost, st));
-        LASSO_HIP_TRY(hipStreamSynchronize(st));
-        if (reduce(reduce_ctx, hsums, batch * 5) != 0) return fail(LASSO_ERR_HIP, "all-reduce callback failed");
-        struct { int flags[4]; float fvals[4]; } dec = {{0, 0, 0, 0}, {0.f, 0.f, 0.f, 0.f}};
-        for (int b = 0; b < batch && !dec.flags[0]; ++b) {
-          const double* sm = hsums + 5 * b;
-          const float rss0 = (float)sm[0], rss1 = (float)sm[1], l1 = (float)sm[2], dzg = (float)sm[3], dz2 = (float)sm[4];
-          const float alpha_f = (float)alpha, half_over_lr = (float)(0.5 / lr_batch[b]);
-          const float f0 = 0.5f * rss0;                                              // ista.py:23
-          const float al1 = alpha_f * l1;
-          const float F = 0.5f * rss1 + al1;                                         // :28
-          const float Q = ((f0 + dzg) + half_over_lr * dz2) + al1;                   // :32-35
-          dec.fvals[0] = F; dec.fvals[1] = Q;
-          dec.flags[1] = (give_up ? t : t + b) + 1;
-          if (give_up || F <= Q) {                                                   // :45
-            dec.flags[0] = 1; dec.flags[2] = give_up ? t : t + b;
-            dec.fvals[2] = (float)lr_batch[b]; dec.fvals[3] = (float)(alpha * lr_batch[b]);
-          }
-        }
-        LASSO_HIP_TRY(hipMemcpyAsync(ws.flags, dec.flags, sizeof(dec.flags), hipMemcpyHostToDevice, st));
-        LASSO_HIP_TRY(hipMemcpyAsync(ws.fvals, dec.fvals, sizeof(dec.fvals), hipMemcpyHostToDevice, st));
-        LASSO_HIP_TRY(hipStreamSynchronize(st));     // (dec lives on this stack frame)
-      }
-      t += batch;
-      if (recompute)   // P is Y (fast) or Z itself: element-wise in place is safe either way
-        LASSO_HIP_TRY(launch_bt_finish_recompute(zout, ws.Y, p.P, ws.G, n * k, coef, ws.flags, ws.fvals, ws.dpart,
-                                                 kBtFinishGrid, st));
-      else
-        LASSO_HIP_TRY(launch_bt_finish(zout, ldz, ws.Y, ws.C, (int)n, (int)k, coef, ws.flags, ws.dpart,
-                                       kBtFinishGrid, st));
-      hipLaunchKernelGGL(reduce_partials_kernel, dim3(1), dim3(256), 0, st, ws.dpart, kBtFinishGrid, ws.delta);
-      LASSO_HIP_TRY(hipGetLastError());
-      LASSO_HIP_TRY(hipMemcpyAsync(host.flags, ws.flags, 4 * sizeof(int), hipMemcpyDeviceToHost, st));
-      LASSO_HIP_TRY(hipMemcpyAsync(&host.delta, ws.delta, sizeof(float), hipMemcpyDeviceToHost, st));
-      if (accepted_lr_out || accepted_f_out)
-        LASSO_HIP_TRY(hipMemcpyAsync(host.fvals, ws.fvals, 4 * sizeof(float), hipMemcpyDeviceToHost, st));
-      LASSO_HIP_TRY(hipStreamSynchronize(st));
-      accepted = host.flags[0] != 0;
-    }
-    if (reduce) {                                    // sum |z_next - z| over all ranks (:93)
-      double dsum = (double)host.delta;
-      if (reduce(reduce_ctx, &dsum, 1) != 0) return fail(LASSO_ERR_HIP, "all-reduce callback failed");
-      host.delta = (float)dsum;
-    }
-    prev_trials = host.flags[2] + 1;
-    if (trials_out) trials_out[it] = host.flags[2] + 1;            // trials evaluated up to the accepted one
-    if (accepted_lr_out) accepted_lr_out[it] = host.fvals[2];      // the step the iteration used (ista.py:40,52)
-    if (accepted_f_out) accepted_f_out[it] = host.fvals[0];        // F(z_next) of the accepted trial (:28)
-    last = host.delta;
-    t_mom = t_next;
-    ++it;
-    if (tol > 0.0 && host.delta <= budget) break;                                      // :93-95
-  }
+    bool stop = false;
+    if (int s = iteration_sync(c, &stop)) return s;
+    if (stop) break;
   }
   if (half) LASSO_HIP_TRY(launch_cvt_bf16(zout, k, zout_any, ldz_any, (int)n, (int)k, 0, st));
-  if (iters_out) *iters_out = it;
-  if (last_delta_out) *last_delta_out = last;
-  return warned ? fail(LASSO_WARN_LINESEARCH, "backtracking line search failed; reverted to lr0") : LASSO_OK;
+  if (iters_out) *iters_out = c.it;
+  if (last_delta_out) *last_delta_out = c.last;
+  return c.warned ? fail(LASSO_WARN_LINESEARCH, "backtracking line search failed; reverted to lr0") : LASSO_OK;
 }
 
 
@@ -1156,16 +1157,14 @@ int solve_fixed_bf16(const void* x_any, int64_t ldx, const void* w_any, int64_t 
   p.n = (int)n; p.d = (int)d; p.k = (int)k; p.ntiles = ntiles;
   const float budget = (float)((double)n * (double)k * tol);
   const float lr_f = (float)lr, lam = (float)(alpha * lr);
-  double t_mom = 1.0;
+  Momentum mom;
   float last = NAN;
   int it = 0;
   for (; it < maxiter; ++it) {
-    const double t_next = (1.0 + sqrt(1.0 + 4.0 * t_mom * t_mom)) / 2.0;
-    const float coef = fast ? (float)((t_mom - 1.0) / t_next) : 0.0f;
+    const float coef = mom.next(fast);
     p.P = ws.Y; p.ldp = k;                    // ISTA: coef = 0 keeps y == z
     LASSO_HIP_TRY(launch_bt16_grad(p, kp, std::min(ntiles, cus), st));
     LASSO_HIP_TRY(launch_generic_prox(Z, k, ws.Y, ws.G, (int)n, (int)k, lr_f, lam, coef, ws.dpart, kBtFinishGrid, st));
-    t_mom = t_next;
     if (tol > 0.0) {
       hipLaunchKernelGGL(reduce_partials_kernel, dim3(1), dim3(256), 0, st, ws.dpart, kBtFinishGrid, ws.delta);
       LASSO_HIP_TRY(hipGetLastError());
@@ -1286,28 +1285,20 @@ int solve_generic(const float* x, int64_t ldx, const float* w, int64_t ldw, cons
   if (ws_bytes < ws.bytes) return fail(LASSO_ERR_WORKSPACE, "workspace %zu < %zu bytes", ws_bytes, ws.bytes);
   if (n > INT32_MAX || d > INT32_MAX || k > INT32_MAX) return fail(LASSO_ERR_UNSUPPORTED, "shape too large");
   LASSO_HIP_TRY(launch_transpose_pad(w, ldw, (int)d, (int)k, ws.Wt, d, (int)k, (int)d, st));
-  if (z0) {
-    if (z0 != zout)
-      LASSO_HIP_TRY(hipMemcpy2DAsync(zout, ldz * 4, z0, ldz0 * 4, k * 4, n, hipMemcpyDeviceToDevice, st));
-  } else {
-    LASSO_HIP_TRY(hipMemset2DAsync(zout, ldz * 4, 0, k * 4, n, st));
-  }
-  LASSO_HIP_TRY(hipMemcpy2DAsync(ws.Y, k * 4, zout, ldz * 4, k * 4, n, hipMemcpyDeviceToDevice, st));
+  if (int s = seed_state(z0, ldz0, zout, ldz, ws.Y, n, k, st)) return s;
   const float budget = (float)((double)n * (double)k * tol);
   const float lr_f = (float)lr, lam = (float)(alpha * lr);
-  double t_mom = 1.0;
+  Momentum mom;
   float last = NAN;
   int it = 0;
   const int parts = gemm_nt_prox_parts((int)n, (int)k);
   auto iterate = [&](float* delta_slot) -> int {
-    const double t_next = (1.0 + sqrt(1.0 + 4.0 * t_mom * t_mom)) / 2.0;
-    const float coef = fast ? (float)((t_mom - 1.0) / t_next) : 0.0f;
+    const float coef = mom.next(fast);
     // NR = x - y W^T  (= -r);   G = 0 - NR Wt^T = r W
     // the gradient block g = r W never goes to memory: the proximal step runs in GEMM-2's epilogue
     LASSO_HIP_TRY(launch_gemm_nt_sub(ws.Y, k, w, ldw, x, ldx, ws.NR, d, (int)n, (int)d, (int)k, st));
     LASSO_HIP_TRY(launch_gemm_nt_prox(ws.NR, d, ws.Wt, d, zout, ldz, ws.Y, k, (int)n, (int)k, (int)d, lr_f, lam, coef,
                                       ws.dpart, st));
-    t_mom = t_next;
     if (delta_slot) {
       hipLaunchKernelGGL(reduce_partials_kernel, dim3(1), dim3(256), 0, st, ws.dpart, parts, delta_slot);
       LASSO_HIP_TRY(hipGetLastError());
@@ -1337,7 +1328,7 @@ int solve_generic(const float* x, int64_t ldx, const float* w, int64_t ldw, cons
       LASSO_HIP_TRY(hipGetLastError());
       return LASSO_OK;
     };
-    if (int s = speculate_stop_rule(maxiter, budget, ws.delta, st, &t_mom, iterate, save, restore,
+    if (int s = speculate_stop_rule(maxiter, budget, ws.delta, st, &mom.t, iterate, save, restore,
                                     [] { return (int)LASSO_OK; }, &it, &last, "lasso_fista_solve (unfused)"))
       return s;
   }
@@ -1356,20 +1347,13 @@ int run_generic(const float* x, int64_t ldx, const float* z_in, int64_t ldz_in,
   GenWorkspace ws = carve_generic(workspace, n, d, k, false, false);   // (no stop-rule checkpoint here)
   if (ws_bytes < ws.bytes) return fail(LASSO_ERR_WORKSPACE, "workspace %zu < %zu bytes", ws_bytes, ws.bytes);
   if (n == 0) return LASSO_OK;
-  if (z_in) {
-    if (z_in != z_out)
-      LASSO_HIP_TRY(hipMemcpy2DAsync(z_out, ldz_out * 4, z_in, ldz_in * 4, k * 4, n, hipMemcpyDeviceToDevice, st));
-  } else {
-    LASSO_HIP_TRY(hipMemset2DAsync(z_out, ldz_out * 4, 0, k * 4, n, st));
-  }
-  const float* ysrc = y_in ? y_in : z_out;
-  LASSO_HIP_TRY(hipMemcpy2DAsync(ws.Y, k * 4, ysrc, (y_in ? ldy_in : ldz_out) * 4, k * 4, n, hipMemcpyDeviceToDevice, st));
+  if (int s = seed_state(z_in, ldz_in, z_out, ldz_out, y_in ? nullptr : ws.Y, n, k, st)) return s;
+  if (y_in) LASSO_HIP_TRY(hipMemcpy2DAsync(ws.Y, k * 4, y_in, ldy_in * 4, k * 4, n, hipMemcpyDeviceToDevice, st));
   const float lr_f = (float)lr, lam = (float)(alpha * lr);
-  double t_mom = 1.0;
-  for (int i = 0; i < it0; ++i) t_mom = (1.0 + sqrt(1.0 + 4.0 * t_mom * t_mom)) / 2.0;
+  Momentum mom;
+  mom.skip(it0);
   for (int i = 0; i < iters; ++i) {
-    const double t_next = (1.0 + sqrt(1.0 + 4.0 * t_mom * t_mom)) / 2.0;
-    const float coef = fast ? (float)((t_mom - 1.0) / t_next) : 0.0f;
+    const float coef = mom.next(fast);
     LASSO_HIP_TRY(launch_gemm_nt_sub(ws.Y, k, ws.Wc, k, x, ldx, ws.NR, d, (int)n, (int)d, (int)k, st));
     LASSO_HIP_TRY(launch_gemm_nt_prox(ws.NR, d, ws.Wt, d, z_out, ldz_out, ws.Y, k, (int)n, (int)k, (int)d, lr_f, lam,
                                       coef, ws.dpart, st));
@@ -1378,7 +1362,6 @@ int run_generic(const float* x, int64_t ldx, const float* z_in, int64_t ldz_in,
                          delta_dev + i);
       LASSO_HIP_TRY(hipGetLastError());
     }
-    t_mom = t_next;
   }
   if (y_out)
     LASSO_HIP_TRY(hipMemcpy2DAsync(y_out, ldy_out * 4, ws.Y, k * 4, k * 4, n, hipMemcpyDeviceToDevice, st));
@@ -1402,35 +1385,29 @@ int solve_generic_backtracking(const float* x, int64_t ldx, const float* w, int6
   if (ws_bytes < ws.bytes) return fail(LASSO_ERR_WORKSPACE, "workspace %zu < %zu bytes", ws_bytes, ws.bytes);
   if (n > INT32_MAX || d > INT32_MAX || k > INT32_MAX) return fail(LASSO_ERR_UNSUPPORTED, "shape too large");
   LASSO_HIP_TRY(launch_transpose_pad(w, ldw, (int)d, (int)k, ws.Wt, d, (int)k, (int)d, st));
-  if (z0) {
-    if (z0 != zout)
-      LASSO_HIP_TRY(hipMemcpy2DAsync(zout, ldz * 4, z0, ldz0 * 4, k * 4, n, hipMemcpyDeviceToDevice, st));
-  } else {
-    LASSO_HIP_TRY(hipMemset2DAsync(zout, ldz * 4, 0, k * 4, n, st));
-  }
-  LASSO_HIP_TRY(hipMemcpy2DAsync(ws.Y, k * 4, zout, ldz * 4, k * 4, n, hipMemcpyDeviceToDevice, st));
+  if (int s = seed_state(z0, ldz0, zout, ldz, ws.Y, n, k, st)) return s;
   BtParams bp;                                             // only what bt_decide_kernel reads
   bp.skip = nullptr;
   bp.partials = ws.part; bp.ntiles = kGenGrid; bp.flags = ws.flags; bp.fvals = ws.fvals;
   const float budget = (float)((double)(reduce ? n_global : n) * (double)k * tol);
+  const BtTrace trace = {trials_out, accepted_lr_out, accepted_f_out};
   bool warned = false;
-  double t_mom = 1.0;
+  Momentum mom;
   float last = NAN;
   int it = 0;
   for (; it < maxiter; ++it) {
-    const double t_next = (1.0 + sqrt(1.0 + 4.0 * t_mom * t_mom)) / 2.0;             // :98
-    const float coef = fast ? (float)((t_mom - 1.0) / t_next) : 0.0f;                 // :99 (ISTA: y == z)
+    const float coef = mom.next(fast);                                                // :98-99 (ISTA: y == z)
     LASSO_HIP_TRY(hipMemsetAsync(ws.flags, 0, 4 * sizeof(int), st));
     // NR = x - p W^T (= -r0, :22);  G = r0 W (:24);  partials[0] = sum r0^2 (:23)
     LASSO_HIP_TRY(launch_gemm_nt_sub(ws.Y, k, w, ldw, x, ldx, ws.NR, d, (int)n, (int)d, (int)k, st));
     LASSO_HIP_TRY(launch_gemm_nt_sub(ws.NR, d, ws.Wt, d, nullptr, 0, ws.G, k, (int)n, (int)k, (int)d, st));
     LASSO_HIP_TRY(launch_sumsq_partials(ws.NR, n * d, ws.part, kGenGrid, st));
-    double lr = lr0;
+    StepLadder ladder{lr0, eta, alpha};
     int t = 0, accepted_at = -1;
-    struct { int flags[4]; float fvals[4]; } host;
+    HostDecision host;
     for (;;) {
       const bool give_up = t >= kBtMaxTrials;
-      const double lr_t = give_up ? lr0 : lr;                                           // :48-52
+      const double lr_t = give_up ? lr0 : ladder.lr;                                    // :48-52
       LASSO_HIP_TRY(launch_generic_trial(ws.Y, ws.G, ws.C, n * k, (float)lr_t, (float)(alpha * lr_t), ws.part,
                                          kGenGrid, st));                                // :40, :31-35
       LASSO_HIP_TRY(launch_gemm_nt_sub(ws.C, k, w, ldw, x, ldx, ws.NR, d, (int)n, (int)d, (int)k, st));   // :27
@@ -1441,19 +1418,9 @@ int solve_generic_backtracking(const float* x, int64_t ldx, const float* w, int6
         LASSO_HIP_TRY(hipMemcpyAsync(hs, ws.sums, sizeof(hs), hipMemcpyDeviceToHost, st));
         LASSO_HIP_TRY(hipStreamSynchronize(st));
         if (reduce(reduce_ctx, hs, 5) != 0) return fail(LASSO_ERR_HIP, "all-reduce callback failed");
-        const float rss0 = (float)hs[0], rss1 = (float)hs[1], l1 = (float)hs[2], dzg = (float)hs[3], dz2 = (float)hs[4];
-        const float f0 = 0.5f * rss0, al1 = (float)alpha * l1;                          // ista.py:23
-        const float F = 0.5f * rss1 + al1;                                              // :28
-        const float Q = ((f0 + dzg) + (float)(0.5 / lr_t) * dz2) + al1;                 // :32-35
-        memset(&host, 0, sizeof(host));
-        host.fvals[0] = F; host.fvals[1] = Q; host.flags[1] = t + 1;
-        if (give_up || F <= Q) {                                                        // :45
-          host.flags[0] = 1; host.flags[2] = t;
-          host.fvals[2] = (float)lr_t; host.fvals[3] = (float)(alpha * lr_t);
-        }
-        LASSO_HIP_TRY(hipMemcpyAsync(ws.flags, host.flags, sizeof(host.flags), hipMemcpyHostToDevice, st));
-        LASSO_HIP_TRY(hipMemcpyAsync(ws.fvals, host.fvals, sizeof(host.fvals), hipMemcpyHostToDevice, st));
-        LASSO_HIP_TRY(hipStreamSynchronize(st));
+        host = HostDecision();
+        host.take(hs, alpha, lr_t, t, give_up);                                         // ista.py:23, :28, :32-35, :45
+        if (int s = host.upload(ws.flags, ws.fvals, st)) return s;
       } else {
         LASSO_HIP_TRY(hipMemcpyAsync(host.flags, ws.flags, sizeof(host.flags), hipMemcpyDeviceToHost, st));
         LASSO_HIP_TRY(hipMemcpyAsync(host.fvals, ws.fvals, sizeof(host.fvals), hipMemcpyDeviceToHost, st));
@@ -1461,7 +1428,7 @@ int solve_generic_backtracking(const float* x, int64_t ldx, const float* w, int6
       }
       if (give_up) warned = true;
       if (host.flags[0]) { accepted_at = t; break; }
-      lr = lr / eta;                                                                    // :47
+      ladder.descend();                                                                 // :47
       ++t;
     }
     LASSO_HIP_TRY(launch_bt_finish(zout, ldz, ws.Y, ws.C, (int)n, (int)k, coef, ws.flags, ws.dpart, kGenGrid, st));
@@ -1474,10 +1441,7 @@ int solve_generic_backtracking(const float* x, int64_t ldx, const float* w, int6
       if (reduce(reduce_ctx, &dsum, 1) != 0) return fail(LASSO_ERR_HIP, "all-reduce callback failed");
       last = (float)dsum;
     }
-    if (trials_out) trials_out[it] = accepted_at + 1;
-    if (accepted_lr_out) accepted_lr_out[it] = host.fvals[2];
-    if (accepted_f_out) accepted_f_out[it] = host.fvals[0];
-    t_mom = t_next;
+    trace.record(it, accepted_at + 1, host.fvals[2], host.fvals[0]);
     if (tol > 0.0 && last <= budget) { ++it; break; }                                   // :93-95
   }
   if (iters_out) *iters_out = it;
@@ -1594,12 +1558,8 @@ int conv_two_kernel_step(const ConvWorkspace& ws, const ConvGeom& g, const float
 // momentum coefficients c_i = (t_i - 1) / t_{i+1} of iterations 0 .. iterations-1 (ista.py:41-42; 0 without momentum)
 std::vector<float> fista_coefs(int iterations, int fast) {
   std::vector<float> coef((size_t)std::max(iterations, 1), 0.0f);
-  double t = 1.0;
-  for (int i = 0; i < iterations; ++i) {
-    const double tn = (1.0 + sqrt(1.0 + 4.0 * t * t)) / 2.0;
-    coef[i] = fast ? (float)((t - 1.0) / tn) : 0.0f;
-    t = tn;
-  }
+  Momentum mom;
+  for (int i = 0; i < iterations; ++i) coef[i] = mom.next(fast);
   return coef;
 }
 
@@ -1845,15 +1805,7 @@ static int solve_impl(const void* x_dev, int64_t ldx, const void* w_dev, int64_t
   float* zout = (float*)z_out_dev;
 
   if (maxiter == 0 || n == 0) {   // ista.py:76,104: returns z0 itself
-    if (n > 0) {
-      if (z0) {
-        if (z0 != zout)
-          LASSO_HIP_TRY(hipMemcpy2DAsync(zout, ldz * 4, z0, ldz0 * 4, k * 4, n, hipMemcpyDeviceToDevice, st));
-      } else {
-        LASSO_HIP_TRY(hipMemset2DAsync(zout, ldz * 4, 0, k * 4, n, st));
-      }
-    }
-    return LASSO_OK;
+    return n > 0 ? seed_state(z0, ldz0, zout, ldz, nullptr, n, k, st) : LASSO_OK;
   }
 
   int hint = stop_mode & LASSO_KERNEL_MASK;            // kernel-selection hint rides in stop_mode
@@ -3263,7 +3215,7 @@ int lasso_conv_ista_solve(const void* x_dev, const void* w_dev, const void* z0_d
   }
   const float budget = (float)((double)M * (double)g.K * tol);     // ista.py:16, compared in fp32
   const float lr_f = (float)lr, lam = (float)(alpha * lr);
-  double t_mom = 1.0;
+  Momentum mom;
   float last = NAN;
   int it = 0;
   // conv_fused.hip takes up to 64 iterations per launch: `iterate` only queues them (momentum factor + where the sum
@@ -3284,8 +3236,7 @@ int lasso_conv_ista_solve(const void* x_dev, const void* w_dev, const void* z0_d
   };
   // one iteration on the stream; the sum |z - z_next| of the iteration (ista.py:44) goes to *delta_slot when given
   auto iterate = [&](float* delta_slot) -> int {
-    const double t_next = (1.0 + sqrt(1.0 + 4.0 * t_mom * t_mom)) / 2.0;           // :41
-    const float coef = fast ? (float)((t_mom - 1.0) / t_next) : 0.0f;               // :42
+    const float coef = mom.next(fast);                                              // :41-42
     if (fused) {
       const bool fits = queued < q_max &&
                         (delta_slot ? (q_slot0 && delta_slot == q_slot0 + queued) : q_slot0 == nullptr);
@@ -3293,12 +3244,10 @@ int lasso_conv_ista_solve(const void* x_dev, const void* w_dev, const void* z0_d
         if (int s = flush()) return s;
       if (queued == 0) q_slot0 = delta_slot;
       q_coef[queued++] = coef;
-      t_mom = t_next;
       return LASSO_OK;
     }
     int dcount = 0;
     if (int s = conv_two_kernel_step(ws, g, (const float*)x_dev, conv_w, lr_f, lam, coef, cus, &dcount, st)) return s;
-    t_mom = t_next;
     if (delta_slot) {
       hipLaunchKernelGGL(reduce_partials_kernel, dim3(1), dim3(256), 0, st, ws.dpart, dcount, delta_slot);
       LASSO_HIP_TRY(hipGetLastError());
@@ -3324,7 +3273,7 @@ int lasso_conv_ista_solve(const void* x_dev, const void* w_dev, const void* z0_d
       LASSO_HIP_TRY(hipGetLastError());
       return LASSO_OK;
     };
-    if (int s = speculate_stop_rule(maxiter, budget, ws.delta, st, &t_mom, iterate, save, restore, flush, &it, &last,
+    if (int s = speculate_stop_rule(maxiter, budget, ws.delta, st, &mom.t, iterate, save, restore, flush, &it, &last,
                                     "lasso_conv_ista_solve"))
       return s;
   }
@@ -3609,15 +3558,7 @@ int lasso_fista_backward_steps(const void* x_dev, int64_t ldx, const void* w_dev
   if (n == 0) return LASSO_OK;
   const int cus = device_cus();
   // momentum coefficients c_i = (t_i - 1)/t_{i+1}  (ista.py:98-99)
-  std::vector<float> coef((size_t)std::max(iterations, 1));
-  {
-    double t = 1.0;
-    for (int i = 0; i < iterations; ++i) {
-      const double tn = (1.0 + sqrt(1.0 + 4.0 * t * t)) / 2.0;
-      coef[i] = fast ? (float)((t - 1.0) / tn) : 0.0f;
-      t = tn;
-    }
-  }
+  const std::vector<float> coef = fista_coefs(iterations, fast);
   LASSO_HIP_TRY(launch_transpose_pad(W, ldw, (int)d, (int)k, ws.Wt, d, (int)k, (int)d, st));
   float* zb_next = ws.zbA;
   float* zb_cur = ws.zbB;

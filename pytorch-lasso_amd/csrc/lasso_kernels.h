@@ -8,6 +8,8 @@
 #include <math.h>
 #include <algorithm>
 
+#include "linesearch_host.hpp"      // kBtMultiMax, BtSteps
+
 struct lasso_gpsr_options;
 struct lasso_gpsr_result;
 
@@ -185,9 +187,7 @@ hipError_t launch_objective_generic(const float* X, int64_t ldx, const float* W,
                                     hipStream_t stream);
 
 hipError_t launch_bt_grad(const BtParams& p, int kpad, int grid, hipStream_t stream);
-// several trials of one outer iteration in one launch (backtrack.hip bt_trials_kernel): their steps, by value
-constexpr int kBtMultiMax = 8;
-struct BtSteps { float lr[kBtMultiMax]; float lam[kBtMultiMax]; float hol[kBtMultiMax]; };   // step, alpha * step, 0.5 / step
+// several trials of one outer iteration in one launch (backtrack.hip bt_trials_kernel): their steps by value, BtSteps
 hipError_t launch_bt_trials(const BtParams& p, int kpad, int grid, double alpha, const BtSteps& s, int ntrials,
                             int first_index, float* partsM /* [kBtMultiMax][4][ntiles] */, hipStream_t stream);
 // one launch per outer iteration (bt_iter.hip): accept step of the previous iteration + gradient + `ntrials` trials per

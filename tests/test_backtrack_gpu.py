@@ -542,3 +542,55 @@ def test_bf16_fixed_step_beyond_the_persistent_kernels_capacity():
     ob = orc.lasso_objective(Xb.float().cpu(), z.float().cpu(), Wb.float().cpu(), 0.5).item()
     of = orc.lasso_objective(Xb.float().cpu(), zf.cpu(), Wb.float().cpu(), 0.5).item()
     assert abs(ob - of) <= 1e-3 * of, (ob, of)
+
+
+@pytest.mark.parametrize("fast", [True, False])
+def test_line_search_into_a_strided_z_out(fast):
+    """z_out as the first k columns of an [n, k + 8] tensor (ldz != k; every Python caller passes a contiguous z_out): the
+    candidates are kept in the workspace and copied by the finish kernel, every iteration runs on the synchronous path.
+    (a) lr0 = 1; (b) lr0 = 30: more than 8 trials per search, so the second batches of kBtBatch / 2 trials run.  The
+    oracle's iteration count and trials, the contiguous solve's accepted steps and -- bit for bit -- its codes; the
+    padding columns are not touched.  (a) starts from a zero tensor (copied into z_out), (b) from z0 = NULL (memset)."""
+    import ctypes as C
+    from lasso_amd import _native as nat
+    from margins import record_margins
+    from oracle import lasso_oracle as orc
+    n, d, k, pad, sentinel = 300, 48, 160, 8, -7.25
+    g = torch.Generator().manual_seed(5)
+    W = torch.nn.functional.normalize(torch.randn(d, k, generator=g), dim=0)
+    X = torch.randn(n, d, generator=g)
+    Xg, Wg, L = X.cuda(), W.cuda(), nat.lib()
+
+    def solve(z, z0, lr0, maxiter):
+        nbytes = L.lasso_fista_workspace_bytes(n, d, k, nat.LASSO_F32, maxiter, 0.0, nat.STOP_GLOBAL, 1)
+        ws = nat.workspace(Xg.device, nbytes)
+        iters, last = C.c_int32(0), C.c_float(float("nan"))
+        trials, acc_lr, acc_f = (C.c_int32 * maxiter)(), (C.c_float * maxiter)(), (C.c_float * maxiter)()
+        nat.check(L.lasso_fista_solve(
+            nat.ptr(Xg), Xg.stride(0), nat.ptr(Wg), Wg.stride(0), nat.ptr(z0), z0.stride(0) if z0 is not None else 0,
+            nat.ptr(z), z.stride(0), n, d, k, nat.LASSO_F32, 0.3, lr0, int(fast), maxiter, 0.0, nat.STOP_GLOBAL, 1, 1.5,
+            C.byref(iters), C.byref(last), trials, acc_lr, acc_f, None, nat.ptr(ws), ws.numel(),
+            nat.stream_ptr(Xg.device)))
+        torch.cuda.synchronize()
+        return iters.value, list(trials[:iters.value]), list(acc_lr[:iters.value])
+
+    margins, codes = {}, {}
+    for tag, lr0, maxiter, zero_tensor in (("a", 1.0, 12, True), ("b", 30.0, 6, False)):
+        tr = orc.FistaTrace()
+        orc.fista(X, torch.zeros(n, k), W, 0.3, fast=fast, lr=lr0, maxiter=maxiter, tol=0.0, backtrack=True, trace=tr)
+        if tag == "b":
+            assert min(tr.trials) > 8
+        z0 = torch.zeros(n, k, device="cuda") if zero_tensor else None
+        flat = torch.empty(n, k, device="cuda")
+        wide = torch.full((n, k + pad), sentinel, device="cuda")
+        it_f, trials_f, lr_f = solve(flat, z0, lr0, maxiter)
+        it_w, trials_w, lr_w = solve(wide[:, :k], z0, lr0, maxiter)
+        assert it_w == tr.iterations == maxiter and trials_w == list(tr.trials), (tag, trials_w, list(tr.trials))
+        assert it_f == it_w and trials_f == trials_w and lr_w == lr_f, tag
+        assert torch.equal(wide[:, k:], torch.full((n, pad), sentinel, device="cuda")), tag
+        margins[tag] = (wide[:, :k] - flat).abs().max().item()
+        codes[tag] = (wide[:, :k], flat)
+        print("strided z_out, case (%s), fast=%s: max|dz| against the contiguous solve = %g" % (tag, fast, margins[tag]))
+    record_margins("line_search_strided_z_out_vs_contiguous_fast%d" % int(fast), margins)
+    for tag, (strided, contiguous) in codes.items():
+        assert torch.equal(strided, contiguous), (tag, margins)
