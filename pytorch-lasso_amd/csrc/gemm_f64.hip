@@ -31,6 +31,7 @@
 #include "../../include/lasso_hip.h"
 #include "lasso_kernels.h"
 #include "host_util.hpp"
+#include "stoprule_host.hpp"
 
 namespace lasso {
 namespace f64 {
@@ -359,7 +360,7 @@ const char* solve_kernel_name(int backtrack) {
 }
 
 // Fixed-step solve.  The stop rule (ista.py:93) is read once per chunk of speculated iterations, as the fp32 unfused
-// path does (speculate_stop_rule): every iteration's sum stays on the device as a double, the host compares
+// path does (speculate_stop_rule in stoprule_host.hpp): every iteration's sum stays on the device as a double, the host compares
 // doubles; a stop inside a chunk restores the chunk's head and replays exactly the iterations up to the stop -- the
 // kernels sum in a fixed order, so the replay is bitwise the state the reference stops in.
 int solve(const double* x, int64_t ldx, const double* w, int64_t ldw, const double* z0, int64_t ldz0, double* zout,
@@ -372,7 +373,7 @@ int solve(const double* x, int64_t ldx, const double* w, int64_t ldw, const doub
       (d + kBN - 1) / kBN > 65535)
     return fail(LASSO_ERR_UNSUPPORTED, "shape too large");
   if (int s = start_state(z0, ldz0, zout, ldz, ws.Y, n, k, st)) return s;
-  const double budget = (double)n * (double)k * tol;                       // z0.numel() * tol (ista.py:64)
+  const double budget = stop_budget<double>(n, k, tol);                    // z0.numel() * tol (ista.py:64)
   const double lam = alpha * lr;
   const int64_t parts = prox_parts(n, k);
   Momentum64 mom;
@@ -394,41 +395,21 @@ int solve(const double* x, int64_t ldx, const double* w, int64_t ldw, const doub
     for (; it < maxiter; ++it)
       if (int s = iterate(nullptr)) return s;
   } else {
-    constexpr int kChunkMax = 64;                    // ws.delta holds 64 sums
-    double deltas[kChunkMax];
-    int chunk = 1;
-    while (it < maxiter) {
-      const int c = std::min(chunk, maxiter - it);
-      const Momentum64 head = mom;
-      if (c > 1) {
-        LASSO_HIP_TRY(hipMemcpy2DAsync(ws.G, k * 8, zout, ldz * 8, k * 8, n, hipMemcpyDeviceToDevice, st));
-        LASSO_HIP_TRY(hipMemcpyAsync(ws.Yc, ws.Y, (size_t)n * k * 8, hipMemcpyDeviceToDevice, st));
-      }
-      for (int j = 0; j < c; ++j)
-        if (int s = iterate(ws.delta + j)) return s;
-      LASSO_HIP_TRY(hipMemcpyAsync(deltas, ws.delta, sizeof(double) * c, hipMemcpyDeviceToHost, st));
-      LASSO_HIP_TRY(hipStreamSynchronize(st));
-      int hit = -1;
-      for (int j = 0; j < c && hit < 0; ++j)
-        if (deltas[j] <= budget) hit = j;
-      if (hit < 0) {
-        it += c;
-        last = deltas[c - 1];
-        const int next = next_stop_chunk<double>(deltas[0], last, budget, c, it, kChunkMax);   // (lasso_kernels.h)
-        chunk = std::max(1, next);
-        continue;
-      }
-      last = deltas[hit];
-      if (hit < c - 1) {
-        LASSO_HIP_TRY(hipMemcpy2DAsync(zout, ldz * 8, ws.G, k * 8, k * 8, n, hipMemcpyDeviceToDevice, st));
-        LASSO_HIP_TRY(hipMemcpyAsync(ws.Y, ws.Yc, (size_t)n * k * 8, hipMemcpyDeviceToDevice, st));
-        mom = head;
-        for (int j = 0; j <= hit; ++j)
-          if (int s = iterate(nullptr)) return s;
-      }
-      it += hit + 1;
-      break;
-    }
+    // z's checkpoint at the head of a chunk lives in G, y's in Yc
+    auto save = [&]() -> int {
+      LASSO_HIP_TRY(hipMemcpy2DAsync(ws.G, k * 8, zout, ldz * 8, k * 8, n, hipMemcpyDeviceToDevice, st));
+      LASSO_HIP_TRY(hipMemcpyAsync(ws.Yc, ws.Y, (size_t)n * k * 8, hipMemcpyDeviceToDevice, st));
+      return LASSO_OK;
+    };
+    auto restore = [&]() -> int {
+      LASSO_HIP_TRY(hipMemcpy2DAsync(zout, ldz * 8, ws.G, k * 8, k * 8, n, hipMemcpyDeviceToDevice, st));
+      LASSO_HIP_TRY(hipMemcpyAsync(ws.Y, ws.Yc, (size_t)n * k * 8, hipMemcpyDeviceToDevice, st));
+      return LASSO_OK;
+    };
+    auto read = [&](double* host, int c) -> int { return read_back(host, ws.delta, sizeof(double) * c, st); };
+    if (int s = speculate_stop_rule<double>(maxiter, budget, ws.delta, &mom.t, iterate, save, restore,
+                                            [] { return (int)LASSO_OK; }, read, &it, &last, "lasso_fista_solve_f64"))
+      return s;
   }
   if (iters_out) *iters_out = it;
   if (last_delta_out) *last_delta_out = last;
@@ -449,7 +430,7 @@ int solve_backtracking(const double* x, int64_t ldx, const double* w, int64_t ld
       (d + kBN - 1) / kBN > 65535)
     return fail(LASSO_ERR_UNSUPPORTED, "shape too large");
   if (int s = start_state(z0, ldz0, zout, ldz, ws.Y, n, k, st)) return s;
-  const double budget = (double)n * (double)k * tol;
+  const double budget = stop_budget<double>(n, k, tol);
   bool warned = false;
   Momentum64 mom;
   double last = NAN;

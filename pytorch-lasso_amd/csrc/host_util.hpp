@@ -40,4 +40,11 @@ int fail(int status, const char* fmt, ...);
       return ::lasso::fail(LASSO_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_));    \
   } while (0)
 
+// `bytes` from device memory to the host, and the wait for them: the one read of a chunk's sums or of a kernel's result words
+inline int read_back(void* host, const void* dev, size_t bytes, hipStream_t st) {
+  LASSO_HIP_TRY(hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, st));
+  LASSO_HIP_TRY(hipStreamSynchronize(st));
+  return LASSO_OK;
+}
+
 }  // namespace lasso

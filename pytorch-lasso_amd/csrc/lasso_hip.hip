@@ -17,6 +17,7 @@
 #include "../../include/lasso_hip.h"
 #include "lasso_kernels.h"
 #include "host_util.hpp"
+#include "stoprule_host.hpp"
 
 namespace lasso {
 
@@ -595,15 +596,8 @@ int run_impl(const Workspace& ws, int kp, const float* x, int64_t ldx, const flo
   return LASSO_OK;
 }
 
-// true if the split-k kernel of the launch(es) enqueued so far gave up (a peer workgroup was
-// not resident); synchronises the stream.  The caller then repeats the work with LASSO_KERNEL_TILE.
-int splitk_aborted(const Workspace& ws, hipStream_t stream, bool* aborted) {
-  int hout[4] = {0, 0, 0, 0};
-  LASSO_HIP_TRY(hipMemcpyAsync(hout, ws.stop_out, 16, hipMemcpyDeviceToHost, stream));
-  LASSO_HIP_TRY(hipStreamSynchronize(stream));
-  *aborted = hout[2] != 0;
-  return LASSO_OK;
-}
+// The four result words a kernel that judges the stop rule itself left at `dev` (StopWords, stoprule_host.hpp)
+int read_stop_words(const int* dev, hipStream_t stream, StopWords* words) { return read_back(words->w, dev, 16, stream); }
 
 static PrepareJob prepare_job(const Workspace& ws, int kp, const float* w, int64_t ldw, int64_t d, int64_t k, int coef_cap,
                               const PrepareExtras* extras) {
@@ -750,17 +744,16 @@ int solve_bf16_persistent(const void* x_dev, int64_t ldx, const void* w_dev, int
   p.n = (int)n; p.d = (int)d; p.k = (int)k; p.ntiles = ntiles;
   p.maxiter = maxiter; p.fast = fast; p.backtrack = backtrack;
   p.alpha = alpha; p.lr0 = lr; p.eta = eta;
-  p.budget = tol > 0.0 ? (float)((double)n * (double)k * tol) : -1.0f;
+  p.budget = tol > 0.0 ? stop_budget<float>(n, k, tol) : -1.0f;
   p.coef = ws.pcoef;
   p.gran = ws.pgran;
   p.dgran = reinterpret_cast<unsigned long long*>((char*)ws.pgran + (size_t)8 * ntiles * 32);
   p.out = ws.pout;
   p.trials = ws.ptrials; p.lrs = ws.plrs; p.fvals = ws.pfvals;
   LASSO_HIP_TRY(launch_bt16_persist(p, kp, st));
-  int hout[4] = {0, 0, 0, 0};
-  LASSO_HIP_TRY(hipMemcpyAsync(hout, ws.pout, 16, hipMemcpyDeviceToHost, st));
-  LASSO_HIP_TRY(hipStreamSynchronize(st));
-  if (hout[2]) {                              // some workgroup was not resident: nothing usable was produced
+  StopWords words;
+  if (int s = read_stop_words(ws.pout, st, &words)) return s;
+  if (words.redo()) {                              // some workgroup was not resident: nothing usable was produced
     if (z0_dev && z0_dev == z_out_dev) {
       // z_out was updated in place by the iterations that did complete: restore the start
       LASSO_HIP_TRY(hipMemcpy2DAsync(z_out_dev, ldz * 2, ws.pZ0, k * 2, k * 2, n, hipMemcpyDeviceToDevice, st));
@@ -768,15 +761,15 @@ int solve_bf16_persistent(const void* x_dev, int64_t ldx, const void* w_dev, int
     return LASSO_OK;
   }
   *ran = true;
-  const int its = hout[0];
+  const int its = words.iterations();
   if (iters_out) *iters_out = its;
-  if (last_delta_out) memcpy(last_delta_out, &hout[1], sizeof(float));
+  if (last_delta_out) *last_delta_out = words.last_delta();
   if (backtrack && its > 0 && (trials_out || accepted_lr_out || accepted_f_out)) {
     if (accepted_f_out) LASSO_HIP_TRY(hipMemcpy(accepted_f_out, ws.pfvals, (size_t)its * 4, hipMemcpyDeviceToHost));
     if (trials_out) LASSO_HIP_TRY(hipMemcpy(trials_out, ws.ptrials, (size_t)its * 4, hipMemcpyDeviceToHost));
     if (accepted_lr_out) LASSO_HIP_TRY(hipMemcpy(accepted_lr_out, ws.plrs, (size_t)its * 4, hipMemcpyDeviceToHost));
   }
-  return hout[3] ? fail(LASSO_WARN_LINESEARCH, "backtracking line search failed; reverted to lr0") : LASSO_OK;
+  return words.warned() ? fail(LASSO_WARN_LINESEARCH, "backtracking line search failed; reverted to lr0") : LASSO_OK;
 }
 
 // The start of a solve (ista.py:76-78): z = z0 in zout -- left alone where z0 IS zout, zeros without a z0 -- and then
@@ -1106,7 +1099,7 @@ int solve_backtracking(const void* x_any, int64_t ldx, const void* w_any, int64_
   p.n = (int)n; p.d = (int)d; p.k = (int)k; p.ntiles = ntiles; p.skip = nullptr;
   c.kp = kp; c.grid = std::min(ntiles, cus); c.fast = fast; c.maxiter = maxiter; c.zout = zout; c.ldz = ldz; c.nk = n * k;
   c.alpha = alpha; c.lr0 = lr0; c.eta = eta; c.reduce = reduce; c.reduce_ctx = reduce_ctx; c.st = st;
-  c.stop_budget = tol > 0.0 ? (float)((double)(reduce ? n_global : n) * (double)k * tol) : -1.0f;
+  c.stop_budget = tol > 0.0 ? stop_budget<float>(reduce ? n_global : n, k, tol) : -1.0f;
   c.trace = {trials_out, accepted_lr_out, accepted_f_out};
   // ---- run a window; one whose search ran out of trials is followed by that one iteration on the synchronous path
   int n_first = kBtFirst; bool safety = false;
@@ -1155,7 +1148,7 @@ int solve_fixed_bf16(const void* x_any, int64_t ldx, const void* w_any, int64_t 
   p.Xh = x_any; p.Wq1 = ws.wp; p.Wq2 = ws.wtp;
   p.G = ws.G; p.C = nullptr; p.partials = ws.partials; p.flags = ws.flags; p.fvals = ws.fvals;
   p.n = (int)n; p.d = (int)d; p.k = (int)k; p.ntiles = ntiles;
-  const float budget = (float)((double)n * (double)k * tol);
+  const float budget = stop_budget<float>(n, k, tol);
   const float lr_f = (float)lr, lam = (float)(alpha * lr);
   Momentum mom;
   float last = NAN;
@@ -1176,64 +1169,6 @@ int solve_fixed_bf16(const void* x_any, int64_t ldx, const void* w_any, int64_t 
   LASSO_HIP_TRY(launch_cvt_bf16(Z, k, zout_any, ldz_any, (int)n, (int)k, 0, st));
   if (iters_out) *iters_out = it;
   if (last_delta_out) *last_delta_out = last;
-  return LASSO_OK;
-}
-
-// ---------------------------------------------------------------------------
-// The stop rule of the multi-launch solvers (ista.py:93 / conv2d/ista.py:44-46: the first iteration whose sum
-// |z - z_next| over ALL elements is <= budget ends the solve with that iteration's z) without a host round trip per
-// iteration -- the speculate-and-replay scheme of DESIGN 3.2 at launch granularity: a chunk of <= 64 iterations is
-// enqueued with every iteration's sum kept on the device (`iterate(slot)` leaves it in *slot), the host reads the
-// chunk's sums ONCE; if iteration j of the chunk met the rule and was not the chunk's last, the state goes back to the
-// chunk's head (`save` / `restore`, the momentum scalar *t_mom with it) and exactly j + 1 iterations are replayed --
-// every kernel of these paths sums in a fixed order, so the replay is bitwise the state the reference stops in.
-// ---------------------------------------------------------------------------
-// `flush` puts iterations that `iterate` only queued on the stream (the convolutional solver's many-iterations-per-launch
-// kernel); solvers that launch in `iterate` pass a no-op.
-template <class Iterate, class Save, class Restore, class Flush>
-int speculate_stop_rule(int maxiter, float budget, float* delta_dev, hipStream_t st, double* t_mom, Iterate iterate,
-                        Save save, Restore restore, Flush flush, int* it_out, float* last_out, const char* who) {
-  constexpr int kChunkMax = 64;                    // delta_dev holds 64 sums
-  static const bool trace_chunks = getenv("LASSO_STOP_TRACE") != nullptr;        // the chunks and their verdicts on stderr
-  float deltas[kChunkMax];
-  float last = NAN;
-  int it = 0, chunk = 1;
-  while (it < maxiter) {
-    const int c = std::min(chunk, maxiter - it);
-    const double t_head = *t_mom;
-    if (c > 1)
-      if (int s = save()) return s;
-    for (int j = 0; j < c; ++j)
-      if (int s = iterate(delta_dev + j)) return s;
-    if (int s = flush()) return s;
-    LASSO_HIP_TRY(hipMemcpyAsync(deltas, delta_dev, sizeof(float) * c, hipMemcpyDeviceToHost, st));
-    LASSO_HIP_TRY(hipStreamSynchronize(st));
-    int hit = -1;
-    for (int j = 0; j < c && hit < 0; ++j)
-      if (deltas[j] <= budget) hit = j;                                            // (fp32 compare like the reference)
-    if (trace_chunks)
-      fprintf(stderr, "%s: iterations %d..%d sums %g .. %g budget %g -> %s %d\n", who, it, it + c - 1, (double)deltas[0],
-              (double)deltas[c - 1], (double)budget, hit < 0 ? "no stop" : "stop at", hit < 0 ? 0 : it + hit + 1);
-    if (hit < 0) {
-      it += c;
-      last = deltas[c - 1];
-      const int next = next_stop_chunk<float>(deltas[0], last, budget, c, it, kChunkMax);   // (lasso_kernels.h)
-      chunk = next;
-      continue;
-    }
-    last = deltas[hit];
-    if (hit < c - 1) {
-      if (int s = restore()) return s;
-      *t_mom = t_head;
-      for (int j = 0; j <= hit; ++j)
-        if (int s = iterate(nullptr)) return s;
-      if (int s = flush()) return s;
-    }
-    it += hit + 1;
-    break;
-  }
-  *it_out = it;
-  *last_out = last;
   return LASSO_OK;
 }
 
@@ -1286,7 +1221,7 @@ int solve_generic(const float* x, int64_t ldx, const float* w, int64_t ldw, cons
   if (n > INT32_MAX || d > INT32_MAX || k > INT32_MAX) return fail(LASSO_ERR_UNSUPPORTED, "shape too large");
   LASSO_HIP_TRY(launch_transpose_pad(w, ldw, (int)d, (int)k, ws.Wt, d, (int)k, (int)d, st));
   if (int s = seed_state(z0, ldz0, zout, ldz, ws.Y, n, k, st)) return s;
-  const float budget = (float)((double)n * (double)k * tol);
+  const float budget = stop_budget<float>(n, k, tol);
   const float lr_f = (float)lr, lam = (float)(alpha * lr);
   Momentum mom;
   float last = NAN;
@@ -1309,7 +1244,7 @@ int solve_generic(const float* x, int64_t ldx, const float* w, int64_t ldw, cons
     for (; it < maxiter; ++it)
       if (int s = iterate(nullptr)) return s;
   } else {
-    // the stop rule once per chunk of speculated iterations (speculate_stop_rule above; round 3: a host round trip
+    // the stop rule once per chunk of speculated iterations (speculate_stop_rule, stoprule_host.hpp; round 3: a host round trip
     // per iteration): z's checkpoint lives in G (unused since the proximal step moved into GEMM-2's epilogue), y's in Yc
     const int64_t words = n * k;
     const bool compact = ldz == k && ((uintptr_t)zout & 15) == 0;      // (else the runtime's strided copy)
@@ -1328,8 +1263,9 @@ int solve_generic(const float* x, int64_t ldx, const float* w, int64_t ldw, cons
       LASSO_HIP_TRY(hipGetLastError());
       return LASSO_OK;
     };
-    if (int s = speculate_stop_rule(maxiter, budget, ws.delta, st, &mom.t, iterate, save, restore,
-                                    [] { return (int)LASSO_OK; }, &it, &last, "lasso_fista_solve (unfused)"))
+    auto read = [&](float* host, int c) -> int { return read_back(host, ws.delta, sizeof(float) * c, st); };
+    if (int s = speculate_stop_rule<float>(maxiter, budget, ws.delta, &mom.t, iterate, save, restore,
+                                           [] { return (int)LASSO_OK; }, read, &it, &last, "lasso_fista_solve (unfused)"))
       return s;
   }
   if (iters_out) *iters_out = it;
@@ -1389,7 +1325,7 @@ int solve_generic_backtracking(const float* x, int64_t ldx, const float* w, int6
   BtParams bp;                                             // only what bt_decide_kernel reads
   bp.skip = nullptr;
   bp.partials = ws.part; bp.ntiles = kGenGrid; bp.flags = ws.flags; bp.fvals = ws.fvals;
-  const float budget = (float)((double)(reduce ? n_global : n) * (double)k * tol);
+  const float budget = stop_budget<float>(reduce ? n_global : n, k, tol);
   const BtTrace trace = {trials_out, accepted_lr_out, accepted_f_out};
   bool warned = false;
   Momentum mom;
@@ -1776,15 +1712,221 @@ int lasso_fista_run(const void* x_dev, int64_t ldx, const void* z_in_dev, int64_
                   ldy_out, n, d, k, alpha, lr, fast, it0, iters, delta_dev, st, -1.0f, kernel_hint);
 }
 
+// What lasso_fista_solve decodes, once, from the LASSO_SOLVE_* bits of stop_mode (status_mapped: LASSO_SOLVE_STATUS_MAPPED,
+// the device-writable host words) and from lr = LASSO_LR_AUTO on the fp32 fixed-step path: {lr, alpha*lr} as floats in
+// device memory, lambda_max they are made from, and the Lipschitz workspace whose launches carry the prepare blocks.
+struct SolveAsync { bool async, sharded, one_chunk, defer_verdict; int32_t* status_mapped; };
+struct AutoStep { const float* lr_dev; const double* lip_dev; void* lip_ws; };
+
+// bf16 fixed step without the stop rule: rows are independent, so a batch beyond the persistent kernel's capacity (one
+// resident workgroup per 64-row tile: `cap` = 16384 rows) is a sequence of launches over row blocks of that size instead
+// of the multi-launch kernels (2.7x slower per row).  *ran = false: a block gave up (busy GPU), the caller redoes everything.
+static int solve_bf16_row_blocks(const void* x_dev, int64_t ldx, const void* w_dev, int64_t ldw, const void* z0_dev,
+                                 int64_t ldz0, void* z_out_dev, int64_t ldz, int64_t n, int64_t d, int64_t k, int kp,
+                                 int64_t cap, double alpha, double lr, int fast, int maxiter, double eta_backtrack,
+                                 int32_t* iters_out, void* workspace_dev, size_t workspace_bytes, hipStream_t st,
+                                 bool* ran) {
+  const char* xb = (const char*)x_dev; const char* zb = (const char*)z0_dev; char* ob = (char*)z_out_dev;
+  *ran = true;
+  int64_t r0 = 0;
+  for (; r0 < n; r0 += cap) {
+    const int64_t nb = std::min(cap, n - r0);
+    bool ran_b = false;
+    const void* fb = nullptr;
+    const int sb = solve_bf16_persistent(xb + r0 * ldx * 2, ldx, w_dev, ldw, zb ? zb + r0 * ldz0 * 2 : nullptr, ldz0,
+                                         ob + r0 * ldz * 2, ldz, nb, d, k, kp, alpha, lr, fast, maxiter, 0.0, 0,
+                                         eta_backtrack, nullptr, nullptr, nullptr, nullptr, nullptr, workspace_dev,
+                                         workspace_bytes, st, &ran_b, &fb);
+    if (sb != LASSO_OK) return sb;
+    if (!ran_b) { *ran = false; break; }
+  }
+  if (*ran && iters_out) *iters_out = maxiter;
+  if (!*ran && z0_dev && z0_dev == z_out_dev && r0 > 0)
+    return fail(LASSO_ERR_HIP, "in-place bf16 solve interrupted after %lld rows", (long long)r0);
+  return LASSO_OK;
+}
+
+// The fp32 fixed-step solve on the fused shapes: solve_fixed_f32 carves and prepares, then runs ONE of the four forms of
+// the stop rule below -- or, after the in-kernel rule gave up, a second one.
+struct FixedSolve {
+  const float* x; int64_t ldx; const float* w; int64_t ldw; const float* z0; int64_t ldz0; float* zout; int64_t ldz;
+  int64_t n, d, k;
+  double alpha, lr; int fast, maxiter, hint;
+  int32_t* iters_out; float* last_delta_out; void* workspace_dev; hipStream_t st;
+  const SolveAsync& req; const AutoStep& step;
+  // set by solve_fixed_f32
+  Workspace ws; int kps;
+  float budget;                               // n k tol (ista.py:64), compared in fp32
+  const float* start; int64_t ld_start;       // z0 -- its copy in ws.state[2] where z0 IS zout: intact for a replay / a second attempt
+};
+
+// `iters` iterations from iteration it0 in one run_impl call, with the hint the form runs under
+static int run_fixed(const FixedSolve& c, int hint, const float* z_in, int64_t ldz_in, const float* y_in, int64_t ldy_in,
+                     float* z_out, int64_t ldz_out, float* y_out, int64_t ldy_out, int it0, int iters, float* delta_dev,
+                     float in_kernel_budget, const ChunkVerdict* cv) {
+  return run_impl(c.ws, c.kps, c.x, c.ldx, z_in, ldz_in, y_in, ldy_in, z_out, ldz_out, y_out, ldy_out, c.n, c.d, c.k,
+                  c.alpha, c.lr, c.fast, it0, iters, delta_dev, c.st, in_kernel_budget, hint, nullptr, c.step.lr_dev, cv);
+}
+
+// LASSO_SOLVE_SHARDED: this batch is a row shard -- the rule needs the other ranks' sums.  One chunk, its per-iteration
+// sums left in ws.delta for the caller's all-reduce; lasso_fista_solve_verdict judges them.
+static int solve_sharded_one_chunk(const FixedSolve& c, int stop_mode) {
+  if (!c.req.async || stop_mode != LASSO_STOP_GLOBAL)
+    return fail(LASSO_ERR_BAD_ARG, "LASSO_SOLVE_SHARDED needs LASSO_SOLVE_ASYNC | LASSO_STOP_GLOBAL");
+  if (c.maxiter > kChunkMax)
+    return fail(LASSO_ERR_UNSUPPORTED, "LASSO_SOLVE_SHARDED: maxiter=%d > %d", c.maxiter, kChunkMax);
+  // (y_out = NULL: the one chunk is the whole solve -- a verdict of "redo" repeats it from its start, nothing
+  // continues from its momentum point; round 6: the kernel no longer writes the n x k tile of y nobody reads)
+  if (int s = run_fixed(c, c.hint, c.start, c.ld_start, nullptr, 0, c.zout, c.ldz, nullptr, 0, 0, c.maxiter, c.ws.delta,
+                        -1.0f, nullptr))
+    return s;
+  return LASSO_PENDING;
+}
+
+// The exact global rule in-kernel (every tile has its own resident workgroup; one-iteration lag): a single
+// launch runs to the stopping iteration -- one host sync, at the end (asynchronous: none, the caller collects the words
+// later).  CUs held by OTHER work are invisible to the occupancy query that admitted the grid: then the handshake times
+// out and the kernel aborts as a whole without touching z_out.  *aborted says so: another form repeats the solve.
+static int solve_in_kernel(const FixedSolve& c, bool* aborted) {
+  *aborted = false;
+  // (granule ring and stop_out were zeroed by the prepare launch)
+  if (int s = run_fixed(c, c.hint, c.start, c.ld_start, nullptr, 0, c.zout, c.ldz, nullptr, 0, 0, c.maxiter, nullptr,
+                        c.budget, nullptr))
+    return s;
+  if (c.req.async) return LASSO_PENDING;
+  StopWords words;
+  if (int s = read_stop_words(c.ws.stop_out, c.st, &words)) return s;
+  if ((*aborted = words.redo())) return LASSO_OK;          // some workgroup was not resident
+  if (c.iters_out) *c.iters_out = words.iterations();
+  if (c.last_delta_out) *c.last_delta_out = words.last_delta();
+  return LASSO_OK;
+}
+
+// LASSO_SOLVE_ASYNC beyond the in-kernel rule (more tiles than resident workgroups) when maxiter fits one chunk: the
+// chunk is enqueued, a one-thread kernel turns its per-iteration deltas into the words the collect call copies --
+// {iterations, last delta, redo} -- and the call returns without waiting.  "redo" is set when the rule fired BEFORE the
+// last iteration (z_out is then a later iterate): the caller repeats the solve synchronously, as after an aborted
+// handshake.  The E-step of an EM loop (maxiter = 10) practically never stops early, and no longer waits for the host.
+static int solve_async_one_chunk(const FixedSolve& c, int hint) {
+  // LASSO_SOLVE_DEFER_VERDICT: the verdict launch is left to lasso_fista_solve_verdict_deferred (another stream)
+  const bool defer = c.req.defer_verdict && c.req.status_mapped && c.maxiter <= 64 && c.n > 0;
+  t_deferred_verdict.armed = false;
+  t_deferred_verdict.workspace = c.workspace_dev;
+  const ChunkVerdict cv{c.budget, c.ws.stop_out, c.req.status_mapped, defer ? &t_deferred_verdict : nullptr};
+  if (int s = run_fixed(c, hint, c.start, c.ld_start, nullptr, 0, c.zout, c.ldz, nullptr, 0, 0, c.maxiter, c.ws.delta,
+                        -1.0f, &cv))
+    return s;
+  if (c.maxiter > 64 || c.n == 0) {
+    hipLaunchKernelGGL(chunk_verdict_kernel, dim3(1), dim3(1), 0, c.st, c.ws.delta, c.maxiter, c.budget, c.ws.stop_out,
+                       c.req.status_mapped);
+    LASSO_HIP_TRY(hipGetLastError());
+  }
+  if (defer && t_deferred_verdict.armed) return LASSO_PENDING_DEFERRED;
+  return c.req.status_mapped ? LASSO_PENDING_MAPPED : LASSO_PENDING;
+}
+
+// The exact global rule, chunked: speculate a chunk, read its per-iteration deltas, replay the chunk up to the stopping
+// iteration if one fired.  The state ping-pongs between two pairs of workspace buffers, so a chunk's
+// input stays intact for its replay without a copy (run_impl takes in / out state pointers: speculate_stop_rule's save /
+// restore would add launches here).
+static int solve_chunked(const FixedSolve& c, int hint) {
+  const float* cur_z = c.start, * cur_y = nullptr;
+  int64_t cur_ldz = c.ld_start, cur_ldy = 0;
+  int done = 0, flip = 0, next_chunk = kChunkMax;
+  float hdelta[kChunkMax], last = NAN;
+  while (done < c.maxiter) {
+    const int cn = std::min(next_chunk, c.maxiter - done);
+    const bool final_chunk = (done + cn == c.maxiter);
+    float* nz = final_chunk ? c.zout : c.ws.state[2 * flip];
+    const int64_t nldz = final_chunk ? c.ldz : c.k;
+    float* ny = c.ws.state[2 * flip + 1];
+    // the aliasing copy used state[2]; first chunk writes state[0]/[1] (flip = 0)
+    if (int s = run_fixed(c, hint, cur_z, cur_ldz, cur_y, cur_ldy, nz, nldz, ny, c.k, done, cn, c.ws.delta, -1.0f, nullptr))
+      return s;
+    if (int s = read_back(hdelta, c.ws.delta, cn * sizeof(float), c.st)) return s;
+    const int hit = first_stop<float>(hdelta, cn, c.budget);
+    if (hit >= 0) {
+      if (hit + 1 < cn) {   // replay the chunk from its (intact) input state
+        if (int s = run_fixed(c, hint, cur_z, cur_ldz, cur_y, cur_ldy, c.zout, c.ldz, nullptr, 0, done, hit + 1, nullptr,
+                              -1.0f, nullptr))
+          return s;
+      } else if (!final_chunk) {
+        LASSO_HIP_TRY(hipMemcpy2DAsync(c.zout, c.ldz * 4, nz, nldz * 4, c.k * 4, c.n, hipMemcpyDeviceToDevice, c.st));
+      }
+      done += hit + 1;
+      last = hdelta[hit];
+      break;
+    }
+    done += cn;
+    last = hdelta[cn - 1];
+    cur_z = nz; cur_ldz = nldz; cur_y = ny; cur_ldy = c.k;
+    flip ^= 1;
+    next_chunk = next_tile_chunk(hdelta, cn, c.budget, kChunkMax);       // (scheduling only: stoprule_host.hpp)
+  }
+  if (c.iters_out) *c.iters_out = done;
+  if (c.last_delta_out) *c.last_delta_out = last;
+  return LASSO_OK;
+}
+
+static int solve_fixed_f32(FixedSolve& c, double tol, int stop_mode, bool stop_rule, size_t workspace_bytes) {
+  const int64_t n = c.n, d = c.d, k = c.k;
+  const int kps = c.kps = pad_k_solve(n, d, k);          // (768 atoms have their own tile kernel)
+  // (a thread-local that pad_d reads: alive across every run_impl, plan_tiles and pad_d call of the solve)
+  const NarrowTiles narrow(narrow_tiles(n, d, k, kps, c.hint));
+  c.ws = carve(c.workspace_dev, n, k, kps, c.maxiter, stop_rule);
+  const Workspace& ws = c.ws;
+  if (workspace_bytes < ws.bytes)
+    return fail(LASSO_ERR_WORKSPACE, "workspace %zu < %zu bytes", workspace_bytes, ws.bytes);
+  // one launch: pack W, momentum table, {lr, alpha*lr} from lambda_max, the zeroing of the in-kernel rule's ring and words
+  PrepareExtras px = {nullptr, 0, nullptr, 0, c.step.lip_dev, c.alpha, const_cast<float*>(c.step.lr_dev)};
+  const TilePlan tp = plan_tiles(n, pad_d(d, kps), kps);
+  if (stop_rule && stop_mode == LASSO_STOP_GLOBAL) {
+    px.zero_a = ws.gran; px.words_a = kStopRing * std::max(tp.ntiles, kSplitMaxParts);
+    px.zero_b = reinterpret_cast<unsigned long long*>(ws.stop_out); px.words_b = 2;
+  }
+  // (lr = LASSO_LR_AUTO: the Lipschitz launches were left to this point -- their Gram launch carries the prepare blocks)
+  if (c.step.lip_ws) {
+    if (int s = prepare_with_lipschitz(ws, kps, c.w, c.ldw, d, k, c.maxiter, c.st, px, c.step.lip_ws)) return s;
+  } else if (int s = prepare_impl(ws, kps, c.w, c.ldw, d, k, c.maxiter, c.st, &px)) return s;
+
+  if (!stop_rule) {
+    if (int s = run_fixed(c, c.hint, c.z0, c.ldz0, nullptr, 0, c.zout, c.ldz, nullptr, 0, 0, c.maxiter, nullptr, -1.0f, nullptr))
+      return s;
+    if (c.iters_out) *c.iters_out = c.maxiter;
+    return LASSO_OK;
+  }
+
+  c.budget = stop_budget<float>(n, k, tol);
+  const bool aliased = c.z0 && c.z0 == c.zout;
+  c.start = c.z0; c.ld_start = c.ldz0;
+  if (aliased) {              // keep the initial state intact for a replay / a second attempt
+    LASSO_HIP_TRY(hipMemcpy2DAsync(ws.state[2], k * 4, c.z0, c.ldz0 * 4, k * 4, n, hipMemcpyDeviceToDevice, c.st));
+    c.start = ws.state[2]; c.ld_start = k;
+  }
+  if (c.req.sharded) return solve_sharded_one_chunk(c, stop_mode);
+  // an asynchronous solve whose maxiter fits one chunk can leave the verdict to the device
+  const bool fits_one_chunk = c.req.async && stop_mode == LASSO_STOP_GLOBAL && c.maxiter <= kChunkMax && !aliased;
+  int hint = c.hint;
+  // (LASSO_SOLVE_ONE_CHUNK: all `maxiter` iterations are expected to run -- the plain kernels + the device verdict are
+  // cheaper per iteration than the in-kernel rule's exchange, whose granule fetch covers 256 tiles: four per lane of a wave)
+  if (stop_mode == LASSO_STOP_GLOBAL && !(c.req.one_chunk && fits_one_chunk) &&
+      tp.ntiles <= std::min(fista_resident_workgroups(kps, pad_d(d, kps), tp.waves), 256)) {
+    bool aborted = false;
+    const int s = solve_in_kernel(c, &aborted);
+    if (!aborted) return s;
+    hint = LASSO_KERNEL_TILE;      // no cross-workgroup traffic from here on
+  }
+  if (fits_one_chunk) return solve_async_one_chunk(c, hint);
+  return solve_chunked(c, hint);
+}
+
 static int solve_impl(const void* x_dev, int64_t ldx, const void* w_dev, int64_t ldw,
                       const void* z0_dev, int64_t ldz0, void* z_out_dev, int64_t ldz, int64_t n,
                       int64_t d, int64_t k, int dtype, double alpha, double lr, int fast,
                       int maxiter, double tol, int stop_mode, int backtrack, double eta_backtrack,
                       int32_t* iters_out, float* last_delta_out, int32_t* trials_out,
                       float* accepted_lr_out, float* accepted_f_out, void* workspace_dev,
-                      size_t workspace_bytes, void* stream, const float* lr_dev = nullptr, bool async = false,
-                      const double* lip_dev = nullptr, bool sharded = false, bool one_chunk = false,
-                      int32_t* status_mapped = nullptr, void* lip_deferred_ws = nullptr, bool defer_verdict = false) {
+                      size_t workspace_bytes, void* stream, const SolveAsync& req, const AutoStep& step) {
   // LASSO_BF16 (x, W, z0, z_out all bf16) is native on the fused shapes
   const bool half_any = dtype == LASSO_BF16 && fused_shape(d, k) && maxiter > 0 && n > 0;
   const bool half_bt = half_any && backtrack;
@@ -1824,7 +1966,7 @@ static int solve_impl(const void* x_dev, int64_t ldx, const void* w_dev, int64_t
     return solve_generic_backtracking(x, ldx, (const float*)w_dev, ldw, z0, ldz0, zout, ldz, n, d, k, alpha, lr, fast,
                                       maxiter, stop_rule ? tol : 0.0, eta_backtrack, iters_out, last_delta_out,
                                       trials_out, accepted_lr_out, accepted_f_out, workspace_dev, workspace_bytes, st);
-  if (!fused_shape(d, k) || (want_unfused && !backtrack && dtype == LASSO_F32 && !lr_dev && !async))
+  if (!fused_shape(d, k) || (want_unfused && !backtrack && dtype == LASSO_F32 && !step.lr_dev && !req.async))
     return solve_generic(x, ldx, (const float*)w_dev, ldw, z0, ldz0, zout, ldz, n, d, k, alpha, lr, fast,
                          maxiter, stop_rule ? tol : 0.0, iters_out, last_delta_out, workspace_dev,
                          workspace_bytes, st);
@@ -1837,30 +1979,12 @@ static int solve_impl(const void* x_dev, int64_t ldx, const void* w_dev, int64_t
     int per_cu = 0;
     const int64_t cap = bt16_persist_occupancy(kp, &per_cu) == hipSuccess ? (int64_t)per_cu * device_cus() * 64 : 0;
     if (!backtrack && !stop_rule && cap > 0 && n > cap) {
-      // Fixed step without the stop rule: rows are independent, so a batch beyond the persistent kernel's capacity
-      // (one resident workgroup per 64-row tile: 16384 rows) is a sequence of launches over row blocks of that size
-      // instead of the multi-launch kernels (2.7x slower per row).  With the stop rule or the line search the
-      // decisions need sums over ALL rows at once -- those keep the multi-launch path.
-      const char* xb = (const char*)x_dev; const char* zb = (const char*)z0_dev; char* ob = (char*)z_out_dev;
-      bool all = true;
-      int64_t r0 = 0;
-      for (; r0 < n; r0 += cap) {
-        const int64_t nb = std::min(cap, n - r0);
-        bool ran_b = false;
-        const void* fb = nullptr;
-        const int sb = solve_bf16_persistent(xb + r0 * ldx * 2, ldx, w_dev, ldw, zb ? zb + r0 * ldz0 * 2 : nullptr, ldz0,
-                                             ob + r0 * ldz * 2, ldz, nb, d, k, kp, alpha, lr, fast, maxiter, 0.0, 0,
-                                             eta_backtrack, nullptr, nullptr, nullptr, nullptr, nullptr, workspace_dev,
-                                             workspace_bytes, st, &ran_b, &fb);
-        if (sb != LASSO_OK) return sb;
-        if (!ran_b) { all = false; break; }       // a block gave up (busy GPU): the multi-launch path redoes everything
-      }
-      if (all) {
-        if (iters_out) *iters_out = maxiter;
-        return LASSO_OK;
-      }
-      if (z0_dev && z0_dev == z_out_dev && r0 > 0)
-        return fail(LASSO_ERR_HIP, "in-place bf16 solve interrupted after %lld rows", (long long)r0);
+      // (with the stop rule or the line search the decisions need sums over ALL rows at once: the multi-launch path)
+      bool all = false;
+      if (int sb = solve_bf16_row_blocks(x_dev, ldx, w_dev, ldw, z0_dev, ldz0, z_out_dev, ldz, n, d, k, kp, cap, alpha, lr,
+                                         fast, maxiter, eta_backtrack, iters_out, workspace_dev, workspace_bytes, st, &all))
+        return sb;
+      if (all) return LASSO_OK;
     } else {
     const int s = solve_bf16_persistent(x_dev, ldx, w_dev, ldw, z0_dev, ldz0, z_out_dev, ldz, n, d, k, kp, alpha, lr,
                                         fast, maxiter, stop_rule ? tol : 0.0, backtrack, eta_backtrack, iters_out,
@@ -1884,174 +2008,10 @@ static int solve_impl(const void* x_dev, int64_t ldx, const void* w_dev, int64_t
                               // A/B knobs of the fp32 line search: TILE = one trial per launch, SPLITK = round 4's
                               // multi-launch form (gradient / trials / accept as separate launches)
                               (hint & 0x300) == LASSO_KERNEL_TILE ? 1 : (hint & 0x300) == LASSO_KERNEL_SPLITK ? 2 : 0);
-  const int kps = pad_k_solve(n, d, k);                  // (fp32 fixed step from here on: 768 atoms have their own tile kernel)
-  const NarrowTiles narrow(narrow_tiles(n, d, k, kps, hint));
-  Workspace ws = carve(workspace_dev, n, k, kps, maxiter, stop_rule);
-  if (workspace_bytes < ws.bytes)
-    return fail(LASSO_ERR_WORKSPACE, "workspace %zu < %zu bytes", workspace_bytes, ws.bytes);
-  // one launch: pack W, momentum table, {lr, alpha*lr} from lambda_max (lr = LASSO_LR_AUTO), and the
-  // zeroing of the in-kernel stop rule's granule ring and result words
-  PrepareExtras px = {nullptr, 0, nullptr, 0, lip_dev, alpha, const_cast<float*>(lr_dev)};
-  const TilePlan tp0 = plan_tiles(n, pad_d(d, kps), kps);
-  if (stop_rule && stop_mode == LASSO_STOP_GLOBAL) {
-    px.zero_a = ws.gran; px.words_a = kStopRing * std::max(tp0.ntiles, kSplitMaxParts);
-    px.zero_b = reinterpret_cast<unsigned long long*>(ws.stop_out); px.words_b = 2;
-  }
-  // (lr = LASSO_LR_AUTO: the Lipschitz launches were left to this point -- their Gram launch carries the prepare blocks)
-  if (lip_deferred_ws) {
-    if (int s = prepare_with_lipschitz(ws, kps, (const float*)w_dev, ldw, d, k, maxiter, st, px, lip_deferred_ws)) return s;
-  } else if (int s = prepare_impl(ws, kps, (const float*)w_dev, ldw, d, k, maxiter, st, &px)) return s;
-
-  if (!stop_rule) {
-    if (int s = run_impl(ws, kps, x, ldx, z0, ldz0, nullptr, 0, zout, ldz, nullptr, 0, n, d, k,
-                         alpha, lr, fast, 0, maxiter, nullptr, st, -1.0f, hint, nullptr, lr_dev))
-      return s;
-    if (iters_out) *iters_out = maxiter;
-    return LASSO_OK;
-  }
-
-  const float budget = (float)((double)n * (double)k * tol);   // ista.py:64, compared in fp32
-  // ---- exact global stop rule, in-kernel: when every tile has its own resident workgroup
-  // the persistent kernel evaluates the rule itself (one-iteration lag) and a
-  // single launch runs to the stopping iteration -- one host sync, at the end. ------------
-  const float* cur_z = z0;  int64_t cur_ldz = ldz0;
-  const float* cur_y = nullptr; int64_t cur_ldy = 0;
-  if (z0 && z0 == zout) {     // aliasing: keep the initial state intact for a replay / a second attempt
-    LASSO_HIP_TRY(hipMemcpy2DAsync(ws.state[2], k * 4, z0, ldz0 * 4, k * 4, n, hipMemcpyDeviceToDevice, st));
-    cur_z = ws.state[2]; cur_ldz = k;
-  }
-  if (sharded) {
-    // LASSO_SOLVE_SHARDED: this batch is a row shard -- the rule needs the other ranks' sums.  One chunk, its
-    // per-iteration sums left in ws.delta for the caller's all-reduce; lasso_fista_solve_verdict judges them.
-    if (!async || stop_mode != LASSO_STOP_GLOBAL)
-      return fail(LASSO_ERR_BAD_ARG, "LASSO_SOLVE_SHARDED needs LASSO_SOLVE_ASYNC | LASSO_STOP_GLOBAL");
-    if (maxiter > kChunkMax)
-      return fail(LASSO_ERR_UNSUPPORTED, "LASSO_SOLVE_SHARDED: maxiter=%d > %d", maxiter, kChunkMax);
-    // (y_out = NULL: the one chunk is the whole solve -- a verdict of "redo" repeats it from its start, nothing
-    // continues from its momentum point; round 6: the kernel no longer writes the n x k tile of y nobody reads)
-    if (int s = run_impl(ws, kps, x, ldx, cur_z, cur_ldz, nullptr, 0, zout, ldz, nullptr, 0, n, d, k,
-                         alpha, lr, fast, 0, maxiter, ws.delta, st, -1.0f, hint, nullptr, lr_dev))
-      return s;
-    return LASSO_PENDING;
-  }
-  if (stop_mode == LASSO_STOP_GLOBAL) {
-    const TilePlan tp = plan_tiles(n, pad_d(d, kps), kps);
-    const int ntiles = tp.ntiles;
-    // The handshake needs every workgroup of the grid resident at once: one workgroup per CU
-    // (LDS-bound), so the grid must not exceed what the occupancy query admits.  CUs held by
-    // OTHER work (a second stream, another process) are invisible to that query: then the
-    // handshake times out, the kernel aborts as a whole without touching z_out, and the solve
-    // is repeated on the chunked path below.
-    // (the rule's granule fetch covers 256 tiles: four per lane of one wave)
-    // (LASSO_SOLVE_ONE_CHUNK: the caller expects all `maxiter` iterations to run -- the plain kernels + the device
-    // verdict below are cheaper per iteration than the in-kernel rule's exchange)
-    const bool as_chunk = one_chunk && async && maxiter <= kChunkMax && !(z0 && z0 == zout);
-    if (!as_chunk && ntiles <= std::min(fista_resident_workgroups(kps, pad_d(d, kps), tp.waves), 256)) {
-      // (granule ring and stop_out were zeroed by the prepare launch)
-      if (int s = run_impl(ws, kps, x, ldx, cur_z, cur_ldz, nullptr, 0, zout, ldz, nullptr, 0, n, d, k,
-                           alpha, lr, fast, 0, maxiter, nullptr, st, budget, hint, nullptr, lr_dev))
-        return s;
-      if (async) return LASSO_PENDING;     // the caller collects {iterations, last delta, abort flag} later
-      int hout[4] = {0, 0, 0, 0};
-      LASSO_HIP_TRY(hipMemcpyAsync(hout, ws.stop_out, 16, hipMemcpyDeviceToHost, st));
-      LASSO_HIP_TRY(hipStreamSynchronize(st));
-      if (!hout[2]) {
-        float lastf;
-        memcpy(&lastf, &hout[1], sizeof(float));
-        if (iters_out) *iters_out = hout[0];
-        if (last_delta_out) *last_delta_out = lastf;
-        return LASSO_OK;
-      }
-      hint = LASSO_KERNEL_TILE;      // some workgroup was not resident: no cross-workgroup traffic from here on
-    }
-  }
-  // ---- LASSO_SOLVE_ASYNC beyond the in-kernel rule (more tiles than resident workgroups) when maxiter fits
-  // one chunk: the chunk is enqueued, a one-thread kernel turns its per-iteration deltas into the words the
-  // collect call copies -- {iterations, last delta, redo} -- and the call returns without waiting.  "redo" is
-  // set when the rule fired BEFORE the last iteration (z_out is then one of the later iterates): the caller
-  // repeats the solve synchronously, exactly like after an aborted handshake.  The E-step of an EM loop
-  // (maxiter = 10) practically never stops early, and no longer makes the GPU wait for the host. -------------
-  if (async && stop_mode == LASSO_STOP_GLOBAL && maxiter <= kChunkMax && !(z0 && z0 == zout)) {
-    // LASSO_SOLVE_DEFER_VERDICT: the verdict launch is left to lasso_fista_solve_verdict_deferred (another stream)
-    const bool defer = defer_verdict && status_mapped && maxiter <= 64 && n > 0;
-    t_deferred_verdict.armed = false;
-    t_deferred_verdict.workspace = workspace_dev;
-    const ChunkVerdict cv{budget, ws.stop_out, status_mapped, defer ? &t_deferred_verdict : nullptr};
-    if (int s = run_impl(ws, kps, x, ldx, cur_z, cur_ldz, nullptr, 0, zout, ldz, nullptr, 0, n, d, k,
-                         alpha, lr, fast, 0, maxiter, ws.delta, st, -1.0f, hint, nullptr, lr_dev, &cv))
-      return s;
-    if (maxiter > 64 || n == 0) {
-      hipLaunchKernelGGL(chunk_verdict_kernel, dim3(1), dim3(1), 0, st, ws.delta, maxiter, budget, ws.stop_out,
-                         status_mapped);
-      LASSO_HIP_TRY(hipGetLastError());
-    }
-    if (defer && t_deferred_verdict.armed) return LASSO_PENDING_DEFERRED;
-    return status_mapped ? LASSO_PENDING_MAPPED : LASSO_PENDING;
-  }
-  // ---- exact global stop rule, chunked: speculate a chunk, read its per-iteration deltas,
-  // replay the chunk up to the stopping iteration if one fired ----------
-  int done = 0, flip = 0;
-  std::vector<float> hdelta(kChunkMax);
-  float last = NAN;
-  int next_chunk = kChunkMax;
-  while (done < maxiter) {
-    const int c = std::min(next_chunk, maxiter - done);
-    const bool final_chunk = (done + c == maxiter);
-    float* nz = final_chunk ? zout : ws.state[2 * flip];
-    const int64_t nldz = final_chunk ? ldz : k;
-    float* ny = ws.state[2 * flip + 1];
-    // the aliasing copy above used state[2]; first chunk writes state[0]/[1] (flip = 0)
-    if (int s = run_impl(ws, kps, x, ldx, cur_z, cur_ldz, cur_y, cur_ldy, nz, nldz, ny, k, n, d, k,
-                         alpha, lr, fast, done, c, ws.delta, st, -1.0f, hint, nullptr, lr_dev))
-      return s;
-    LASSO_HIP_TRY(hipMemcpyAsync(hdelta.data(), ws.delta, c * sizeof(float), hipMemcpyDeviceToHost, st));
-    LASSO_HIP_TRY(hipStreamSynchronize(st));
-    int hit = -1;
-    for (int i = 0; i < c; ++i) {
-      last = hdelta[i];
-      if (hdelta[i] <= budget) { hit = i; break; }
-    }
-    if (hit >= 0) {
-      if (hit + 1 < c) {   // replay the chunk from its (intact) input state
-        if (int s = run_impl(ws, kps, x, ldx, cur_z, cur_ldz, cur_y, cur_ldy, zout, ldz, nullptr, 0,
-                             n, d, k, alpha, lr, fast, done, hit + 1, nullptr, st, -1.0f, hint, nullptr, lr_dev))
-          return s;
-      } else if (!final_chunk) {
-        LASSO_HIP_TRY(hipMemcpy2DAsync(zout, ldz * 4, nz, nldz * 4, k * 4, n, hipMemcpyDeviceToDevice, st));
-      }
-      done += hit + 1;
-      if (iters_out) *iters_out = done;
-      if (last_delta_out) *last_delta_out = last;
-      return LASSO_OK;
-    }
-    done += c;
-    cur_z = nz; cur_ldz = nldz; cur_y = ny; cur_ldy = k;
-    flip ^= 1;
-    // Size the next speculative chunk from the decay of the deltas seen so far (purely a
-    // scheduling heuristic -- the stop decision itself stays exact): estimate the
-    // iterations left until delta <= budget from the geometric decay over the chunk and
-    // approach the predicted stop with short chunks so that little work is wasted or replayed.
-    next_chunk = kChunkMax;
-    if (c >= 8 && budget > 0.0f) {
-      const int h = c / 2;
-      float hi = 0.0f, lo = 0.0f;
-      for (int i = 0; i < h; ++i) hi = std::max(hi, hdelta[i]);
-      for (int i = h; i < c; ++i) lo = std::max(lo, hdelta[i]);
-      if (lo > budget && hi > lo) {
-        const double rate = log((double)hi / lo) / h;              // per-iteration log decay
-        const double left = log((double)lo / budget) / rate;       // iterations still needed
-        if (left < 2.0 * kChunkMax) {
-          const int guess = (int)left - 6;
-          next_chunk = guess >= kChunkMax ? kChunkMax : std::max(8, std::min(guess, kChunkMax));
-        }
-      } else if (lo <= budget * 4.0f) {
-        next_chunk = 8;
-      }
-    }
-  }
-  if (iters_out) *iters_out = done;
-  if (last_delta_out) *last_delta_out = last;
-  return LASSO_OK;
+  // fp32 fixed step from here on
+  FixedSolve c{x, ldx, (const float*)w_dev, ldw, z0, ldz0, zout, ldz, n, d, k, alpha, lr, fast, maxiter, hint, iters_out,
+               last_delta_out, workspace_dev, st, req, step};
+  return solve_fixed_f32(c, tol, stop_mode, stop_rule, workspace_bytes);
 }
 
 // float64 tensors: see lasso_fista_solve_f64 in include/lasso_hip.h
@@ -2143,27 +2103,22 @@ int lasso_fista_solve(const void* x_dev, int64_t ldx, const void* w_dev, int64_t
     return status;
   }
   if (objective_out) *objective_out = NAN;
-  const bool async = (stop_mode & LASSO_SOLVE_ASYNC) != 0;
-  const bool sharded = (stop_mode & LASSO_SOLVE_SHARDED) != 0;
-  const bool one_chunk = (stop_mode & LASSO_SOLVE_ONE_CHUNK) != 0;
-  int32_t* status_mapped = nullptr;
+  SolveAsync req = {(stop_mode & LASSO_SOLVE_ASYNC) != 0, (stop_mode & LASSO_SOLVE_SHARDED) != 0,
+                    (stop_mode & LASSO_SOLVE_ONE_CHUNK) != 0, (stop_mode & LASSO_SOLVE_DEFER_VERDICT) != 0, nullptr};
   if (stop_mode & LASSO_SOLVE_STATUS_MAPPED) {      // iters_out is a device-writable host buffer of four words
-    if (!async || !iters_out) return fail(LASSO_ERR_BAD_ARG, "LASSO_SOLVE_STATUS_MAPPED needs LASSO_SOLVE_ASYNC and iters_out");
-    status_mapped = iters_out;
+    if (!req.async || !iters_out) return fail(LASSO_ERR_BAD_ARG, "LASSO_SOLVE_STATUS_MAPPED needs LASSO_SOLVE_ASYNC and iters_out");
+    req.status_mapped = iters_out;
     iters_out = nullptr; last_delta_out = nullptr;
   }
-  const bool defer_verdict = (stop_mode & LASSO_SOLVE_DEFER_VERDICT) != 0;
-  if (defer_verdict && (!(status_mapped && one_chunk) || sharded))
+  if (req.defer_verdict && (!(req.status_mapped && req.one_chunk) || req.sharded))
     return fail(LASSO_ERR_BAD_ARG, "LASSO_SOLVE_DEFER_VERDICT needs LASSO_SOLVE_STATUS_MAPPED and LASSO_SOLVE_ONE_CHUNK, without LASSO_SOLVE_SHARDED");
   stop_mode &= ~(LASSO_SOLVE_ASYNC | LASSO_SOLVE_SHARDED | LASSO_SOLVE_ONE_CHUNK | LASSO_SOLVE_STATUS_MAPPED |
                  LASSO_SOLVE_DEFER_VERDICT);
-  if (sharded && !(async && tol > 0.0 && maxiter > 0 && n > 0 && fused_shape(d, k)))
+  if (req.sharded && !(req.async && tol > 0.0 && maxiter > 0 && n > 0 && fused_shape(d, k)))
     return fail(LASSO_ERR_UNSUPPORTED, "LASSO_SOLVE_SHARDED: asynchronous fp32 solves with tol > 0 on the fused shapes only");
-  if (async && (objective_out || backtrack || dtype != LASSO_F32))
+  if (req.async && (objective_out || backtrack || dtype != LASSO_F32))
     return fail(LASSO_ERR_BAD_ARG, "LASSO_SOLVE_ASYNC: fp32 fixed-step solves without objective_out only");
-  const float* lr_dev = nullptr;
-  const double* lip_dev = nullptr;
-  void* lip_deferred = nullptr;
+  AutoStep step = {nullptr, nullptr, nullptr};
   if (lr == LASSO_LR_AUTO) {
     // lr = 1/L, L = lambda_max(W^T W) (ista.py:72-73, :8-14) computed here on the stream.  The fp32
     // fixed-step kernels read {lr, alpha*lr} from device memory -- no host round trip; the other
@@ -2179,9 +2134,9 @@ int lasso_fista_solve(const void* x_dev, int64_t ldx, const void* w_dev, int64_t
     char* const lip_ws = (char*)workspace_dev + before;
     if (fused_shape(d, k) && !backtrack && maxiter > 0 && n > 0) {
       float* const slot = (float*)(lip_ws + reg.lipschitz - 256);
-      lip_dev = (const double*)lip_ws;                 // solve_impl enqueues the Lipschitz launches with its prepare blocks;
-      lip_deferred = lip_ws;                           //   the launch that finishes lambda_max fills the slot
-      lr_dev = slot;
+      // solve_fixed_f32 enqueues the Lipschitz launches with its prepare blocks; the launch that finishes lambda_max
+      // fills the slot
+      step = {slot, (const double*)lip_ws, lip_ws};
       lr = 1.0;                                        // placeholder, never used by the kernels
     } else {
       LASSO_HIP_TRY(launch_lipschitz((const float*)w_dev, ldw, d, k, lip_ws, 20, st));
@@ -2194,8 +2149,7 @@ int lasso_fista_solve(const void* x_dev, int64_t ldx, const void* w_dev, int64_t
   const int status = solve_impl(x_dev, ldx, w_dev, ldw, z0_dev, ldz0, z_out_dev, ldz, n, d, k, dtype, alpha, lr,
                                 fast, maxiter, tol, stop_mode, backtrack, eta_backtrack, iters_out,
                                 last_delta_out, trials_out, accepted_lr_out, accepted_f_out, workspace_dev,
-                                workspace_bytes, stream, lr_dev, async, lip_dev, sharded, one_chunk, status_mapped, lip_deferred,
-                                defer_verdict);
+                                workspace_bytes, stream, req, step);
   if ((status != LASSO_OK && status != LASSO_WARN_LINESEARCH) || !objective_out || n <= 0) return status;
   // objective_out: (0.5*||x - z W^T||^2 + alpha*||z||_1)/n of the RETURNED code, evaluated in fp32
   // (the verbose print of ista.py:66-69,80-81 for the final iterate; dict_learning.py:10-13)
@@ -2290,7 +2244,7 @@ static int solve_verdict_impl(int64_t n, int64_t n_global, int64_t d, int64_t k,
     return fail(LASSO_ERR_BAD_ARG, "no pending sharded solve of this shape");
   Workspace ws = carve(workspace_dev, n, k, pad_k_solve(n, d, k), maxiter, true);
   if (!workspace_dev || workspace_bytes < ws.bytes) return fail(LASSO_ERR_WORKSPACE, "need %zu bytes", ws.bytes);
-  const float budget = (float)((double)n_global * (double)k * tol);   // ista.py:64 on the whole batch
+  const float budget = stop_budget<float>(n_global, k, tol);   // ista.py:64 on the whole batch
   hipLaunchKernelGGL(chunk_verdict_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, sums_dev ? sums_dev : ws.delta,
                      maxiter, budget, ws.stop_out, status_mapped);
   LASSO_HIP_TRY(hipGetLastError());
@@ -2337,20 +2291,16 @@ int lasso_fista_solve_finish(int64_t n, int64_t d, int64_t k, int dtype, int max
   const int kp = pad_k_solve(n, d, k);
   Workspace ws = carve(workspace_dev, n, k, kp, maxiter, true);
   if (!workspace_dev || workspace_bytes < ws.bytes) return fail(LASSO_ERR_WORKSPACE, "need %zu bytes", ws.bytes);
-  hipStream_t st = (hipStream_t)stream;
-  int hout[4] = {0, 0, 0, 0};
-  LASSO_HIP_TRY(hipMemcpyAsync(hout, ws.stop_out, 16, hipMemcpyDeviceToHost, st));
-  LASSO_HIP_TRY(hipStreamSynchronize(st));
-  if (hout[2]) {
+  StopWords words;
+  if (int s = read_stop_words(ws.stop_out, (hipStream_t)stream, &words)) return s;
+  if (words.redo()) {
     if (iters_out) *iters_out = 0;
     if (last_delta_out) *last_delta_out = NAN;
     snprintf(g_err, sizeof(g_err), "asynchronous solve must be repeated (handshake gave up, or the rule fired before the end of the chunk)");
     return LASSO_WARN_ABORTED;
   }
-  float lastf;
-  memcpy(&lastf, &hout[1], sizeof(float));
-  if (iters_out) *iters_out = hout[0];
-  if (last_delta_out) *last_delta_out = lastf;
+  if (iters_out) *iters_out = words.iterations();
+  if (last_delta_out) *last_delta_out = words.last_delta();
   return LASSO_OK;
 }
 
@@ -3213,7 +3163,7 @@ int lasso_conv_ista_solve(const void* x_dev, const void* w_dev, const void* z0_d
     LASSO_HIP_TRY(hipMemsetAsync(ws.Zm, 0, (size_t)M * g.K * 4, st));
     LASSO_HIP_TRY(hipMemsetAsync(ws.Ym, 0, (size_t)M * g.K * 4, st));
   }
-  const float budget = (float)((double)M * (double)g.K * tol);     // ista.py:16, compared in fp32
+  const float budget = stop_budget<float>(M, g.K, tol);            // ista.py:16, compared in fp32
   const float lr_f = (float)lr, lam = (float)(alpha * lr);
   Momentum mom;
   float last = NAN;
@@ -3273,8 +3223,9 @@ int lasso_conv_ista_solve(const void* x_dev, const void* w_dev, const void* z0_d
       LASSO_HIP_TRY(hipGetLastError());
       return LASSO_OK;
     };
-    if (int s = speculate_stop_rule(maxiter, budget, ws.delta, st, &mom.t, iterate, save, restore, flush, &it, &last,
-                                    "lasso_conv_ista_solve"))
+    auto read = [&](float* host, int c) -> int { return read_back(host, ws.delta, sizeof(float) * c, st); };
+    if (int s = speculate_stop_rule<float>(maxiter, budget, ws.delta, &mom.t, iterate, save, restore, flush, read, &it,
+                                           &last, "lasso_conv_ista_solve"))
       return s;
   }
   LASSO_HIP_TRY(launch_conv_relayout(ws.Zm, (float*)z_out_dev, nullptr, g.N, g.K, P, 0, st));

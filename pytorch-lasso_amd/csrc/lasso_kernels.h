@@ -447,31 +447,6 @@ hipError_t launch_generic_prox(float* Z, int64_t ldz, float* Y, const float* G, 
 hipError_t launch_zero_columns(float* Z, int64_t ldz, int n, int k, const int* degenerate,
                                hipStream_t stream);
 
-// Size of the next chunk of speculated iterations of a stop rule that is read once per chunk (speculate_stop_rule in
-// lasso_hip.hip, T = float; the float64 driver in gemm_f64.hip, T = double) after a chunk of `c` iterations without a
-// stop whose first / last sums were `first` / `last`, `it` iterations done.  Only speed depends on it; a stop inside a
-// chunk costs one chunk (the speculated rest plus the replay).  Within a factor 2 of the budget: one iteration at a time
-// (the reference's own cadence: the sums of a momentum run are not monotone, and an iteration speculated past the stop
-// costs more than the wait it saves).  Further away: the iterations the rule is still away at the chunk's average decay
-// -- that many when it is near (so that it fires at the chunk's END: nothing to replay), half as many when it is far;
-// without a decaying chunk behind us, as many iterations as the solve has done; at most half the iterations done, and
-// never fewer than the sums would need if they halved every iteration.
-template <class T>
-inline int next_stop_chunk(T first, T last, T budget, int c, int it, int chunk_max) {
-  int next = 1;
-  if (last > T(2) * budget) {
-    next = std::min(chunk_max, std::max(2, it));
-    if (c > 1 && first > T(0) && last < first && budget > T(0)) {
-      const double rate = log((double)first / (double)last) / (double)(c - 1);
-      const double away = log((double)last / (double)budget) / rate;
-      next = away <= 8.0 ? std::max(1, (int)ceil(away)) : (int)std::min((double)chunk_max, away / 2.0);
-    }
-    const int lg = budget > T(0) ? (int)std::min((double)chunk_max, log2((double)last / (double)budget)) : chunk_max;
-    next = std::max(lg, std::min(next, std::max(2, it / 2)));
-  }
-  return next;
-}
-
 // the Lipschitz computation from a float64 dictionary (the Gram product reads doubles; the squarings are the same)
 hipError_t launch_lipschitz_f64(const double* W, int64_t ldw, int64_t d, int64_t k, void* workspace, int squarings,
                                 hipStream_t stream);

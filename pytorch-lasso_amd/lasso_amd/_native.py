@@ -71,6 +71,11 @@ class GpsrResult(C.Structure):
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_double), C.c_int)
 
 
+def stop_budget(numel, tol):
+    """ista.py:64,93: ``z0.numel() * tol`` rounded once to float32 (stop_budget<float>, csrc/stoprule_host.hpp)"""
+    return C.c_float(float(numel) * tol).value
+
+
 def use_library(path):
     """Bind a different build of the library (A/B builds of the kernels under tools/); must be
     called before the first native call."""

@@ -72,7 +72,7 @@ def _solve(xg, zg, wg, geom, alpha, lr, fast, maxiter, tol, verbose, dev):
             # iteration at a time cannot carry the momentum state across calls, so the verbose
             # trace re-solves with maxiter = i for the printed value (debugging mode)
             stride, padding = geom[9:11], geom[11:13]
-            budget = float(np.float32(zg.numel() * tol))
+            budget = nat.stop_budget(zg.numel(), tol)
             for i in range(int(maxiter)):
                 zi = zg
                 if i > 0:

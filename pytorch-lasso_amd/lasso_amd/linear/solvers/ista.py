@@ -61,7 +61,7 @@ def _ista_verbose(x, z0, weight, alpha, fast, lr, maxiter, tol, dev):
     from ...engine import HipEngine
     eng = HipEngine(dev)
     n, k = z0.shape
-    budget = torch.tensor(float(n * k) * tol, dtype=torch.float32).item()
+    budget = nat.stop_budget(n * k, tol)
     z, y, done, last = z0, None, 0, float('nan')
     ws = eng.fista_workspace(n, x.shape[1], k, maxiter)
     for it in range(maxiter):

@@ -17,6 +17,8 @@ import math
 
 import torch
 
+from ._native import stop_budget
+
 try:
     import torch.distributed as dist
 except Exception:  # pragma: no cover
@@ -104,6 +106,26 @@ def constrained_mstep(engine, A, B, D, eps=1e-10, positive=False, group=None):
     return mask
 
 
+def _first_stop(hdelta, budget):        # ista.py:93 over a chunk's sums: the index of the first one <= budget, or -1
+    return next((i for i, v in enumerate(hdelta) if v <= budget), -1)
+
+
+def _next_tile_chunk(hdelta, c, budget):
+    """Size of the chunk after one of ``c`` sums without a stop, from their geometric decay: scheduling only, and alike on
+    every rank.  Twin of next_tile_chunk in csrc/stoprule_host.hpp (tests/test_stoprule_host_cpu.py holds them equal)."""
+    chunk = 64
+    if c >= 8 and budget > 0:
+        h = c // 2
+        hi, lo = max(hdelta[:h]), max(hdelta[h:])
+        if lo > budget and hi > lo:
+            left = math.log(lo / budget) / (math.log(hi / lo) / h)
+            if left < 128:
+                chunk = max(8, min(int(left) - 6, 64))
+        elif lo <= 4 * budget:
+            chunk = 8
+    return chunk
+
+
 def sharded_encode(engine, X, W, alpha, z0, group=None, **kw):
     """E-step on this rank's shard.  world == 1: plain sparse_encode.  world > 1 with an
     active stop rule: exact GLOBAL rule through chunked speculation + one all-reduce of
@@ -178,7 +200,7 @@ def sharded_encode(engine, X, W, alpha, z0, group=None, **kw):
         _all_reduce(n_glob, group)
         n_global = n_glob.item()
     # ista.py:64,93 on the rows of ALL ranks: sum_i |z - z_next| <= n_global * k * tol, compared in fp32
-    budget = torch.tensor(float(n_global) * k * tol, dtype=torch.float32).item()
+    budget = stop_budget(n_global * k, tol)
     chunk, done = 64, 0
     z, y = z0, None
     last = float('nan')
@@ -187,25 +209,13 @@ def sharded_encode(engine, X, W, alpha, z0, group=None, **kw):
         z2, y2, delta = run(z, y, done, c, True)
         _all_reduce(delta, group)           # ONE small all-reduce per chunk of <= 64 iterations, not per iteration
         hdelta = delta.tolist()             # the chunk's one host read; every rank sees the same summed vector
-        hit = next((i for i, v in enumerate(hdelta) if v <= budget), -1)
+        hit = _first_stop(hdelta, budget)
         if hit >= 0:
             if hit + 1 < c:                 # replay the chunk from its intact input state up to the stopping iteration
                 z2, _, _ = run(z, y, done, hit + 1, False)
             return result(z2, done + hit + 1, hdelta[hit])
         z, y, done, last = z2, y2, done + c, hdelta[-1]
-        # scheduling only (the stop decision stays exact; every rank holds the same summed vector, so every rank sizes
-        # the next chunk alike): iterations left from the geometric decay over this chunk, approached with short chunks
-        # so that little is speculated past the stopping iteration -- the heuristic of lasso_fista_solve's chunked path
-        chunk = 64
-        if c >= 8 and budget > 0:
-            h = c // 2
-            hi, lo = max(hdelta[:h]), max(hdelta[h:])
-            if lo > budget and hi > lo:
-                left = math.log(lo / budget) / (math.log(hi / lo) / h)
-                if left < 128:
-                    chunk = max(8, min(int(left) - 6, 64))
-            elif lo <= 4 * budget:
-                chunk = 8
+        chunk = _next_tile_chunk(hdelta, c, budget)
     return result(z, done, last)
 
 
@@ -229,9 +239,9 @@ class _EmptyShardPending:
     def __call__(self):
         if getattr(self, '_ev', None) is not None:
             self._ev.synchronize()
-        budget = torch.tensor(float(self._n_global) * self._k * self._tol, dtype=torch.float32).item()
+        budget = stop_budget(self._n_global * self._k, self._tol)
         h = self._reduced.tolist()
-        hit = next((i for i, v in enumerate(h) if v <= budget), -1)
+        hit = _first_stop(h, budget)
         self.iterations, self.last_delta = (hit + 1 if hit >= 0 else len(h)), h[hit]
         return not (hit >= 0 and hit + 1 < len(h))
 
