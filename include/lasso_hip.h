@@ -11,6 +11,16 @@
  *     library allocates nothing persistent and never frees caller memory;
  *   - matrices are row-major with an explicit leading dimension in ELEMENTS:
  *       X [n][d] (ldx), W [d][k] (ldw, atoms are columns), Z [n][k] (ldz);
+ *   - layout contract, for every matrix that carries a leading dimension (ldx, ldw, ldz, ldz0, ldd, ldv, ldo, ldab,
+ *     pool_ld, the ld of the patch calls, the ld*_in / ld*_out of lasso_fista_run, ldzt): ANY leading dimension >= the
+ *     row length is accepted (a smaller one is LASSO_ERR_BAD_ARG before anything is enqueued), and a base pointer
+ *     aligned to the ELEMENT is enough -- a sub-matrix of the caller's own allocation is a valid operand.  The kernels
+ *     choose 16-byte vector loads / stores or LDS-DMA at run time, per operand, from the pitch AND the pointer; the
+ *     result does not depend on that choice (same products, same order) except where a function says so.  The elements
+ *     between the rows (ld - row length per row) are never read into a result -- they may hold NaN -- and never
+ *     written.  Two functions ask for more and refuse, with a status and a text, before the first launch:
+ *     lasso_fista_solve_sharded (ldz == k) and the lasso_mstep_pipe_* calls (16-byte aligned bases, pitches that are
+ *     multiples of 4 floats); stated there;
  *   - `stream` is a hipStream_t passed as void* (NULL = the null stream); work is
  *     enqueued on it; a call only blocks the host where a host-visible result
  *     (iteration count, stop decision) is produced -- stated per function;
@@ -298,6 +308,10 @@ int lasso_objective_f64(const void* x_dev, int64_t ldx, const void* w_dev, int64
  *   the i-th flagged atom (atom order) becomes pool row i, clamped at 0 if `positive`,
  *   normalised (:93-96).
  * lasso_zero_columns: Z[:, j] = 0 where degenerate_dev[j] != 0 (:98).
+ * Layout: lasso_gram_accumulate runs its 256- and 128-wide block kernels when z_dev and x_dev are 16-byte aligned with
+ *   pitches that are multiples of 4 floats, and 32-wide blocks with scalar loads otherwise: other sample splits, so A
+ *   and B differ in the last bits between the two (each is deterministic, A exactly symmetric, either way).  The sweep's
+ *   dictionary does not depend on ldd / ldo / pool_ld or on the alignment of d_dev.
  */
 size_t lasso_gram_workspace_bytes(int64_t n, int64_t d, int64_t k);
 int lasso_gram_accumulate(const void* z_dev, int64_t ldz, const void* x_dev, int64_t ldx,
@@ -368,7 +382,12 @@ int lasso_stream_wait_word(const int32_t* word, int32_t value, int host_memory, 
  * (lasso_mstep_pipe_workspace_bytes; caller-owned, shared by both streams, ZEROED once before its first use).
  * Results: the dictionary of lasso_dict_sweep on the same (A, B) bit for bit -- the same products in the same order --;
  * A and B themselves differ from lasso_gram_accumulate's in the last bits (other sample splits, hence another
- * summation order). */
+ * summation order).
+ * Layout (stricter than the library's general contract -- these kernels have 16-byte vector forms only): ab_dev, and in
+ * lasso_mstep_pipe_gram z_dev and x_dev (n > 0), in lasso_mstep_pipe_rows and _sweep d_dev, must be 16-byte aligned with
+ * pitches (ldab, ldz, ldx, ldd) that are multiples of 4 floats; lasso_mstep_pipe_sweep reads ab_dev element-wise (any ldab >=
+ * k + d, any alignment) and lasso_mstep_pipe_finish writes d_dev element-wise (any ldd >= k).  Anything else answers
+ * LASSO_ERR_BAD_ARG with the rule in the text, before the shape is looked at and before anything is enqueued. */
 int lasso_mstep_pipe_stages(int64_t n, int64_t d, int64_t k);
 int lasso_mstep_pipe_stage_rows(int64_t n, int64_t d, int64_t k, int stage, int64_t* row_lo, int64_t* row_hi);
 size_t lasso_mstep_pipe_workspace_bytes(int64_t n, int64_t d, int64_t k);
@@ -432,7 +451,8 @@ int lasso_zero_columns(void* z_dev, int64_t ldz, int64_t n, int64_t k, int dtype
  * invoked the same number of times with the same counts on every rank, and all ranks take the
  * same decisions (trials_out / accepted_lr_out / accepted_f_out are identical everywhere).
  * Workspace: lasso_fista_workspace_bytes(n, d, k, dtype, maxiter, tol, LASSO_STOP_GLOBAL, 1).
- * Requires ldz == k. */
+ * Requires ldz == k (z_out is the line search's flat [n][k] state; x, W, z0 take any layout): any other ldz answers
+ * LASSO_ERR_UNSUPPORTED "row-sharded line search needs ldz == k" before the first launch, z_out untouched. */
 typedef int (*lasso_allreduce_fn)(void* ctx, double* sums, int count);
 int lasso_fista_solve_sharded(const void* x_dev, int64_t ldx, const void* w_dev, int64_t ldw,
                               const void* z0_dev, int64_t ldz0, void* z_out_dev, int64_t ldz,

@@ -1077,6 +1077,8 @@ int solve_backtracking(const void* x_any, int64_t ldx, const void* w_any, int64_
   const BtForm form = (reduce || !recompute) ? BtForm::Sync : (flat16 && !(bt_hint & 3)) ? BtForm::Fused : BtForm::MultiLaunch;
   c.half = half; c.recompute = recompute; c.multi_trials = flat16 && !(bt_hint & 1);
   c.zero_in_kernel = form == BtForm::Fused && !z0_any && maxiter > 0;
+  // (refused before the first launch: z_out is not touched)
+  if (reduce && !recompute) return fail(LASSO_ERR_UNSUPPORTED, "row-sharded line search needs ldz == k");
   // ---- pack W and seed the state: z lives in zout, y in the workspace (y0 = z0, ista.py:76-78)
   if (half) {
     LASSO_HIP_TRY(launch_pack_w_bf16(w_any, ldw, (int)d, (int)k, kp, 1, ws.wp, ws.wtp, st));
@@ -1090,7 +1092,6 @@ int solve_backtracking(const void* x_any, int64_t ldx, const void* w_any, int64_
     if (!c.zero_in_kernel)
       if (int s = seed_state((const float*)z0_any, ldz0, zout, ldz, ws.Y, n, k, st)) return s;
   }
-  if (reduce && !recompute) return fail(LASSO_ERR_UNSUPPORTED, "row-sharded line search needs ldz == k");
   BtParams& p = c.p;
   p.X = (const float*)x_any; p.ldx = ldx; p.Wp = ws.wp; p.Wtp = ws.wtp;
   p.Xh = x_any; p.Wq1 = ws.wp; p.Wq2 = ws.wtp;
@@ -1416,6 +1417,16 @@ int check_cd(int64_t n, int64_t d, int64_t k, int dtype) {
                                               (long long)n, (long long)d, (long long)k);
   if (pad_k_cd(k) < 0) return fail(LASSO_ERR_UNSUPPORTED, "coordinate descent: k=%lld > 4096", (long long)k);
   if (n > INT32_MAX / 2 || d > INT32_MAX / 2) return fail(LASSO_ERR_UNSUPPORTED, "shape too large");
+  return LASSO_OK;
+}
+// the arguments of lasso_cd_run / lasso_cd_finish beyond the shape: one copy, also for lasso_cd_solve, which asks before
+// lasso_cd_prepare enqueues anything
+int check_cd_run_args(int iters, double alpha) {
+  if (iters < 0 || !(alpha >= 0.0)) return fail(LASSO_ERR_BAD_ARG, "iters=%d alpha=%g", iters, alpha);
+  return LASSO_OK;
+}
+int check_cd_finish_args(const void* z_out_dev, int64_t ldz, const void* z_track_out_dev, int64_t ldzt, int64_t k) {
+  if ((z_out_dev && ldz < k) || (z_track_out_dev && ldzt < k)) return fail(LASSO_ERR_BAD_ARG, "leading dimension too small");
   return LASSO_OK;
 }
 
@@ -2682,11 +2693,14 @@ int lasso_mstep_pipe_gram(const void* z_dev, int64_t ldz, const void* x_dev, int
   PipeWs w;
   if (!ab_dev || !workspace_dev || n < 0 || (n > 0 && (!z_dev || !x_dev || ldz < k || ldx < d)) || ldab < k + d)
     return fail(LASSO_ERR_BAD_ARG, "bad argument");
+  // (the layout rules of include/lasso_hip.h come first: they hold for every shape and need no device)
+  if ((ldab & 3) || ((uintptr_t)ab_dev & 15)) return fail(LASSO_ERR_BAD_ARG, "[A | B] must be 16-byte aligned, pitch a multiple of 4");
+  if (n > 0 && ((ldz & 3) || (ldx & 3) || ((uintptr_t)z_dev & 15) || ((uintptr_t)x_dev & 15)))
+    return fail(LASSO_ERR_BAD_ARG, "Z and X must be 16-byte aligned, pitches multiples of 4");
   if (!pipe_carve(std::max<int64_t>(n, 1), d, k, workspace_dev, &w)) return fail(LASSO_ERR_UNSUPPORTED, "no pipelined M-step for n=%lld d=%lld k=%lld",
                                                            (long long)n, (long long)d, (long long)k);
   if (workspace_bytes < w.bytes) return fail(LASSO_ERR_WORKSPACE, "need %zu bytes", w.bytes);
   if (stage < 0 || stage >= w.plan.nstages) return fail(LASSO_ERR_BAD_ARG, "stage %d of %d", stage, w.plan.nstages);
-  if ((ldab & 3) || ((uintptr_t)ab_dev & 15)) return fail(LASSO_ERR_BAD_ARG, "[A | B] must be 16-byte aligned, pitch a multiple of 4");
   // the head's launch also clears the sweep's flag words: it sits in front of every launch that sets or reads them
   int* const flags = stage == 0 ? sweep_persist_flags(w.extra, (int)k) : nullptr;
   if (n == 0) {
@@ -2733,6 +2747,8 @@ int lasso_mstep_pipe_rows(const float* ab_dev, int64_t ldab, const void* d_dev, 
   if (dtype != LASSO_F32) return fail(LASSO_ERR_UNSUPPORTED, "dtype %d", dtype);
   PipeWs w;
   if (!ab_dev || !d_dev || !workspace_dev || ldd < k || ldab < k + d) return fail(LASSO_ERR_BAD_ARG, "bad argument");
+  if ((ldab & 3) || (ldd & 3) || ((uintptr_t)ab_dev & 15) || ((uintptr_t)d_dev & 15))
+    return fail(LASSO_ERR_BAD_ARG, "[A | B] and the dictionary must be 16-byte aligned, pitches multiples of 4");
   if (!pipe_carve(n, d, k, workspace_dev, &w)) return fail(LASSO_ERR_UNSUPPORTED, "no pipelined M-step for this shape");
   if (workspace_bytes < w.bytes) return fail(LASSO_ERR_WORKSPACE, "need %zu bytes", w.bytes);
   if (stage < 0 || stage >= w.plan.nstages) return fail(LASSO_ERR_BAD_ARG, "stage %d of %d", stage, w.plan.nstages);
@@ -2741,8 +2757,6 @@ int lasso_mstep_pipe_rows(const float* ab_dev, int64_t ldab, const void* d_dev, 
   const int64_t r0 = 256 * (int64_t)lo;
   // U[j] = B[j] - sum_i A[j][i] D[:, i]   for the rows j of the block (dict_learning.py:82 in Gram form)
   // (uprod_rows_kernel: bitwise launch_gemm_nt_sub's product; its last workgroup raises the block row's flag)
-  if ((ldab & 3) || (ldd & 3) || ((uintptr_t)ab_dev & 15) || ((uintptr_t)d_dev & 15))
-    return fail(LASSO_ERR_BAD_ARG, "[A | B] and the dictionary must be 16-byte aligned, pitches multiples of 4");
   // (the head: `seq` into the word lasso_mstep_pipe_wait watches -- the head of the chain is through; the other
   // stages: the flags of their block rows for the running sweep)
   int* const words = sweep_pipe_words(w.extra, (int)k);
@@ -2760,9 +2774,9 @@ int lasso_mstep_pipe_sweep(const float* ab_dev, int64_t ldab, const void* d_dev,
   PipeWs w;
   if (!ab_dev || !d_dev || !degenerate_dev || !workspace_dev || ldd < k || ldab < k + d)
     return fail(LASSO_ERR_BAD_ARG, "bad argument");
+  if ((k & 3) || (ldd & 3) || ((uintptr_t)d_dev & 15)) return fail(LASSO_ERR_BAD_ARG, "the dictionary must be 16-byte aligned, pitch a multiple of 4");
   if (!pipe_carve(n, d, k, workspace_dev, &w)) return fail(LASSO_ERR_UNSUPPORTED, "no pipelined M-step for this shape");
   if (workspace_bytes < w.bytes) return fail(LASSO_ERR_WORKSPACE, "need %zu bytes", w.bytes);
-  if ((k & 3) || (ldd & 3) || ((uintptr_t)d_dev & 15)) return fail(LASSO_ERR_BAD_ARG, "the dictionary must be 16-byte aligned, pitch a multiple of 4");
   SweepParams& p = w.p;
   p.A = ab_dev; p.lda = ldab;
   p.Dsrc = (const float*)d_dev; p.ldd = ldd;
@@ -3050,7 +3064,7 @@ int lasso_cd_run(int64_t n, int64_t d, int64_t k, double alpha, double tol_abs, 
                  size_t workspace_bytes, void* stream) {
   if (int s = check_cd(n, d, k, LASSO_F32)) return s;
   if (!workspace_dev) return fail(LASSO_ERR_BAD_ARG, "null workspace");
-  if (iters < 0 || !(alpha >= 0.0)) return fail(LASSO_ERR_BAD_ARG, "iters=%d alpha=%g", iters, alpha);
+  if (int s = check_cd_run_args(iters, alpha)) return s;
   const int kp = pad_k_cd(k);
   CdWorkspace ws = carve_cd(workspace_dev, n, d, kp);
   if (workspace_bytes < ws.bytes) return fail(LASSO_ERR_WORKSPACE, "workspace %zu < %zu bytes", workspace_bytes, ws.bytes);
@@ -3078,7 +3092,7 @@ int lasso_cd_finish(void* z_out_dev, int64_t ldz, void* z_track_out_dev, int64_t
                     void* stream) {
   if (int s = check_cd(n, d, k, LASSO_F32)) return s;
   if (!workspace_dev) return fail(LASSO_ERR_BAD_ARG, "null workspace");
-  if ((z_out_dev && ldz < k) || (z_track_out_dev && ldzt < k)) return fail(LASSO_ERR_BAD_ARG, "leading dimension too small");
+  if (int s = check_cd_finish_args(z_out_dev, ldz, z_track_out_dev, ldzt, k)) return s;
   const int kp = pad_k_cd(k);
   CdWorkspace ws = carve_cd(workspace_dev, n, d, kp);
   if (workspace_bytes < ws.bytes) return fail(LASSO_ERR_WORKSPACE, "workspace %zu < %zu bytes", workspace_bytes, ws.bytes);
@@ -3091,7 +3105,11 @@ int lasso_cd_solve(const void* x_dev, int64_t ldx, const void* w_dev, int64_t ld
                    int64_t ldz0, void* z_out_dev, int64_t ldz, int64_t n, int64_t d, int64_t k, int dtype,
                    double alpha, int maxiter, double tol, int32_t* n_active_out, int32_t* max_steps_out,
                    void* workspace_dev, size_t workspace_bytes, void* stream) {
+  if (int s = check_cd(n, d, k, dtype)) return s;
   if (!z_out_dev && n > 0) return fail(LASSO_ERR_BAD_ARG, "null z_out");
+  // (what lasso_cd_run / _finish would refuse, before lasso_cd_prepare enqueues anything)
+  if (int s = check_cd_run_args(maxiter, alpha)) return s;
+  if (int s = check_cd_finish_args(z_out_dev, ldz, z0_inout_dev, ldz0, k)) return s;
   if (int s = lasso_cd_prepare(x_dev, ldx, w_dev, ldw, z0_inout_dev, ldz0, n, d, k, dtype, workspace_dev,
                                workspace_bytes, stream))
     return s;
