@@ -676,6 +676,44 @@ int lasso_conv_ista_backward(const void* x_dev, const void* w_dev, const void* t
                              void* grad_x_dev, void* grad_w_dev, void* grad_z0_dev,
                              void* workspace_dev, size_t workspace_bytes, void* stream);
 
+/* ---- float64 tensors on the convolutional path ---------------------------------------
+ * lasso_conv_ista_solve, lasso_conv_objective, lasso_conv_ista_run_traced and lasso_conv_ista_backward accept
+ * dtype == LASSO_F64: every tensor (x, weight, codes, trace, gradients) is then contiguous NCHW double, every value,
+ * sum, threshold, momentum step and stop-rule comparison an IEEE double (fp64 MFMA, csrc/conv_f64.hip), and the
+ * workspace / trace sizes are those of the _f64 byte-count functions below (the functions without the suffix take no
+ * dtype and describe fp32).  Their float slots (last_delta_out, the float at loss_dev) receive the double rounded once;
+ * the entry points below keep the doubles.  Same reach as the fp32 explicit path: any N >= 0, C, K, kernel size, stride
+ * and padding.  A geometry mismatch or a null required pointer is LASSO_ERR_BAD_ARG, a short workspace
+ * LASSO_ERR_WORKSPACE; both are decided on the host before any HIP call.  Two calls with the same arguments give the
+ * same bits.  lasso_conv_ista_kernel_name describes the fp32 dispatch only.
+ *   lasso_conv_lip_bound_f64: the Toeplitz bound with the phases, sin / cos and all sums in double on the frequency
+ *     grid 2*pi*i/(sample-1) (an extension: the reference multiplies a double kernel by its float32 phase table and
+ *     raises).  l_out: HOST (synchronises). */
+size_t lasso_conv_ista_workspace_bytes_f64(int64_t N, int64_t C, int64_t H, int64_t W, int64_t K,
+                                           int64_t Hz, int64_t Wz, int kh, int kw,
+                                           int sh, int sw, int ph, int pw);
+size_t lasso_conv_ista_trace_bytes_f64(int64_t N, int64_t C, int64_t H, int64_t W, int64_t K,
+                                       int64_t Hz, int64_t Wz, int kh, int kw, int sh, int sw, int ph, int pw,
+                                       int iterations);
+size_t lasso_conv_ista_backward_workspace_bytes_f64(int64_t N, int64_t C, int64_t H, int64_t W, int64_t K,
+                                                    int64_t Hz, int64_t Wz, int kh, int kw, int sh, int sw,
+                                                    int ph, int pw);
+size_t lasso_conv_lip_workspace_bytes_f64(int64_t K, int64_t C, int ksize, int sample);
+int lasso_conv_ista_solve_f64(const void* x_dev, const void* w_dev, const void* z0_dev, void* z_out_dev,
+                              int64_t N, int64_t C, int64_t H, int64_t W, int64_t K, int64_t Hz, int64_t Wz,
+                              int kh, int kw, int sh, int sw, int ph, int pw,
+                              double alpha, double lr, int fast, int maxiter, double tol,
+                              int32_t* iters_out, double* last_delta_out,
+                              void* workspace_dev, size_t workspace_bytes, void* stream);
+int lasso_conv_objective_f64(const void* x_dev, const void* w_dev, const void* z_dev,
+                             int64_t N, int64_t C, int64_t H, int64_t W, int64_t K, int64_t Hz, int64_t Wz,
+                             int kh, int kw, int sh, int sw, int ph, int pw,
+                             double alpha, double* loss_dev,
+                             void* workspace_dev, size_t workspace_bytes, void* stream);
+int lasso_conv_lip_bound_f64(const void* w_dev, int64_t K, int64_t C, int ksize, int padding, int sample,
+                             int take_sqrt, double* l_out,
+                             void* workspace_dev, size_t workspace_bytes, void* stream);
+
 /* ---- reverse-mode derivative of the unrolled fixed-step solve ------------------------
  * The reference's ista() is ordinary autograd-traceable torch code (ista.py:57-104; the
  * README advertises back-propagation through the solver).  Given the iterates

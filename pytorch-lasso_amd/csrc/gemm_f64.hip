@@ -32,15 +32,14 @@
 #include "lasso_kernels.h"
 #include "host_util.hpp"
 #include "stoprule_host.hpp"
+#include "f64_device.hpp"
 
 namespace lasso {
 namespace f64 {
 namespace {
 
-typedef double f64x4 __attribute__((ext_vector_type(4)));
-
 constexpr int kBM = 64, kBN = 64, kKC = 16, kRS = kKC + 1;
-constexpr int kGrid = 1024;           // workgroups (and partial sums per set) of the element-wise kernels
+constexpr int kGrid = kSumGrid;       // workgroups (and partial sums per set) of the element-wise kernels
 constexpr int kMaxTrials = 1000;      // ista.py:17 (maxiter=1000)
 enum { EPI_SUB = 0, EPI_PLAIN = 1, EPI_PROX = 2 };
 
@@ -54,23 +53,6 @@ struct GemmArgs {
   double* dpart;
   int m, nn, kk;
 };
-
-// sum of v over the workgroup's 256 threads in a fixed tree; valid in thread 0
-__device__ __forceinline__ double block_sum(double v, double* red) {
-  const int tid = threadIdx.x;
-  red[tid] = v;
-  __syncthreads();
-#pragma unroll
-  for (int s = 128; s > 0; s >>= 1) {
-    if (tid < s) red[tid] += red[tid + s];
-    __syncthreads();
-  }
-  return red[0];
-}
-
-__device__ __forceinline__ double softshrink(double u, double lam) {      // ATen's softshrink
-  return u > lam ? u - lam : (u < -lam ? u + lam : 0.0);
-}
 
 template <int EPI, bool BT>
 __global__ __launch_bounds__(256) void gemm_f64_nt_kernel(const GemmArgs g) {
@@ -349,6 +331,29 @@ hipError_t launch_gemm_sub(const double* A, int64_t lda, const double* B, int64_
   return b_t ? launch_gemm<EPI_SUB, true>(g, st) : launch_gemm<EPI_SUB, false>(g, st);
 }
 
+// C [m][nn] = A [m][kk] B, B [kk][nn] (conv_f64.hip's explicit synthesis: COLS = Ym W)
+hipError_t launch_gemm_plain(const double* A, int64_t lda, const double* B, int64_t ldb, double* C, int64_t ldc, int m,
+                             int nn, int kk, hipStream_t st) {
+  GemmArgs g{A, lda, B, ldb, nullptr, 0, C, ldc, nullptr, 0, 0.0, 0.0, 0.0, nullptr, m, nn, kk};
+  return launch_gemm<EPI_PLAIN, true>(g, st);
+}
+
+hipError_t launch_reduce_sets(const double* parts, int64_t count, int sets, double* out, hipStream_t st) {
+  hipLaunchKernelGGL(reduce_sets_kernel, dim3(sets), dim3(256), 0, st, parts, count, out);
+  return hipGetLastError();
+}
+
+// loss = (0.5 sum R^2 + alpha sum |Z|) / n_total from R [nd] and Z [n][k] (pitch ldz); part: 2 kSumGrid doubles
+hipError_t launch_objective_sums(const double* R, int64_t nd, const double* Z, int64_t ldz, int64_t n, int64_t k,
+                                 double* part, double alpha, double n_total, double* sums, double* loss64, float* loss32,
+                                 hipStream_t st) {
+  hipLaunchKernelGGL(sumsq_kernel, dim3(kGrid), dim3(256), 0, st, R, nd, part);
+  hipLaunchKernelGGL(sumabs_kernel, dim3(kGrid), dim3(256), 0, st, Z, ldz, n, k, part + kGrid);
+  hipLaunchKernelGGL(objective_finish_kernel, dim3(1), dim3(256), 0, st, part, (int64_t)kGrid, alpha, n_total, sums,
+                     loss64, loss32);
+  return hipGetLastError();
+}
+
 size_t solve_workspace_bytes(int64_t n, int64_t d, int64_t k, int maxiter, double tol, int stop_mode, int backtrack) {
   const bool with_state = !backtrack && tol > 0.0 && (stop_mode & 0xFF) != LASSO_STOP_NONE && maxiter > 0;
   return carve(nullptr, n, d, k, backtrack != 0, with_state).bytes;
@@ -504,11 +509,7 @@ int objective(const double* x, int64_t ldx, const double* w, int64_t ldw, const 
   double* part = reinterpret_cast<double*>(base + align_up((size_t)n * d * 8));
   double* own = part + 2 * kGrid;
   LASSO_HIP_TRY(gemm_sub(z, ldz, w, ldw, x, ldx, R, d, (int)n, (int)d, (int)k, st));
-  hipLaunchKernelGGL(sumsq_kernel, dim3(kGrid), dim3(256), 0, st, R, n * d, part);
-  hipLaunchKernelGGL(sumabs_kernel, dim3(kGrid), dim3(256), 0, st, z, ldz, n, k, part + kGrid);
-  hipLaunchKernelGGL(objective_finish_kernel, dim3(1), dim3(256), 0, st, part, (int64_t)kGrid, alpha, (double)n,
-                     sums ? sums : own, loss64, loss32);
-  LASSO_HIP_TRY(hipGetLastError());
+  LASSO_HIP_TRY(launch_objective_sums(R, n * d, z, ldz, n, k, part, alpha, (double)n, sums ? sums : own, loss64, loss32, st));
   return LASSO_OK;
 }
 

@@ -1461,7 +1461,8 @@ ConvWorkspace carve_conv(void* base, const ConvGeom& g) {
 }
 
 int check_conv(const ConvGeom& g, int dtype) {
-  if (dtype != LASSO_F32) return fail(LASSO_ERR_UNSUPPORTED, "dtype %d: only LASSO_F32 is implemented", dtype);
+  if (dtype != LASSO_F32 && dtype != LASSO_F64)
+    return fail(LASSO_ERR_UNSUPPORTED, "dtype %d: LASSO_F32 and LASSO_F64 are implemented", dtype);
   if (g.N < 0 || g.C <= 0 || g.K <= 0 || g.H <= 0 || g.W <= 0 || g.Hz <= 0 || g.Wz <= 0 || g.kh <= 0 ||
       g.kw <= 0 || g.sh <= 0 || g.sw <= 0 || g.ph < 0 || g.pw < 0)
     return fail(LASSO_ERR_BAD_ARG, "bad convolution geometry");
@@ -3157,6 +3158,15 @@ int lasso_conv_ista_solve(const void* x_dev, const void* w_dev, const void* z0_d
                           int sh, int sw, int ph, int pw, int dtype, double alpha, double lr, int fast,
                           int maxiter, double tol, int32_t* iters_out, float* last_delta_out,
                           void* workspace_dev, size_t workspace_bytes, void* stream) {
+  if (dtype == LASSO_F64) {
+    // the same solve; the float slot receives the double rounded once (lasso_conv_ista_solve_f64 keeps it)
+    double last64 = NAN;
+    const int status = lasso_conv_ista_solve_f64(x_dev, w_dev, z0_dev, z_out_dev, N, C, H, W, K, Hz, Wz, kh, kw, sh, sw, ph,
+                                                 pw, alpha, lr, fast, maxiter, tol, iters_out, &last64, workspace_dev,
+                                                 workspace_bytes, stream);
+    if (status == LASSO_OK && last_delta_out) *last_delta_out = (float)last64;
+    return status;
+  }
   const ConvGeom g = make_geom(N, C, H, W, K, Hz, Wz, kh, kw, sh, sw, ph, pw);
   if (int s = check_conv(g, dtype)) return s;
   if (!w_dev || !workspace_dev || (N > 0 && (!x_dev || !z_out_dev))) return fail(LASSO_ERR_BAD_ARG, "null pointer");
@@ -3261,6 +3271,9 @@ int lasso_conv_objective(const void* x_dev, const void* w_dev, const void* z_dev
   if (int s = check_conv(g, dtype)) return s;
   if (!x_dev || !w_dev || !z_dev || !loss_dev || !workspace_dev) return fail(LASSO_ERR_BAD_ARG, "null pointer");
   if (N == 0) return fail(LASSO_ERR_BAD_ARG, "empty batch");
+  if (dtype == LASSO_F64)       // the double loss rounded once into the float slot (lasso_conv_objective_f64 keeps it)
+    return f64::conv_objective((const double*)x_dev, (const double*)w_dev, (const double*)z_dev, g, alpha, nullptr,
+                               loss_dev, workspace_dev, workspace_bytes, static_cast<hipStream_t>(stream));
   ConvWorkspace ws = carve_conv(workspace_dev, g);
   if (workspace_bytes < ws.bytes) return fail(LASSO_ERR_WORKSPACE, "workspace %zu < %zu bytes", workspace_bytes, ws.bytes);
   hipStream_t st = static_cast<hipStream_t>(stream);
@@ -3294,6 +3307,10 @@ int lasso_conv_ista_run_traced(const void* x_dev, const void* w_dev, const void*
     return fail(LASSO_ERR_BAD_ARG, "null pointer");
   if (iterations < 0 || !(lr > 0.0) || !(alpha >= 0.0))
     return fail(LASSO_ERR_BAD_ARG, "iterations=%d lr=%g alpha=%g", iterations, lr, alpha);
+  if (dtype == LASSO_F64)       // trace_dev: lasso_conv_ista_trace_bytes_f64 bytes, doubles
+    return f64::conv_solve((const double*)x_dev, (const double*)w_dev, (const double*)z0_dev, (double*)z_out_dev, g, alpha,
+                           lr, fast, iterations, 0.0, (double*)trace_dev, nullptr, nullptr, workspace_dev, workspace_bytes,
+                           static_cast<hipStream_t>(stream));
   ConvWorkspace ws = carve_conv(workspace_dev, g);
   if (workspace_bytes < ws.bytes) return fail(LASSO_ERR_WORKSPACE, "workspace %zu < %zu bytes", workspace_bytes, ws.bytes);
   if (N == 0) return LASSO_OK;
@@ -3363,6 +3380,10 @@ int lasso_conv_ista_backward(const void* x_dev, const void* w_dev, const void* t
   if (!w_dev || !workspace_dev || (N > 0 && (!x_dev || !trace_dev || !grad_z_dev)))
     return fail(LASSO_ERR_BAD_ARG, "null pointer");
   if (iterations < 0 || !(lr > 0.0)) return fail(LASSO_ERR_BAD_ARG, "iterations=%d lr=%g", iterations, lr);
+  if (dtype == LASSO_F64)       // trace and gradients in double; workspace: lasso_conv_ista_backward_workspace_bytes_f64
+    return f64::conv_backward((const double*)x_dev, (const double*)w_dev, (const double*)trace_dev,
+                              (const double*)grad_z_dev, g, lr, fast, iterations, (double*)grad_x_dev, (double*)grad_w_dev,
+                              (double*)grad_z0_dev, workspace_dev, workspace_bytes, static_cast<hipStream_t>(stream));
   const int cus = std::max(device_cus(), 1);
   ConvBwWorkspace ws = carve_conv_bw(workspace_dev, g, cus);
   if (workspace_bytes < ws.bytes) return fail(LASSO_ERR_WORKSPACE, "workspace %zu < %zu bytes", workspace_bytes, ws.bytes);
@@ -3470,6 +3491,68 @@ int lasso_conv_lip_bound(const void* w_dev, int64_t K, int64_t C, int ksize, int
     LASSO_HIP_TRY(hipStreamSynchronize(st));
   }
   return LASSO_OK;
+}
+
+// ---- float64 forms of the convolutional entry points (conv_f64.hip) ------------------------
+size_t lasso_conv_ista_workspace_bytes_f64(int64_t N, int64_t C, int64_t H, int64_t W, int64_t K, int64_t Hz,
+                                           int64_t Wz, int kh, int kw, int sh, int sw, int ph, int pw) {
+  const ConvGeom g = make_geom(N, C, H, W, K, Hz, Wz, kh, kw, sh, sw, ph, pw);
+  if (check_conv(g, LASSO_F64)) return 0;
+  return f64::conv_workspace_bytes(g);
+}
+
+size_t lasso_conv_ista_trace_bytes_f64(int64_t N, int64_t C, int64_t H, int64_t W, int64_t K, int64_t Hz, int64_t Wz,
+                                       int kh, int kw, int sh, int sw, int ph, int pw, int iterations) {
+  const ConvGeom g = make_geom(N, C, H, W, K, Hz, Wz, kh, kw, sh, sw, ph, pw);
+  if (iterations < 0 || check_conv(g, LASSO_F64)) return 0;
+  return (size_t)(iterations + 1) * (size_t)N * Hz * Wz * K * 8;
+}
+
+size_t lasso_conv_ista_backward_workspace_bytes_f64(int64_t N, int64_t C, int64_t H, int64_t W, int64_t K, int64_t Hz,
+                                                    int64_t Wz, int kh, int kw, int sh, int sw, int ph, int pw) {
+  const ConvGeom g = make_geom(N, C, H, W, K, Hz, Wz, kh, kw, sh, sw, ph, pw);
+  if (check_conv(g, LASSO_F64)) return 0;
+  return f64::conv_backward_workspace_bytes(g);
+}
+
+int lasso_conv_ista_solve_f64(const void* x_dev, const void* w_dev, const void* z0_dev, void* z_out_dev, int64_t N,
+                              int64_t C, int64_t H, int64_t W, int64_t K, int64_t Hz, int64_t Wz, int kh, int kw, int sh,
+                              int sw, int ph, int pw, double alpha, double lr, int fast, int maxiter, double tol,
+                              int32_t* iters_out, double* last_delta_out, void* workspace_dev, size_t workspace_bytes,
+                              void* stream) {
+  const ConvGeom g = make_geom(N, C, H, W, K, Hz, Wz, kh, kw, sh, sw, ph, pw);
+  if (int s = check_conv(g, LASSO_F64)) return s;
+  if (!w_dev || !workspace_dev || (N > 0 && (!x_dev || !z_out_dev))) return fail(LASSO_ERR_BAD_ARG, "null pointer");
+  if (maxiter < 0 || !(lr > 0.0) || !(alpha >= 0.0)) return fail(LASSO_ERR_BAD_ARG, "maxiter=%d lr=%g alpha=%g", maxiter, lr, alpha);
+  return f64::conv_solve((const double*)x_dev, (const double*)w_dev, (const double*)z0_dev, (double*)z_out_dev, g, alpha,
+                         lr, fast, maxiter, tol, nullptr, iters_out, last_delta_out, workspace_dev, workspace_bytes,
+                         static_cast<hipStream_t>(stream));
+}
+
+int lasso_conv_objective_f64(const void* x_dev, const void* w_dev, const void* z_dev, int64_t N, int64_t C, int64_t H,
+                             int64_t W, int64_t K, int64_t Hz, int64_t Wz, int kh, int kw, int sh, int sw, int ph, int pw,
+                             double alpha, double* loss_dev, void* workspace_dev, size_t workspace_bytes, void* stream) {
+  const ConvGeom g = make_geom(N, C, H, W, K, Hz, Wz, kh, kw, sh, sw, ph, pw);
+  if (int s = check_conv(g, LASSO_F64)) return s;
+  if (!x_dev || !w_dev || !z_dev || !loss_dev || !workspace_dev) return fail(LASSO_ERR_BAD_ARG, "null pointer");
+  if (N == 0) return fail(LASSO_ERR_BAD_ARG, "empty batch");
+  return f64::conv_objective((const double*)x_dev, (const double*)w_dev, (const double*)z_dev, g, alpha, loss_dev, nullptr,
+                             workspace_dev, workspace_bytes, static_cast<hipStream_t>(stream));
+}
+
+size_t lasso_conv_lip_workspace_bytes_f64(int64_t K, int64_t C, int ksize, int sample) {
+  (void)ksize;
+  if (K <= 0 || C <= 0 || sample <= 0) return 0;
+  return f64::conv_lip_workspace_bytes(K, C, sample);
+}
+
+int lasso_conv_lip_bound_f64(const void* w_dev, int64_t K, int64_t C, int ksize, int padding, int sample, int take_sqrt,
+                             double* l_out, void* workspace_dev, size_t workspace_bytes, void* stream) {
+  if (!w_dev || !workspace_dev || K <= 0 || C <= 0 || ksize <= 0 || sample < 2)
+    return fail(LASSO_ERR_BAD_ARG, "bad argument");
+  if (ksize % 2 != 1) return fail(LASSO_ERR_BAD_ARG, "The dimension of the kernel must be odd.");   // :101-102
+  return f64::conv_lip_bound((const double*)w_dev, K, C, ksize, padding, sample, take_sqrt, l_out, workspace_dev,
+                             workspace_bytes, static_cast<hipStream_t>(stream));
 }
 
 // ---- reverse-mode derivative of the unrolled fixed-step solve (autograd.hip) --------------

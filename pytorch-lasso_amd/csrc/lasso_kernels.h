@@ -473,6 +473,33 @@ int init_transpose(const double* x, int64_t ldx, const double* w, int64_t ldw, d
 // C = C0 - A B^T on gemm_f64_nt_kernel; b_t = 0: B [nn][kk], else B [kk][nn]; C may be C0 (gemm_f64.hip)
 hipError_t launch_gemm_sub(const double* A, int64_t lda, const double* B, int64_t ldb, int b_t, const double* C0,
                            int64_t ldc0, double* C, int64_t ldc, int m, int nn, int kk, hipStream_t st);
+// C [m][nn] = A [m][kk] B, B [kk][nn], on the same kernel's `plain` epilogue
+hipError_t launch_gemm_plain(const double* A, int64_t lda, const double* B, int64_t ldb, double* C, int64_t ldc, int m,
+                             int nn, int kk, hipStream_t st);
+constexpr int kSumGrid = 1024;        // workgroups (and partial sums per set) of the element-wise reductions
+// out[s] = sum of parts[s*count .. s*count + count) in a fixed order, s < sets
+hipError_t launch_reduce_sets(const double* parts, int64_t count, int sets, double* out, hipStream_t st);
+// loss = (0.5 sum R^2 + alpha sum |Z|) / n_total from R [nd] and Z [n][k] (pitch ldz); part: 2 kSumGrid doubles;
+// sums = {sum R^2, sum |Z|}; loss64 / loss32 nullable
+hipError_t launch_objective_sums(const double* R, int64_t nd, const double* Z, int64_t ldz, int64_t n, int64_t k,
+                                 double* part, double alpha, double n_total, double* sums, double* loss64, float* loss32,
+                                 hipStream_t st);
+// float64 convolutional solve (conv_f64.hip): drivers behind the LASSO_F64 forms of the lasso_conv_* entry points.
+// The geometry is checked by the caller; they return a lasso_status, failure text through lasso::fail.
+size_t conv_workspace_bytes(const ConvGeom& g);
+size_t conv_backward_workspace_bytes(const ConvGeom& g);
+size_t conv_lip_workspace_bytes(int64_t K, int64_t C, int sample);
+// trace (nullable): the iterates z_0 .. z_T as rows [T+1][M][K]
+int conv_solve(const double* x, const double* w, const double* z0, double* zout, const ConvGeom& g, double alpha, double lr,
+               int fast, int maxiter, double tol, double* trace, int32_t* iters_out, double* last_delta_out,
+               void* workspace, size_t ws_bytes, hipStream_t st);
+int conv_objective(const double* x, const double* w, const double* z, const ConvGeom& g, double alpha, double* loss64,
+                   float* loss32, void* workspace, size_t ws_bytes, hipStream_t st);
+int conv_backward(const double* x, const double* w, const double* trace, const double* grad_z, const ConvGeom& g, double lr,
+                  int fast, int iterations, double* gx, double* gw, double* gz0, void* workspace, size_t ws_bytes,
+                  hipStream_t st);
+int conv_lip_bound(const double* w, int64_t K, int64_t C, int ksize, int padding, int sample, int take_sqrt, double* l_out,
+                   void* workspace, size_t ws_bytes, hipStream_t st);
 // float64 M-step (mstep_f64.hip): Gram products, atom sweep, ridge solve in double on the fp64 MFMA
 constexpr int kGramF64MaxSplits = 16;
 int gram_splits(int64_t n, int64_t d, int64_t k, int cus);      // row splits of both products (1: no partial slabs)

@@ -248,6 +248,21 @@ def _declare(lib):
     lib.lasso_conv_lip_workspace_bytes.argtypes = [i64, i64, i32, i32]
     lib.lasso_conv_lip_bound.restype = i32
     lib.lasso_conv_lip_bound.argtypes = [vp, i64, i64, i32, i32, i32, i32, C.POINTER(dbl), vp, sz, vp]
+    # float64 forms of the convolutional entry points (csrc/conv_f64.hip)
+    lib.lasso_conv_ista_workspace_bytes_f64.restype = sz
+    lib.lasso_conv_ista_workspace_bytes_f64.argtypes = geom
+    lib.lasso_conv_ista_trace_bytes_f64.restype = sz
+    lib.lasso_conv_ista_trace_bytes_f64.argtypes = geom + [i32]
+    lib.lasso_conv_ista_backward_workspace_bytes_f64.restype = sz
+    lib.lasso_conv_ista_backward_workspace_bytes_f64.argtypes = geom
+    lib.lasso_conv_lip_workspace_bytes_f64.restype = sz
+    lib.lasso_conv_lip_workspace_bytes_f64.argtypes = [i64, i64, i32, i32]
+    lib.lasso_conv_ista_solve_f64.restype = i32
+    lib.lasso_conv_ista_solve_f64.argtypes = [vp, vp, vp, vp] + geom + [dbl, dbl, i32, i32, dbl, pi32, pdbl, vp, sz, vp]
+    lib.lasso_conv_objective_f64.restype = i32
+    lib.lasso_conv_objective_f64.argtypes = [vp, vp, vp] + geom + [dbl, vp, vp, sz, vp]
+    lib.lasso_conv_lip_bound_f64.restype = i32
+    lib.lasso_conv_lip_bound_f64.argtypes = [vp, i64, i64, i32, i32, i32, i32, pdbl, vp, sz, vp]
     lib.lasso_fista_backward_workspace_bytes.restype = sz
     lib.lasso_fista_backward_workspace_bytes.argtypes = [i64, i64, i64]
     lib.lasso_fista_backward.restype = i32

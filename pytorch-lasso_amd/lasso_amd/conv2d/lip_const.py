@@ -18,12 +18,17 @@ def _check(kernel_size, stride):
 
 
 def lip_bound_conv2d(kernel, padding, stride=1, sample=50, sqrt=False):
-    """-> 0-d float32 tensor on the kernel's device, like the reference (:131-135)."""
+    """-> 0-d float32 tensor on the kernel's device, like the reference (:131-135).
+
+    A float64 kernel gives a float64 0-d tensor: phases, sin / cos and every sum in double on the frequency grid
+    ``2*pi*i/(sample-1)``.  This is an extension -- the reference multiplies a double kernel by its float32 phase
+    table and fails with a dtype RuntimeError."""
     assert kernel.dim() == 4                                                # :98
     _check(kernel.shape, stride)
     nat.require_gpu()
-    if kernel.dtype != torch.float32:
-        raise NotImplementedError("lasso_amd: lip_bound_conv2d is implemented for float32 kernels")
+    if kernel.dtype not in (torch.float32, torch.float64):
+        raise NotImplementedError("lasso_amd: lip_bound_conv2d is implemented for float32 and float64 kernels")
+    f64 = kernel.dtype == torch.float64
     out_device = kernel.device
     dev = nat.pick_device(kernel)
     wg = kernel.detach().to(dev).contiguous()
@@ -31,10 +36,12 @@ def lip_bound_conv2d(kernel, padding, stride=1, sample=50, sqrt=False):
     L = nat.lib()
     val = C.c_double(0.0)
     with torch.cuda.device(dev):
-        ws = nat.workspace(dev, L.lasso_conv_lip_workspace_bytes(K, Cin, ks, int(sample)), "convlip")
-        nat.check(L.lasso_conv_lip_bound(nat.ptr(wg), K, Cin, ks, int(padding), int(sample), int(bool(sqrt)),
-                                         C.byref(val), nat.ptr(ws), ws.numel(), nat.stream_ptr(dev)))
-    return torch.tensor(val.value, dtype=torch.float32, device=out_device)
+        size_fn, bound_fn = ((L.lasso_conv_lip_workspace_bytes_f64, L.lasso_conv_lip_bound_f64) if f64 else
+                             (L.lasso_conv_lip_workspace_bytes, L.lasso_conv_lip_bound))
+        ws = nat.workspace(dev, size_fn(K, Cin, ks, int(sample)), "convlip")
+        nat.check(bound_fn(nat.ptr(wg), K, Cin, ks, int(padding), int(sample), int(bool(sqrt)),
+                           C.byref(val), nat.ptr(ws), ws.numel(), nat.stream_ptr(dev)))
+    return torch.tensor(val.value, dtype=kernel.dtype, device=out_device)
 
 
 class LipBoundConv2d(torch.nn.Module):
