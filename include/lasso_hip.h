@@ -598,6 +598,33 @@ int lasso_cd_solve(const void* x_dev, int64_t ldx, const void* w_dev, int64_t ld
                    int32_t* n_active_out, int32_t* max_steps_out,
                    void* workspace_dev, size_t workspace_bytes, void* stream);
 
+/* ---- cyclic coordinate descent with a duality-gap stop: replaces coord_descent_mod(),
+ *      lasso/linear/solvers/coordinate_descent.py:57-139 (after sklearn's enet_coordinate_descent) ----
+ * Per row, sweeps over the atoms in order: z_i <- S_alpha(R . w_i + ||w_i||^2 z_i) / ||w_i||^2 with the residual
+ * R = x - z W^T kept current (:110-129); an atom of zero norm is skipped, its coordinate keeps its start value (:111).
+ * After a sweep the row is checked (:132) when max|z| == 0, when max|change| / max|z| < tol, or on sweep max_iter; a
+ * checked row gets the duality gap (:87-99), and stops once gap < tol * ||x_row||^2.  The whole solve of all rows is
+ * ONE launch behind two products (G = W^T W, b0 = x W): a wave keeps a row's z and q = b0 - G z in registers and visits
+ * only the coordinates that can change (csrc/cd_mod.hip).  No atomics: two calls give the same bits.
+ *   z_inout [n][k] (ldz): with z_has_start != 0 the start, updated IN PLACE like the reference's z0 (:76,139); with
+ *     z_has_start == 0 it is only written (zero start).
+ *   gap_out [n] (device): the last evaluated gap of each row; tol + 1 for a row never checked (max_iter == 0, :78).
+ *   sweeps_out [n] int32 / converged_out [n] bytes (device, nullable): sweeps run and gap < tol * ||x_row||^2.  A row
+ *     whose sweep changed nothing and did not converge reports max_iter: the remaining sweeps would repeat it.
+ *   n_unconverged_out / committed_out (HOST, nullable): rows not converged, and coordinate updates with a nonzero
+ *     change summed over rows and sweeps; when either is given the call synchronises `stream`, else nothing blocks.
+ * The layout contract above applies to x, W and z (padding is never written).  Null pointers, negative sizes and too
+ * small leading dimensions answer LASSO_ERR_BAD_ARG with nothing enqueued; dtypes other than LASSO_F32 and k > 4096
+ * LASSO_ERR_UNSUPPORTED.  Any d.  Rows are independent: a row shard needs no collective.
+ */
+size_t lasso_cd_mod_workspace_bytes(int64_t n, int64_t d, int64_t k, int dtype);
+int lasso_cd_mod_solve(const void* x_dev, int64_t ldx, const void* w_dev, int64_t ldw,
+                       void* z_inout_dev, int64_t ldz, int z_has_start,
+                       float* gap_out_dev, int32_t* sweeps_out_dev, uint8_t* converged_out_dev,
+                       int64_t n, int64_t d, int64_t k, int dtype, double alpha, int max_iter, double tol,
+                       int32_t* n_unconverged_out, int64_t* committed_out,
+                       void* workspace_dev, size_t workspace_bytes, void* stream);
+
 /* ---- convolutional ISTA/FISTA: replaces ista_conv2d(), lasso/conv2d/ista.py:7-49, and
  *      lip_bound_conv2d(), lasso/conv2d/lip_const.py:96-135 ---------------------------------
  * All tensors are contiguous NCHW fp32: x [N][C][H][W], weight [K][C][kh][kw] (the layout

@@ -3122,6 +3122,74 @@ int lasso_cd_solve(const void* x_dev, int64_t ldx, const void* w_dev, int64_t ld
                          workspace_bytes, stream);
 }
 
+// ---- cyclic coordinate descent with a duality-gap stop: coordinate_descent.py:57-139 ----
+namespace {
+struct CdModWorkspace { float* G; float* Wt; float* B0; int* row_sweeps; int* row_conv; unsigned long long* row_commits;
+                        long long* info; size_t bytes; };
+
+CdModWorkspace carve_cd_mod(void* base, int64_t n, int64_t d, int kp) {
+  CdModWorkspace w;
+  Arena a(base);
+  w.G = a.take((size_t)kp * kp * 4);
+  w.Wt = a.take((size_t)kp * d * 4);
+  w.B0 = a.take((size_t)n * kp * 4);
+  w.row_sweeps = a.take<int>((size_t)n * 4);
+  w.row_conv = a.take<int>((size_t)n * 4);
+  w.row_commits = a.take<unsigned long long>((size_t)n * 8);
+  w.info = a.take<long long>(256);
+  w.bytes = a.bytes();
+  return w;
+}
+}  // namespace
+
+size_t lasso_cd_mod_workspace_bytes(int64_t n, int64_t d, int64_t k, int dtype) {
+  const int kp = pad_k_cd(k);
+  if (dtype != LASSO_F32 || kp < 0 || n < 0 || d <= 0) return 0;
+  return carve_cd_mod(nullptr, n, d, kp).bytes;
+}
+
+int lasso_cd_mod_solve(const void* x_dev, int64_t ldx, const void* w_dev, int64_t ldw, void* z_inout_dev, int64_t ldz,
+                       int z_has_start, float* gap_out_dev, int32_t* sweeps_out_dev, uint8_t* converged_out_dev,
+                       int64_t n, int64_t d, int64_t k, int dtype, double alpha, int max_iter, double tol,
+                       int32_t* n_unconverged_out, int64_t* committed_out, void* workspace_dev, size_t workspace_bytes,
+                       void* stream) {
+  if (int s = check_cd(n, d, k, dtype)) return s;
+  if (!w_dev || !workspace_dev || (n > 0 && (!x_dev || !z_inout_dev || !gap_out_dev)))
+    return fail(LASSO_ERR_BAD_ARG, "null pointer");
+  if (ldx < d || ldw < k || ldz < k) return fail(LASSO_ERR_BAD_ARG, "leading dimension too small");
+  if (max_iter < 0 || !(alpha >= 0.0) || tol != tol)
+    return fail(LASSO_ERR_BAD_ARG, "max_iter=%d alpha=%g tol=%g", max_iter, alpha, tol);
+  const int kp = pad_k_cd(k);
+  CdModWorkspace ws = carve_cd_mod(workspace_dev, n, d, kp);
+  if (workspace_bytes < ws.bytes) return fail(LASSO_ERR_WORKSPACE, "workspace %zu < %zu bytes", workspace_bytes, ws.bytes);
+  long long info[2] = {0, 0};
+  if (n > 0) {
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    // Wt [kp][d] (zero rows past k);  G = Wt Wt^T, whose diagonal holds the atoms' squared norms (:84);
+    // b0 = x Wt^T.  Padded columns of b0 and G are exact zeros, and so are the row and column of an all-zero atom.
+    LASSO_HIP_TRY(launch_transpose_pad((const float*)w_dev, ldw, (int)d, (int)k, ws.Wt, d, kp, (int)d, st));
+    LASSO_HIP_TRY(launch_gemm_nt_sub(ws.Wt, d, ws.Wt, d, nullptr, 0, ws.G, kp, kp, kp, (int)d, st, /*add=*/1));
+    LASSO_HIP_TRY(launch_gemm_nt_sub((const float*)x_dev, ldx, ws.Wt, d, nullptr, 0, ws.B0, kp, (int)n, kp, (int)d, st,
+                                     /*add=*/1));
+    CdModParams p;
+    p.x = (const float*)x_dev; p.ldx = ldx; p.B0 = ws.B0; p.G = ws.G;
+    p.z = (float*)z_inout_dev; p.ldz = ldz; p.has_start = z_has_start ? 1 : 0;
+    p.gap = gap_out_dev; p.sweeps_out = sweeps_out_dev; p.conv_out = converged_out_dev;
+    p.row_sweeps = ws.row_sweeps; p.row_conv = ws.row_conv; p.row_commits = ws.row_commits;
+    p.n = (int)n; p.d = (int)d; p.k = (int)k; p.max_iter = max_iter;
+    p.alpha = (float)alpha; p.tol = (float)tol; p.gap0 = (float)(tol + 1.0);     // :78
+    LASSO_HIP_TRY(launch_cd_mod_rows(p, kp, device_cus(), st));
+    if (n_unconverged_out || committed_out) {
+      LASSO_HIP_TRY(launch_cd_mod_info(ws.row_conv, ws.row_commits, (int)n, ws.info, st));
+      LASSO_HIP_TRY(hipMemcpyAsync(info, ws.info, sizeof(info), hipMemcpyDeviceToHost, st));
+      LASSO_HIP_TRY(hipStreamSynchronize(st));
+    }
+  }
+  if (n_unconverged_out) *n_unconverged_out = (int32_t)info[0];
+  if (committed_out) *committed_out = (int64_t)info[1];
+  return LASSO_OK;
+}
+
 // ---- convolutional ISTA/FISTA: lasso/conv2d/ista.py:7-49, lip_const.py:96-135 ----------
 size_t lasso_conv_ista_workspace_bytes(int64_t N, int64_t C, int64_t H, int64_t W, int64_t K, int64_t Hz,
                                        int64_t Wz, int kh, int kw, int sh, int sw, int ph, int pw) {

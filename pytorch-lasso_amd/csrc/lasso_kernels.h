@@ -153,6 +153,25 @@ struct CdParams {
   float alpha, tol;        // tol = absolute per-row threshold (reference: tol*k)
 };
 
+// cyclic coordinate descent with a duality-gap stop (cd_mod.hip): one launch solves every row
+struct CdModParams {
+  const float* x; int64_t ldx;   // [n][d] samples (only their squared norms are read)
+  const float* B0;               // [n][kp] b0 = x W (zero padded)
+  const float* G;                // [kp][kp] W^T W (zero padded, bitwise symmetric)
+  float* z; int64_t ldz;         // [n][k] code, in/out
+  int has_start;                 // 0: z is write-only (zero start)
+  float* gap;                    // [n]
+  int* sweeps_out;               // [n] nullable
+  unsigned char* conv_out;       // [n] nullable
+  int* row_sweeps; int* row_conv; unsigned long long* row_commits;   // [n] workspace copies for the host counts
+  int n, d, k, max_iter;
+  float alpha, tol, gap0;        // gap0 = tol + 1: the gap of a row that was never checked
+};
+hipError_t launch_cd_mod_rows(const CdModParams& p, int kp, int cus, hipStream_t stream);
+// info[0] = rows not converged, info[1] = coordinate updates with a nonzero change, summed in row order
+hipError_t launch_cd_mod_info(const int* row_conv, const unsigned long long* row_commits, int n, long long* info,
+                              hipStream_t stream);
+
 // convolutional ISTA (conv.hip): x [N][C][H][W], weight [K][C][kh][kw], code z [N][K][Hz][Wz]
 constexpr int kConvDpart = 64 * 1024;      // words of the convolutional solver's partial-sum buffer (lasso_hip.hip carves it;
                                            // conv_fused.hip plans against it: 64 iterations per launch x up to 1024 workgroups)

@@ -283,6 +283,11 @@ def _declare(lib):
     lib.lasso_cd_solve.restype = i32
     lib.lasso_cd_solve.argtypes = [vp, i64, vp, i64, vp, i64, vp, i64, i64, i64, i64, i32, dbl, i32,
                                    dbl, pi32, pi32, vp, sz, vp]
+    lib.lasso_cd_mod_workspace_bytes.restype = sz
+    lib.lasso_cd_mod_workspace_bytes.argtypes = [i64, i64, i64, i32]
+    lib.lasso_cd_mod_solve.restype = i32
+    lib.lasso_cd_mod_solve.argtypes = [vp, i64, vp, i64, vp, i64, i32, vp, vp, vp, i64, i64, i64, i32, dbl, i32,
+                                       dbl, pi32, C.POINTER(C.c_int64), vp, sz, vp]
 
 
 def lib():

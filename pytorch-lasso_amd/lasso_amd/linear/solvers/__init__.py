@@ -1,5 +1,6 @@
 """Mirror of lasso/linear/solvers/__init__.py:1,5 -- the solvers on the HIP path:
-'ista' (SURVEY.md section 8a), greedy coordinate descent 'cd' (8f row f2) and GPSR-Basic 'gpsr'."""
+'ista' (SURVEY.md section 8a), greedy coordinate descent 'cd' (8f row f2), GPSR-Basic 'gpsr', and the cyclic coordinate descent with a duality-gap
+stop, `coord_descent_mod`, which the reference exports beside them without routing it through sparse_encode."""
 from .ista import ista  # noqa: F401
-from .coordinate_descent import coord_descent  # noqa: F401
+from .coordinate_descent import coord_descent, coord_descent_mod  # noqa: F401
 from .gpsr import gpsr_basic  # noqa: F401
