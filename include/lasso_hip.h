@@ -39,7 +39,9 @@
  *     lasso_gram_accumulate take any d, k (unfused MFMA GEMM paths), lasso_dict_sweep
  *     d <= 1024 and k <= 4096, lasso_cd_* k <= 4096; lasso_fista_prepare/_run take any
  *     d, k too (unfused: state in HBM, kernel_hint ignored); lasso_fista_solve_sharded takes
- *     any d, k on fp32 tensors (bf16: fused shapes only).
+ *     any d, k on fp32 tensors (bf16: fused shapes only);
+ *   - GPSR-Basic has two entry points on one driver: lasso_gpsr_solve (the dictionary as the operator) and
+ *     lasso_conv_gpsr_solve (conv_transpose2d / conv2d as the operator, contiguous NCHW tensors); both LASSO_F32 only.
  */
 #ifndef LASSO_HIP_H_
 #define LASSO_HIP_H_
@@ -831,6 +833,32 @@ int lasso_gpsr_solve(const void* x_dev, int64_t ldx, const void* w_dev, int64_t 
                      void* z_out_dev, int64_t ldz, int64_t n, int64_t d, int64_t k, int dtype, double alpha,
                      const lasso_gpsr_options* options, lasso_gpsr_result* result,
                      void* workspace_dev, size_t workspace_bytes, void* stream);
+
+/* ---- convolutional GPSR-Basic: gpsr_basic(y, A, tau, AT, ...) of gpsr.py:209-365 with the closures
+ *        A  = lambda v: conv_transpose2d(v, W, stride, padding)      AT = lambda v: conv2d(v, W, stride, padding)
+ * min_z 0.5 |x - conv_transpose2d(z, W)|^2 + tau |z|_1 over the whole batch (csrc/conv_gpsr.hip): the loop, the decision
+ * kernels, options, result, trace and flag bits of lasso_gpsr_solve, on the convolutional operator.  Tensors are
+ * contiguous NCHW like the other lasso_conv_* entry points: x [N][C][H][W], W [K][C][kh][kw], z0 (nullable; only read)
+ * and z_out [N][K][Hz][Wz]; z_out may not alias an input.  The debias test "too many nonzeros" compares against the
+ * elements of x.  options->init: 0 (zeros) or 2 (conv2d(x, W)) when z0_dev is NULL; init 1 is the caller's to draw and
+ * pass as z0_dev (LASSO_ERR_UNSUPPORTED).
+ * Status: a geometry with (Hz-1) sh - 2 ph + kh != H (or the same for the width), a null pointer or a stop_criterion
+ * outside 0..4 is LASSO_ERR_BAD_ARG with nothing enqueued; a dtype other than LASSO_F32 is LASSO_ERR_UNSUPPORTED;
+ * N = 0 writes nothing.  The call blocks like lasso_gpsr_solve.  A problem whose code pixels N Hz Wz, K or
+ * C kh kw exceed 2^23 (32-bit offsets of a 64-row GEMM block) is LASSO_ERR_UNSUPPORTED.  _workspace_bytes returns 0 for
+ * every geometry the solve refuses.
+ * Two kernel families (csrc/conv_gpsr.hip): "implicit" where the implicit-GEMM kernels of lasso_conv_ista_solve cover
+ * the geometry (the rule of lasso_conv_ista_kernel_name: stride 1, few channels, 3/5/7 kernels, K a multiple of 4),
+ * "patches" (patch matrix + GEMM, GEMM + overlap-add) everywhere else.  Bit 0 of options->reserved forces "patches";
+ * lasso_conv_gpsr_form says which one a solve of that geometry with that `reserved` takes ("" for a refused geometry). */
+size_t lasso_conv_gpsr_workspace_bytes(int64_t N, int64_t C, int64_t H, int64_t W, int64_t K, int64_t Hz, int64_t Wz,
+                                       int kh, int kw, int sh, int sw, int ph, int pw);
+const char* lasso_conv_gpsr_form(int64_t N, int64_t C, int64_t H, int64_t W, int64_t K, int64_t Hz, int64_t Wz, int kh,
+                                 int kw, int sh, int sw, int ph, int pw, int reserved);
+int lasso_conv_gpsr_solve(const void* x_dev, const void* w_dev, const void* z0_dev, void* z_out_dev, int64_t N,
+                          int64_t C, int64_t H, int64_t W, int64_t K, int64_t Hz, int64_t Wz, int kh, int kw, int sh,
+                          int sw, int ph, int pw, int dtype, double tau, const lasso_gpsr_options* options,
+                          lasso_gpsr_result* result, void* workspace_dev, size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -153,6 +153,11 @@ struct ConvGradProx {
   int tv_shift;                 // TV = 1 << tv_shift
   float inv_plane, inv_rw;      // 1 / (RH RW), 1 / RW: exact index splits of e < 2^14 without integer division
 };
+// the GPSR instantiations take the GRAD epilogue's operands behind the same block: the ISTA instantiations keep their
+// kernel arguments, and with them their code
+struct ConvGradProxGpsr : ConvGradProx { ConvGradGpsr ge; };
+template <bool GPSR> struct CgpParams { typedef ConvGradProx type; };
+template <> struct CgpParams<true> { typedef ConvGradProxGpsr type; };
 // Dictionaries of at most 64 atoms (KW = 64; round 4): a 128-atom tile left two of the four waves multiplying
 // zeros and half of the epilogue's 16-byte pieces out of range, so the tile is turned to 128 pixels x 64 atoms --
 // waves 2 (pixel halves) x 2 (atom halves), the same 4 x 2 MFMA blocks per wave, every z / y piece of the epilogue real.
@@ -198,8 +203,12 @@ __device__ __forceinline__ void cgp_stage_field(float* __restrict__ S, const __a
   }
 }
 
-template <int S4, int KW, bool SKIP>     // SKIP: C kh kw <= 4 S4 - 4, the last MFMA steps would multiply zeros
-__global__ __launch_bounds__(256, cgp_occ(S4)) void conv_grad_prox_kernel(const ConvGradProx p) {
+// GPSR = true (conv_gpsr.hip, the implicit form of convolutional GPSR-Basic): the same implicit GEMM g = conv2d(R, W) with
+// GPSR's GRAD epilogue in place of the proximal step -- t = g - Ay, gu = t + tau, gv = tau - t, c = cu - cv; reads Ay, u, v,
+// writes t and c; per workgroup the partials {<gu,cu>, <gv,cv>, max|min(gu,u)|, max|min(gv,v)|, max|u|, max|v|} as doubles,
+// folded in a fixed order.  The ISTA instantiations (GPSR = false) compile to what they were.
+template <int S4, int KW, bool SKIP, bool GPSR = false>     // SKIP: C kh kw <= 4 S4 - 4, the last MFMA steps would multiply zeros
+__global__ __launch_bounds__(256, cgp_occ(S4)) void conv_grad_prox_kernel(const typename CgpParams<GPSR>::type p) {
   constexpr int TP = 8192 / KW;                             // code pixels of a tile: 64 (KW = 128), 128 (KW = 64), 256 (KW = 32)
   constexpr int kCgpGtLd = KW + 4;
   constexpr int NWA = KW / 32;                              // waves side by side along the atoms
@@ -257,6 +266,8 @@ __global__ __launch_bounds__(256, cgp_occ(S4)) void conv_grad_prox_kernel(const 
   const __amdgpu_buffer_rsrc_t zrsrc = __builtin_amdgcn_make_buffer_rsrc(p.Zm, 0, (int)zbytes, 0x00020000);
   const __amdgpu_buffer_rsrc_t yrsrc = __builtin_amdgcn_make_buffer_rsrc(p.Ym, 0, (int)zbytes, 0x00020000);
   float dsum = 0.0f;
+  double gs0 = 0.0, gs1 = 0.0;                              // GPSR only
+  float gm0 = 0.0f, gm1 = 0.0f, gm2 = 0.0f, gm3 = 0.0f;
   for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
     const int n = tile / tiles_img, tt = tile - n * tiles_img;
     const int u0 = (tt / p.tiles_v) * p.TU, v0 = (tt % p.tiles_v) * p.TV;
@@ -284,11 +295,13 @@ __global__ __launch_bounds__(256, cgp_occ(S4)) void conv_grad_prox_kernel(const 
         const int col = KW * blockIdx.y + c4;
         const bool ok = u < g.Hz && v < g.Wz && col < K;
         zoff[h] = ok ? (unsigned)(((n * g.Hz + u) * g.Wz + v) * K + col) * 4u : ~0u;
+        if constexpr (!GPSR) {
 #ifdef LASSO_ABL_CONV_NOMEM    // timing ablation only (results invalid)
         yo[h] = (f32x4){0.f, 0.f, 0.f, (float)zoff[h]};
 #else
         yo[h] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(yrsrc, zoff[h], 0, 0));
 #endif
+        }
       }
     }
     LDS_BARRIER();
@@ -316,7 +329,29 @@ __global__ __launch_bounds__(256, cgp_occ(S4)) void conv_grad_prox_kernel(const 
 #pragma unroll
         for (int rg = 0; rg < 4; ++rg) Gt[(64 * wp + 16 * mt + 4 * q + rg) * kCgpGtLd + 32 * wa + 16 * nt + l15] = acc[mt][nt][rg];
     LDS_BARRIER();
-    if (kvec) {
+    if constexpr (GPSR) {
+      // every element of the tile: one at a time (Ay, u, v, t, c are [M][K] like z; no 16-byte pieces needed for K % 4 != 0)
+      for (int idx = tid; idx < TP * KW; idx += 256) {
+        const int pix = idx / KW, cc = idx - pix * KW;
+        const int u = u0 + (pix >> p.tv_shift), v = v0 + (pix & (p.TV - 1));
+        const int col = KW * blockIdx.y + cc;
+        if (u >= g.Hz || v >= g.Wz || col >= K) continue;
+        const int64_t e = (((int64_t)n * g.Hz + u) * g.Wz + v) * K + col;
+        const float t = __fsub_rn(Gt[pix * kCgpGtLd + cc], p.ge.Ay[e]);
+        const float gu = __fadd_rn(t, p.ge.tau), gv = __fadd_rn(-t, p.ge.tau);
+        const float uu = p.ge.U[e], vv = p.ge.V[e];
+        const float cu = (uu <= 0.0f && gu >= 0.0f) ? 0.0f : gu;
+        const float cv = (vv <= 0.0f && gv >= 0.0f) ? 0.0f : gv;
+        gs0 += __fmul_rn(gu, cu);
+        gs1 += __fmul_rn(gv, cv);
+        gm0 = fmaxf(gm0, fabsf(fminf(gu, uu)));
+        gm1 = fmaxf(gm1, fabsf(fminf(gv, vv)));
+        gm2 = fmaxf(gm2, fabsf(uu));
+        gm3 = fmaxf(gm3, fabsf(vv));
+        p.ge.T[e] = t;
+        p.ge.Cc[e] = __fsub_rn(cu, cv);
+      }
+    } else if (kvec) {
       f32x4 zo[8];
 #pragma unroll
       for (int h = 0; h < 8; ++h)
@@ -370,6 +405,22 @@ __global__ __launch_bounds__(256, cgp_occ(S4)) void conv_grad_prox_kernel(const 
       }
     }
     LDS_BARRIER();
+  }
+  if constexpr (GPSR) {
+    __shared__ double gred[256];
+    double vals[6] = {gs0, gs1, (double)gm0, (double)gm1, (double)gm2, (double)gm3};
+    double* const out = p.ge.part + (int64_t)(blockIdx.y * gridDim.x + blockIdx.x) * 8;
+    for (int i = 0; i < 6; ++i) {
+      __syncthreads();
+      gred[tid] = vals[i];
+      __syncthreads();
+      for (int st = 128; st > 0; st >>= 1) {
+        if (tid < st) gred[tid] = i < 2 ? gred[tid] + gred[tid + st] : fmax(gred[tid], gred[tid + st]);
+        __syncthreads();
+      }
+      if (tid == 0) out[i] = gred[0];
+    }
+    return;
   }
   red[tid] = dsum;
   __syncthreads();
@@ -568,7 +619,7 @@ hipError_t launch_conv_gradient(const float* r, const float* Wp, float* rc, int 
 // the caller has to take the explicit path.
 hipError_t launch_conv_grad_prox(const float* r, const float* Wp, int ldr, float* Zm, float* Ym, float lr, float lam,
                                  float coef, float* dpart, int dpart_cap, const ConvGeom& g, int cus, int* count,
-                                 hipStream_t stream, int dry) {
+                                 hipStream_t stream, int dry, const ConvGradGpsr* gpsr) {
   *count = 0;
   const int ckk = g.C * g.kh * g.kw;
   if (ckk > 192) return hipSuccess;
@@ -600,6 +651,9 @@ hipError_t launch_conv_grad_prox(const float* r, const float* Wp, int ldr, float
   p.tiles_u = (g.Hz + p.TU - 1) / p.TU;
   p.tiles_v = (g.Wz + p.TV - 1) / p.TV;
   p.R = r; p.Wp = Wp; p.ldr = ldr; p.Zm = Zm; p.Ym = Ym; p.lr = lr; p.lam = lam; p.coef = coef; p.dpart = dpart; p.g = g;
+  ConvGradProxGpsr pg;
+  static_cast<ConvGradProx&>(pg) = p;
+  pg.ge = gpsr ? *gpsr : ConvGradGpsr{};
   const int64_t ntiles = (int64_t)g.N * p.tiles_u * p.tiles_v;
   const int gy = (g.K + kw - 1) / kw;
   const int s4 = ckk <= 64 ? 16 : ckk <= 96 ? 24 : ckk <= 144 ? 36 : 48;
@@ -613,9 +667,13 @@ hipError_t launch_conv_grad_prox(const float* r, const float* Wp, int ldr, float
   const dim3 grid(gx, gy);
   const bool skip = ckk <= 4 * s4 - 4;
 #define LASSO_CGP_CASE2(S4_, KW_, SK_)                                                                       \
-  if (s4 == S4_ && kw == KW_ && skip == SK_) {                                                               \
+  if (s4 == S4_ && kw == KW_ && skip == SK_ && !gpsr) {                                                      \
     if (hipError_t e = ensure_dynamic_lds((const void*)&conv_grad_prox_kernel<S4_, KW_, SK_>, lds); e != hipSuccess) return e; \
     hipLaunchKernelGGL((conv_grad_prox_kernel<S4_, KW_, SK_>), grid, dim3(256), lds, stream, p);             \
+  }                                                                                                          \
+  if (s4 == S4_ && kw == KW_ && skip == SK_ && gpsr) {                                                       \
+    if (hipError_t e = ensure_dynamic_lds((const void*)&conv_grad_prox_kernel<S4_, KW_, SK_, true>, lds); e != hipSuccess) return e; \
+    hipLaunchKernelGGL((conv_grad_prox_kernel<S4_, KW_, SK_, true>), grid, dim3(256), lds, stream, pg);      \
   }
 #define LASSO_CGP_CASE(S4_, KW_) LASSO_CGP_CASE2(S4_, KW_, false) LASSO_CGP_CASE2(S4_, KW_, true)
   LASSO_CGP_CASE(16, 128) LASSO_CGP_CASE(24, 128) LASSO_CGP_CASE(36, 128) LASSO_CGP_CASE(48, 128)

@@ -1,631 +1,60 @@
-// GPSR-Basic (Figueiredo, Nowak, Wright 2007; the reference's lasso/linear/solvers/gpsr.py) on the fp32 MFMA GEMM:
-// gradient projection on the split z = u - v, u, v >= 0 of  min 0.5 |y - z W^T|^2 + tau |z|_1  over the whole batch.
-//
-// Every [n,k] x [k,d]-class product is the main loop of gemm.hip (gemm_mainloop.hpp) with an epilogue of its own, so no
-// [n,k] / [n,d] intermediate makes a trip through HBM that an epilogue can absorb:
-//   EPI_GRAD   t = rb W - Ay on the accumulators; reads u, v, writes t (gu = t + tau, gv = tau - t: one array gives both)
-//              and c = cu - cv, block partials of <gu,cu>, <gv,cv> and the four infinity norms of the LCP criterion
-//   EPI_SUMSQ  |c W^T|^2: block partials only, the [n,d] product never reaches memory
-//   EPI_RESID  rb+ = z+ W^T stored, block partials of |y - rb+|^2; blockIdx.z = rung of the step-size ladder
-//   EPI_STORE / EPI_RESID0 / EPI_MASK_R / EPI_MASK_AP: Ay, and the two products of the debias CG with the support mask
-// All sums: per-thread, wave butterfly, the four waves, block partial (double) -- then ONE workgroup folds the partials
-// in a fixed order (no float atomics: two solves of the same arguments are bitwise equal).  The scalars that steer the
-// iteration (lambda, the sufficient-decrease test, the stop criterion) are computed by those one-workgroup kernels with
-// the reference's fp32 operation order and land in a control block that the host reads ONCE per outer iteration: the
-// first trial, its decision, the accept step and the criterion are all enqueued behind the gradient; only a rejected
-// first trial costs another wait, for a ladder of kLadder further step sizes evaluated in one batch.
-#include <hip/hip_runtime.h>
-#include <math.h>
-#include <stdint.h>
-#include <stdio.h>
-#include <string.h>
-#include <algorithm>
-#include <vector>
-
-#include "../../include/lasso_hip.h"
-#include "lasso_kernels.h"
-#include "host_util.hpp"
-#include "gemm_mainloop.hpp"
+// GPSR-Basic on the dictionary (the reference's lasso/linear/solvers/gpsr.py with A z = z W^T, AT r = r W): the operator
+// that gpsr_driver.hpp's host loop is instantiated with for lasso_gpsr_solve.  Every [n,k] x [k,d]-class product is ONE
+// launch of the driver's GEMM with the epilogue the loop asks for; the kernels, the control block and the loop itself
+// are in the header and serve the convolutional operator of conv_gpsr.hip as well.
+#include "gpsr_driver.hpp"
 
 namespace lasso {
 namespace gpsr {
 namespace {
 
-using gemm_detail::f32x4;
+// y = x [n][d] (pitch ldx), the code [n][k], the dictionary w [d][k] (pitch ldw) and its transpose Wt [k][d]
+struct LinearOp {
+  // what the loop reads
+  int rows, cols;
+  int64_t nd;
+  int pk, pd;
+  const float* y; int64_t ldy; int y_rows, y_cols;
+  const float* start; int64_t ld_start;
+  // the operator's own
+  const float* w; int64_t ldw;
+  float* Wt;
+  float* zout; int64_t ldz;
+  int d, side_k, side_d;
 
-constexpr int kLadder = 4;            // step sizes per batch behind a rejected first trial
-constexpr int kMaxReductions = 100;   // the line search gives up after this many reductions of lambda
-constexpr int kPart = 8;              // doubles per block partial
-constexpr int kEwBlocks = 1024;       // most blocks of an element-wise launch
+  hipError_t prepare(hipStream_t st) const { return launch_transpose_pad(w, ldw, d, cols, Wt, d, cols, d, st); }
 
-enum { EPI_STORE = 0, EPI_GRAD, EPI_SUMSQ, EPI_RESID, EPI_RESID0, EPI_MASK_R, EPI_MASK_AP };
+  // AT(img) = img W: [n,d] x [d,k]; the data itself has the caller's pitch, every other image is packed
+  template <int MODE>
+  hipError_t at(const float* img, const Epi& ep, hipStream_t st) const {
+    return launch_gemm<MODE>(img, img == y ? ldy : (int64_t)d, Wt, d, rows, cols, d, ep, side_k, 1, st);
+  }
 
-// control block (device; copied to the host once per outer iteration)
-struct Ctl {
-  float f, f_prev, lam0, lam_acc;
-  float crit3, crit, ssdx, ssz;
-  int accept, bad, nz, dnz;
-  float fnew[kLadder], bound[kLadder];
-  float absmax, rr, l1, f0;
-  // debias CG
-  float rtr, thresh, alpha_cg, beta_cg;
-  float f_db, rr_db, conv_db; int nz_db;
-  int nz0; float rr_rb; int pad[2];
+  // A(code) = code W^T: [n,k] x [k,d]
+  template <int MODE>
+  hipError_t a(const float* code, Epi ep, int rungs, hipStream_t st) const {
+    ep.Y = y; ep.ldy = ldy; ep.ldo = d;
+    return launch_gemm<MODE>(code, cols, w, ldw, rows, d, cols, ep, side_d, rungs, st);
+  }
+
+  hipError_t write_out(const float* Z, int zero, hipStream_t st) const {
+    hipLaunchKernelGGL(copy_out_kernel, dim3(ew_grid((int64_t)rows * cols)), dim3(256), 0, st, Z, zout, ldz, rows, cols, zero);
+    return hipGetLastError();
+  }
 };
 
-struct Epi {
-  const float* Ay; const float* U; const float* V;   // GRAD
-  float* T; float* Cc;                               // GRAD out (ld = nn)
-  const float* Y; int64_t ldy;                       // RESID / RESID0: the data x [m][nn]
-  float* Out; int64_t ldo; int64_t out_stride;       // STORE / RESID / RESID0 / MASK_*: the product (per rung: + z * out_stride)
-  const float* Mask;                                 // MASK_*: 1 where the code is off the support
-  float* P;                                          // MASK_R: -r out; MASK_AP: p in
-  int64_t a_stride;                                  // per rung offset of the A operand
-  double* part;                                      // [blocks][kPart]
-  float tau;
-};
-
-// sums s[NS] and maxima mx[NM] of a block of 256 threads in a fixed order -> out[NS + NM] by thread 0
-template <int NS, int NM>
-__device__ __forceinline__ void block_fold(double (&s)[NS > 0 ? NS : 1], float (&mx)[NM > 0 ? NM : 1], double* red /* [4][8] */,
-                                           double* out) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-#pragma unroll
-    for (int i = 0; i < NS; ++i) s[i] += __shfl_xor(s[i], off);
-#pragma unroll
-    for (int i = 0; i < NM; ++i) mx[i] = fmaxf(mx[i], __shfl_xor(mx[i], off));
-  }
-  __syncthreads();
-  if (lane == 0) {
-#pragma unroll
-    for (int i = 0; i < NS; ++i) red[w * 8 + i] = s[i];
-#pragma unroll
-    for (int i = 0; i < NM; ++i) red[w * 8 + NS + i] = (double)mx[i];
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-#pragma unroll
-    for (int i = 0; i < NS; ++i) out[i] = (red[i] + red[8 + i]) + (red[16 + i] + red[24 + i]);
-#pragma unroll
-    for (int i = 0; i < NM; ++i) out[NS + i] = fmax(fmax(red[NS + i], red[8 + NS + i]), fmax(red[16 + NS + i], red[24 + NS + i]));
-  }
-}
-
-// C = A B^T on the block (blockIdx.y, blockIdx.x), rung blockIdx.z; A [m][kk], B [nn][kk]
-template <int BM, int BN, bool VEC, bool DMA, int MODE>
-__global__ __launch_bounds__(256, 2) void gpsr_gemm_kernel(const float* __restrict__ A, int64_t lda,
-                                                           const float* __restrict__ B, int64_t ldb, int m, int nn,
-                                                           int kk, Epi ep) {
-  constexpr int MI = BM / 32, NJ = BN / 32;
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int i0 = blockIdx.y * BM, j0 = blockIdx.x * BN;
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const int wr = w >> 1, wc = w & 1;
-  const int l15 = lane & 15, q = lane >> 4;
-  A += (int64_t)blockIdx.z * ep.a_stride;
-  f32x4 acc[MI][NJ] = {};
-  gemm_detail::gemm_nt_accumulate<BM, BN, VEC, DMA>(A, lda, B, ldb, m, nn, kk, i0, j0, smem, acc);
-  // the epilogue's operands through buffer descriptors of the tile's rows, as in gemm.hip: out of range reads 0 and
-  // drops the store
-  const int rows_valid = min(BM, m - i0);
-  auto tile_rsrc = [&](const float* base, int64_t ld) {
-    const int64_t bytes = (int64_t)rows_valid * ld * 4;
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(base + (int64_t)i0 * ld), 0,
-                                             (int)(bytes < 0x7fffffff ? bytes : 0x7fffffff), 0x00020000);
-  };
-  auto tile_off = [&](int rl, int cc, int64_t ld) {
-    unsigned o = (rl < rows_valid && cc < nn) ? (unsigned)(rl * (int)ld + cc) * 4u : 0xfffffff0u;
-    asm volatile("" : "+v"(o));
-    return o;
-  };
-  auto ld32 = [](__amdgpu_buffer_rsrc_t rs, unsigned o) {
-    return __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs, o, 0, 0));
-  };
-  auto st32 = [](float v, __amdgpu_buffer_rsrc_t rs, unsigned o) {
-    __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), rs, o, 0, 0);
-  };
-  double s[2] = {0.0, 0.0};
-  float mx[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-  float s0 = 0.0f, s1 = 0.0f;
-  const int64_t ldn = nn;
-#pragma unroll
-  for (int mi = 0; mi < MI; ++mi) {
-    unsigned o[NJ][4];
-#pragma unroll
-    for (int nj = 0; nj < NJ; ++nj)
-#pragma unroll
-      for (int rg = 0; rg < 4; ++rg)
-        o[nj][rg] = tile_off((BM / 2) * wr + 16 * mi + 4 * q + rg, j0 + (BN / 2) * wc + 16 * nj + l15, ldn);
-    if constexpr (MODE == EPI_GRAD) {
-      const __amdgpu_buffer_rsrc_t ars = tile_rsrc(ep.Ay, ldn), urs = tile_rsrc(ep.U, ldn), vrs = tile_rsrc(ep.V, ldn);
-      const __amdgpu_buffer_rsrc_t trs = tile_rsrc(ep.T, ldn), crs = tile_rsrc(ep.Cc, ldn);
-      float ay[NJ][4], u[NJ][4], v[NJ][4];
-#pragma unroll
-      for (int nj = 0; nj < NJ; ++nj)
-#pragma unroll
-        for (int rg = 0; rg < 4; ++rg) {
-          ay[nj][rg] = ld32(ars, o[nj][rg]);
-          u[nj][rg] = ld32(urs, o[nj][rg]);
-          v[nj][rg] = ld32(vrs, o[nj][rg]);
-        }
-#pragma unroll
-      for (int nj = 0; nj < NJ; ++nj)
-#pragma unroll
-        for (int rg = 0; rg < 4; ++rg) {
-          const bool in = o[nj][rg] != 0xfffffff0u;
-          const float t = __fsub_rn(acc[mi][nj][rg], ay[nj][rg]);
-          const float gu = __fadd_rn(t, ep.tau), gv = __fadd_rn(-t, ep.tau);
-          const float uu = u[nj][rg], vv = v[nj][rg];
-          const float cu = (uu <= 0.0f && gu >= 0.0f) ? 0.0f : gu;
-          const float cv = (vv <= 0.0f && gv >= 0.0f) ? 0.0f : gv;
-          if (in) {
-            s0 += __fmul_rn(gu, cu);
-            s1 += __fmul_rn(gv, cv);
-            mx[0] = fmaxf(mx[0], fabsf(fminf(gu, uu)));
-            mx[1] = fmaxf(mx[1], fabsf(fminf(gv, vv)));
-            mx[2] = fmaxf(mx[2], fabsf(uu));
-            mx[3] = fmaxf(mx[3], fabsf(vv));
-          }
-          st32(t, trs, o[nj][rg]);
-          st32(__fsub_rn(cu, cv), crs, o[nj][rg]);
-        }
-    } else if constexpr (MODE == EPI_SUMSQ) {
-#pragma unroll
-      for (int nj = 0; nj < NJ; ++nj)
-#pragma unroll
-        for (int rg = 0; rg < 4; ++rg)       // (the LDS-DMA form clamps rows beyond the operand instead of zeroing them)
-          if (o[nj][rg] != 0xfffffff0u) s0 += __fmul_rn(acc[mi][nj][rg], acc[mi][nj][rg]);
-    } else if constexpr (MODE == EPI_STORE) {
-      const __amdgpu_buffer_rsrc_t ors = tile_rsrc(ep.Out, ep.ldo);
-#pragma unroll
-      for (int nj = 0; nj < NJ; ++nj)
-#pragma unroll
-        for (int rg = 0; rg < 4; ++rg) {
-          const int rl = (BM / 2) * wr + 16 * mi + 4 * q + rg, cc = j0 + (BN / 2) * wc + 16 * nj + l15;
-          st32(acc[mi][nj][rg], ors, tile_off(rl, cc, ep.ldo));
-        }
-    } else if constexpr (MODE == EPI_RESID || MODE == EPI_RESID0) {
-      // RESID: store rb+, sum (y - rb+)^2;  RESID0 (debias): store rb - y, sum of its squares
-      const __amdgpu_buffer_rsrc_t yrs = tile_rsrc(ep.Y, ep.ldy);
-      const __amdgpu_buffer_rsrc_t ors = tile_rsrc(ep.Out + (int64_t)blockIdx.z * ep.out_stride, ep.ldo);
-      float y[NJ][4];
-      unsigned oo[NJ][4];
-#pragma unroll
-      for (int nj = 0; nj < NJ; ++nj)
-#pragma unroll
-        for (int rg = 0; rg < 4; ++rg) {
-          const int rl = (BM / 2) * wr + 16 * mi + 4 * q + rg, cc = j0 + (BN / 2) * wc + 16 * nj + l15;
-          y[nj][rg] = ld32(yrs, tile_off(rl, cc, ep.ldy));
-          oo[nj][rg] = tile_off(rl, cc, ep.ldo);
-        }
-#pragma unroll
-      for (int nj = 0; nj < NJ; ++nj)
-#pragma unroll
-        for (int rg = 0; rg < 4; ++rg) {
-          const float r = MODE == EPI_RESID ? __fsub_rn(y[nj][rg], acc[mi][nj][rg]) : __fsub_rn(acc[mi][nj][rg], y[nj][rg]);
-          if (oo[nj][rg] != 0xfffffff0u) s0 += __fmul_rn(r, r);
-          st32(MODE == EPI_RESID ? acc[mi][nj][rg] : r, ors, oo[nj][rg]);
-        }
-    } else {                                   // EPI_MASK_R, EPI_MASK_AP
-      const __amdgpu_buffer_rsrc_t mrs = tile_rsrc(ep.Mask, ldn), ors = tile_rsrc(ep.Out, ldn), prs = tile_rsrc(ep.P, ldn);
-      float mk[NJ][4], p[NJ][4];
-#pragma unroll
-      for (int nj = 0; nj < NJ; ++nj)
-#pragma unroll
-        for (int rg = 0; rg < 4; ++rg) {
-          mk[nj][rg] = ld32(mrs, o[nj][rg]);
-          p[nj][rg] = MODE == EPI_MASK_AP ? ld32(prs, o[nj][rg]) : 0.0f;
-        }
-#pragma unroll
-      for (int nj = 0; nj < NJ; ++nj)
-#pragma unroll
-        for (int rg = 0; rg < 4; ++rg) {
-          const float val = mk[nj][rg] != 0.0f ? 0.0f : acc[mi][nj][rg];
-          st32(val, ors, o[nj][rg]);
-          const bool in = o[nj][rg] != 0xfffffff0u;
-          if constexpr (MODE == EPI_MASK_R) {
-            st32(-val, prs, o[nj][rg]);
-            if (in) s0 += __fmul_rn(val, val);
-          } else {
-            if (in) s0 += __fmul_rn(p[nj][rg], val);
-          }
-        }
-    }
-  }
-  if constexpr (MODE != EPI_STORE) {
-    s[0] = (double)s0;
-    s[1] = (double)s1;
-    double* const out = ep.part + ((int64_t)(blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x) * kPart;
-    block_fold<2, 4>(s, mx, reinterpret_cast<double*>(smem), out);
-  }
-}
-
-// ---- one-workgroup folds of the block partials (fixed order) --------------------------------------------------------
-// out[i] (shared) = sum (i < ns) or max over the blocks' partial i
-__device__ __forceinline__ void fold_partials(const double* __restrict__ part, int nblocks, int ns, int nm, double* red /* [256] */,
-                                              double* out /* [kPart] */) {
-  for (int i = 0; i < ns + nm; ++i) {
-    double a = 0.0;
-    for (int b = threadIdx.x; b < nblocks; b += 256) {
-      const double v = part[(int64_t)b * kPart + i];
-      a = i < ns ? a + v : fmax(a, v);
-    }
-    red[threadIdx.x] = a;
-    __syncthreads();
-    for (int h = 128; h > 0; h >>= 1) {
-      if ((int)threadIdx.x < h) red[threadIdx.x] = i < ns ? red[threadIdx.x] + red[threadIdx.x + h] : fmax(red[threadIdx.x], red[threadIdx.x + h]);
-      __syncthreads();
-    }
-    if (threadIdx.x == 0) out[i] = red[0];
-    __syncthreads();
-  }
-}
-
-// start of a solve / continuation step: f = 0.5 |y - rb|^2 + tau (sum u + sum v); nz of the start
-__global__ __launch_bounds__(256) void start_kernel(const double* __restrict__ part_r, int nb_r, const double* __restrict__ part_uv,
-                                                    int nb_uv, float tau, Ctl* __restrict__ ctl) {
-  __shared__ double red[256], a[kPart], b[kPart];
-  fold_partials(part_r, nb_r, 1, 0, red, a);
-  fold_partials(part_uv, nb_uv, 3, 0, red, b);
-  if (threadIdx.x == 0) {
-    const float f = __fadd_rn(__fmul_rn(0.5f, (float)a[0]), __fmul_rn(tau, __fadd_rn((float)b[0], (float)b[1])));
-    ctl->f = f;
-    ctl->f_prev = f;
-    ctl->f0 = f;
-    ctl->nz0 = (int)b[2];
-    ctl->bad = 0;
-  }
-}
-
-// lambda0 = (<gu,cu> + <gv,cv>) / (|c W^T|^2 + 1e-7); the LCP criterion of this iterate
-__global__ __launch_bounds__(256) void lambda_kernel(const double* __restrict__ part_g, int nb_g, const double* __restrict__ part_q,
-                                                     int nb_q, Ctl* __restrict__ ctl) {
-  __shared__ double red[256], g[kPart], qq[kPart];
-  fold_partials(part_g, nb_g, 2, 4, red, g);
-  fold_partials(part_q, nb_q, 1, 0, red, qq);
-  if (threadIdx.x == 0) {
-    const float num = __fadd_rn((float)g[0], (float)g[1]);
-    const float den = __fadd_rn((float)qq[0], 1e-7f);
-    ctl->lam0 = __fdiv_rn(num, den);
-    const float numer = fmaxf((float)g[2], (float)g[3]);
-    const float denom = fmaxf(fmaxf((float)g[4], (float)g[5]), 1e-6f);
-    ctl->crit3 = __fdiv_rn(numer, denom);
-    ctl->accept = -1;
-  }
-}
-
-__device__ __forceinline__ float rung_lambda(float lam0, float beta, int rung) {
-  float lam = lam0;
-  for (int j = 0; j < rung; ++j) lam = __fmul_rn(lam, beta);     // the reference's lambd = lambd * lambda_backtrack
-  return lam;
-}
-
-struct Step { float du, dv, un, vn; };
-__device__ __forceinline__ Step take_step(float u, float v, float t, float tau, float lam) {
-  const float gu = __fadd_rn(t, tau), gv = __fadd_rn(-t, tau);
-  Step s;
-  s.du = __fsub_rn(fmaxf(__fsub_rn(u, __fmul_rn(lam, gu)), 0.0f), u);
-  s.dv = __fsub_rn(fmaxf(__fsub_rn(v, __fmul_rn(lam, gv)), 0.0f), v);
-  s.un = __fadd_rn(u, s.du);
-  s.vn = __fadd_rn(v, s.dv);
-  return s;
-}
-
-// candidates of rungs first + blockIdx.y: z+ = z + (du - dv); partials {sum u+, sum v+, <gu,du>, <gv,dv>}
-__global__ __launch_bounds__(256) void trial_kernel(const float* __restrict__ U, const float* __restrict__ V,
-                                                    const float* __restrict__ T, const float* __restrict__ Z,
-                                                    float* __restrict__ Zc, int64_t total, float tau, float beta, int first,
-                                                    const Ctl* __restrict__ ctl, double* __restrict__ part) {
-  __shared__ double red[32];
-  if (first > 0 && ctl->accept >= 0) return;
-  const float lam = rung_lambda(ctl->lam0, beta, first + blockIdx.y);
-  float* const zc = Zc + (int64_t)blockIdx.y * total;
-  double s[4] = {0.0, 0.0, 0.0, 0.0};
-  float nomax[1] = {0.0f};
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
-    const float u = U[i], v = V[i], t = T[i];
-    const Step st = take_step(u, v, t, tau, lam);
-    zc[i] = __fadd_rn(Z[i], __fsub_rn(st.du, st.dv));
-    s[0] += (double)st.un;
-    s[1] += (double)st.vn;
-    s[2] += (double)__fmul_rn(__fadd_rn(t, tau), st.du);
-    s[3] += (double)__fmul_rn(__fadd_rn(-t, tau), st.dv);
-  }
-  block_fold<4, 0>(s, nomax, red, part + ((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * kPart);
-}
-
-// the sufficient-decrease test of `count` rungs in the reference's order: the first with f+ <= f + mu g is accepted
-__global__ __launch_bounds__(256) void decide_kernel(const double* __restrict__ part_t, int nb_t, const double* __restrict__ part_r,
-                                                     int nb_r, int first, int count, float tau, float mu, float beta,
-                                                     Ctl* __restrict__ ctl) {
-  __shared__ double red[256], t[kPart], r[kPart];
-  if (first > 0 && ctl->accept >= 0) return;
-  for (int j = 0; j < count; ++j) {
-    fold_partials(part_t + (int64_t)j * nb_t * kPart, nb_t, 4, 0, red, t);
-    fold_partials(part_r + (int64_t)j * nb_r * kPart, nb_r, 1, 0, red, r);
-    if (threadIdx.x == 0 && ctl->accept < 0 && !ctl->bad) {
-      const float fnew = __fadd_rn(__fmul_rn(0.5f, (float)r[0]), __fmul_rn(tau, __fadd_rn((float)t[0], (float)t[1])));
-      const float bound = __fadd_rn(ctl->f, __fmul_rn(mu, __fadd_rn((float)t[2], (float)t[3])));
-      ctl->fnew[j] = fnew;
-      ctl->bound[j] = bound;
-      if (fnew <= bound) {
-        ctl->accept = first + j;
-        ctl->lam_acc = rung_lambda(ctl->lam0, beta, first + j);
-        ctl->f_prev = ctl->f;
-        ctl->f = fnew;
-      } else if (!isfinite(fnew)) {
-        ctl->bad = 1;
-      }
-    }
-    __syncthreads();
-  }
-}
-
-// accept step: u, v without their common part, z = u - v; partials {nz, changed pattern, |dz|^2, |z|^2}
-__global__ __launch_bounds__(256) void finish_kernel(float* __restrict__ U, float* __restrict__ V, const float* __restrict__ T,
-                                                     float* __restrict__ Z, int64_t total, float tau,
-                                                     const Ctl* __restrict__ ctl, double* __restrict__ part) {
-  __shared__ double red[32];
-  if (ctl->accept < 0) return;
-  const float lam = ctl->lam_acc;
-  double s[4] = {0.0, 0.0, 0.0, 0.0};
-  float nomax[1] = {0.0f};
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
-    const Step st = take_step(U[i], V[i], T[i], tau, lam);
-    const float mn = fminf(st.un, st.vn);
-    const float u = __fsub_rn(st.un, mn), v = __fsub_rn(st.vn, mn);
-    const float zn = __fsub_rn(u, v), dz = __fsub_rn(st.du, st.dv);
-    const bool was = Z[i] != 0.0f, is = zn != 0.0f;
-    s[0] += is ? 1.0 : 0.0;
-    s[1] += was != is ? 1.0 : 0.0;
-    s[2] += (double)__fmul_rn(dz, dz);
-    s[3] += (double)__fmul_rn(zn, zn);
-    U[i] = u;
-    V[i] = v;
-    Z[i] = zn;
-  }
-  block_fold<4, 0>(s, nomax, red, part + (int64_t)blockIdx.x * kPart);
-}
-
-// the iteration's stop criterion (gpsr.py:85-117)
-__global__ __launch_bounds__(256) void criterion_kernel(const double* __restrict__ part, int nb, int crit_id, Ctl* __restrict__ ctl) {
-  __shared__ double red[256], a[kPart];
-  if (ctl->accept < 0) return;
-  fold_partials(part, nb, 4, 0, red, a);
-  if (threadIdx.x == 0) {
-    ctl->nz = (int)a[0];
-    ctl->dnz = (int)a[1];
-    ctl->ssdx = (float)a[2];
-    ctl->ssz = (float)a[3];
-    float c;
-    if (crit_id == 0) c = a[0] >= 1.0 ? (float)a[1] : -INFINITY;
-    else if (crit_id == 1) c = __fdiv_rn(fabsf(__fsub_rn(ctl->f, ctl->f_prev)), ctl->f_prev);
-    else if (crit_id == 2) c = __fdiv_rn(__fsqrt_rn((float)a[2]), __fsqrt_rn((float)a[3]));
-    else if (crit_id == 3) c = ctl->crit3;
-    else c = ctl->f;
-    ctl->crit = c;
-  }
-}
-
-// z = start (z0, Ay or zeros) unless keep_z; u = relu(start), v = relu(-start); partials {sum u, sum v, nz of z}
-__global__ __launch_bounds__(256) void init_kernel(const float* __restrict__ S, int64_t lds_, float* __restrict__ Z,
-                                                   float* __restrict__ U, float* __restrict__ V, int n, int k, int keep_z,
-                                                   double* __restrict__ part) {
-  __shared__ double red[32];
-  double s[3] = {0.0, 0.0, 0.0};
-  float nomax[1] = {0.0f};
-  const int64_t total = (int64_t)n * k;
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
-    const float x = S ? S[(i / k) * lds_ + (i % k)] : 0.0f;
-    const float u = fmaxf(x, 0.0f), v = fmaxf(-x, 0.0f);
-    U[i] = u;
-    V[i] = v;
-    if (!keep_z) Z[i] = x;
-    s[0] += (double)u;
-    s[1] += (double)v;
-    s[2] += (keep_z ? Z[i] : x) != 0.0f ? 1.0 : 0.0;
-  }
-  block_fold<3, 0>(s, nomax, red, part + (int64_t)blockIdx.x * kPart);
-}
-
-// max |a|, sum |a|, nonzeros of a [total]; (mask != null) mask = 1 where a == 0
-__global__ __launch_bounds__(256) void absstat_kernel(const float* __restrict__ a, int64_t total, float* __restrict__ mask,
-                                                      double* __restrict__ part) {
-  __shared__ double red[32];
-  double s[2] = {0.0, 0.0};
-  float mx[1] = {0.0f};
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
-    const float v = fabsf(a[i]);
-    s[0] += (double)v;
-    s[1] += v != 0.0f ? 1.0 : 0.0;
-    mx[0] = fmaxf(mx[0], v);
-    if (mask) mask[i] = v == 0.0f ? 1.0f : 0.0f;
-  }
-  block_fold<2, 1>(s, mx, red, part + (int64_t)blockIdx.x * kPart);
-}
-
-// ctl->l1 / nz_db / absmax from absstat partials; (part_r) ctl->rr = the sum of squares a product's epilogue left
-__global__ __launch_bounds__(256) void stat_kernel(const double* __restrict__ part, int nb, const double* __restrict__ part_r, int nb_r,
-                                                   Ctl* __restrict__ ctl) {
-  __shared__ double red[256], a[kPart], r[kPart];
-  fold_partials(part, nb, 2, 1, red, a);
-  if (part_r) fold_partials(part_r, nb_r, 1, 0, red, r);
-  if (threadIdx.x == 0) {
-    ctl->l1 = (float)a[0];
-    ctl->nz_db = (int)a[1];
-    ctl->absmax = (float)a[2];
-    if (part_r) ctl->rr = (float)r[0];
-  }
-}
-
-// |x - rb|^2 of the rb the iteration carries (in a continuation step it is not z W^T: the reference keeps the code
-// u - v of the stale pair beside the residual of z + dz, gpsr.py:53,69 -- its summary prints this one)
-__global__ __launch_bounds__(256) void rb_sumsq_kernel(const float* __restrict__ X, int64_t ldx, const float* __restrict__ RB, int n,
-                                                       int d, double* __restrict__ part) {
-  __shared__ double red[32];
-  double s[1] = {0.0};
-  float nomax[1] = {0.0f};
-  const int64_t total = (int64_t)n * d;
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
-    const float r = __fsub_rn(X[(i / d) * ldx + (i % d)], RB[i]);
-    s[0] += (double)__fmul_rn(r, r);
-  }
-  block_fold<1, 0>(s, nomax, red, part + (int64_t)blockIdx.x * kPart);
-}
-
-__global__ __launch_bounds__(256) void rb_stat_kernel(const double* __restrict__ part, int nb, Ctl* __restrict__ ctl) {
-  __shared__ double red[256], a[kPart];
-  fold_partials(part, nb, 1, 0, red, a);
-  if (threadIdx.x == 0) ctl->rr_rb = (float)a[0];
-}
-
-// debias: rTr of the first masked gradient and the CG threshold tol * rTr
-__global__ __launch_bounds__(256) void cg_start_kernel(const double* __restrict__ part, int nb, float tol, Ctl* __restrict__ ctl) {
-  __shared__ double red[256], a[kPart];
-  fold_partials(part, nb, 1, 0, red, a);
-  if (threadIdx.x == 0) {
-    ctl->rtr = (float)a[0];
-    ctl->thresh = __fmul_rn(tol, (float)a[0]);
-  }
-}
-
-__global__ __launch_bounds__(256) void cg_alpha_kernel(const double* __restrict__ part, int nb, Ctl* __restrict__ ctl) {
-  __shared__ double red[256], a[kPart];
-  fold_partials(part, nb, 1, 0, red, a);
-  if (threadIdx.x == 0) ctl->alpha_cg = __fdiv_rn(ctl->rtr, (float)a[0]);
-}
-
-// z += a p, r += a Ap over [nk]; resid += a Wp over [nd]; partials {r.r, sum |z|, resid.resid}
-__global__ __launch_bounds__(256) void cg_axpy_kernel(float* __restrict__ Z, float* __restrict__ R, const float* __restrict__ P,
-                                                      const float* __restrict__ AP, int64_t nk, float* __restrict__ RES,
-                                                      const float* __restrict__ WP, int64_t nd, const Ctl* __restrict__ ctl,
-                                                      double* __restrict__ part) {
-  __shared__ double red[32];
-  const float a = ctl->alpha_cg;
-  double s[3] = {0.0, 0.0, 0.0};
-  float nomax[1] = {0.0f};
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < nk + nd; i += (int64_t)gridDim.x * 256) {
-    if (i < nk) {
-      const float z = __fadd_rn(Z[i], __fmul_rn(a, P[i]));
-      const float r = __fadd_rn(R[i], __fmul_rn(a, AP[i]));
-      Z[i] = z;
-      R[i] = r;
-      s[0] += (double)__fmul_rn(r, r);
-      s[1] += (double)fabsf(z);
-    } else {
-      const float e = __fadd_rn(RES[i - nk], __fmul_rn(a, WP[i - nk]));
-      RES[i - nk] = e;
-      s[2] += (double)__fmul_rn(e, e);
-    }
-  }
-  block_fold<3, 0>(s, nomax, red, part + (int64_t)blockIdx.x * kPart);
-}
-
-// end of a CG step: beta = rTr+ / rTr, the objective and the figures of the verbose line
-__global__ __launch_bounds__(256) void cg_beta_kernel(const double* __restrict__ part, int nb, float tau, Ctl* __restrict__ ctl) {
-  __shared__ double red[256], a[kPart];
-  fold_partials(part, nb, 3, 0, red, a);
-  if (threadIdx.x == 0) {
-    const float rtr_new = (float)a[0];
-    ctl->beta_cg = __fdiv_rn(rtr_new, ctl->rtr);
-    ctl->rtr = rtr_new;
-    ctl->rr_db = (float)a[2];
-    ctl->f_db = __fadd_rn(__fmul_rn(0.5f, (float)a[2]), __fmul_rn(tau, (float)a[1]));
-    ctl->conv_db = __fdiv_rn(rtr_new, ctl->thresh);
-  }
-}
-
-__global__ __launch_bounds__(256) void cg_dir_kernel(float* __restrict__ P, const float* __restrict__ R, int64_t nk,
-                                                     const Ctl* __restrict__ ctl) {
-  const float b = ctl->beta_cg;
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < nk; i += (int64_t)gridDim.x * 256)
-    P[i] = __fadd_rn(-R[i], __fmul_rn(b, P[i]));
-}
-
-__global__ __launch_bounds__(256) void copy_out_kernel(const float* __restrict__ Z, float* __restrict__ out, int64_t ldo, int n,
-                                                       int k, int zero) {
-  const int64_t total = (int64_t)n * k;
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256)
-    out[(i / k) * ldo + (i % k)] = zero ? 0.0f : Z[i];
-}
-
-// ---- launchers -------------------------------------------------------------------------------------------------------
-int ew_grid(int64_t total) { return (int)std::max<int64_t>(1, std::min<int64_t>(kEwBlocks, (total + 1023) / 1024)); }
-
-int device_cus() {
-  int dev = 0, cus = 0;
-  if (hipGetDevice(&dev) != hipSuccess ||
-      hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1)
-    cus = 1;
-  return cus;
-}
-
-// 128 x 128 blocks while they still give every CU two workgroups, 64 x 64 otherwise (and for a very wide row pitch)
-int block_side(int m, int nn, int64_t ldmax, int cus) {
-  const int64_t blocks = (int64_t)((m + 127) / 128) * ((nn + 127) / 128);
-  return (blocks >= 2 * (int64_t)cus && ldmax * 128 * 4 < ((int64_t)1 << 31)) ? 128 : 64;
-}
-int gemm_parts(int m, int nn, int side) { return ((m + side - 1) / side) * ((nn + side - 1) / side); }
-
-template <int BS, bool VEC, bool DMA, int MODE>
-hipError_t launch_one(const float* A, int64_t lda, const float* B, int64_t ldb, int m, int nn, int kk, const Epi& ep, int rungs,
-                      hipStream_t st) {
-  constexpr int lds = 2 * (BS + BS) * 128;
-  if (lds > 48 * 1024)
-    if (hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(&gpsr_gemm_kernel<BS, BS, VEC, DMA, MODE>), lds);
-        e != hipSuccess)
-      return e;
-  const dim3 grid((nn + BS - 1) / BS, (m + BS - 1) / BS, rungs);
-  hipLaunchKernelGGL((gpsr_gemm_kernel<BS, BS, VEC, DMA, MODE>), grid, dim3(256), lds, st, A, lda, B, ldb, m, nn, kk, ep);
-  return hipGetLastError();
-}
-
-template <int MODE>
-hipError_t launch_gemm(const float* A, int64_t lda, const float* B, int64_t ldb, int m, int nn, int kk, const Epi& ep, int side,
-                       int rungs, hipStream_t st) {
-  const bool vec = kk % 4 == 0 && lda % 4 == 0 && ldb % 4 == 0 && ((uintptr_t)A & 15) == 0 && ((uintptr_t)B & 15) == 0 &&
-                   (ep.a_stride % 4) == 0;
-  const bool dma = vec && kk % 32 == 0 && lda * side * 4 < ((int64_t)1 << 31) && ldb * side * 4 < ((int64_t)1 << 31);
-  if (side == 128) {
-    if (dma) return launch_one<128, true, true, MODE>(A, lda, B, ldb, m, nn, kk, ep, rungs, st);
-    if (vec) return launch_one<128, true, false, MODE>(A, lda, B, ldb, m, nn, kk, ep, rungs, st);
-    return launch_one<128, false, false, MODE>(A, lda, B, ldb, m, nn, kk, ep, rungs, st);
-  }
-  if (dma) return launch_one<64, true, true, MODE>(A, lda, B, ldb, m, nn, kk, ep, rungs, st);
-  if (vec) return launch_one<64, true, false, MODE>(A, lda, B, ldb, m, nn, kk, ep, rungs, st);
-  return launch_one<64, false, false, MODE>(A, lda, B, ldb, m, nn, kk, ep, rungs, st);
-}
-
-struct Space {
-  float *Wt, *Ay, *U, *V, *Z, *T, *C, *Zc, *RB;
-  double *part_g, *part_q, *part_t, *part_r, *part_e;
-  Ctl* ctl;
+struct LinearSpace {
+  float* Wt;
+  Space common;
   size_t bytes;
 };
 
-Space carve(void* base, int64_t n, int64_t d, int64_t k) {
-  Space w;
+LinearSpace carve(void* base, int64_t n, int64_t d, int64_t k) {
+  LinearSpace w;
   Arena a(base);
-  const size_t nk = (size_t)n * k * 4, nd = (size_t)n * d * 4;
   w.Wt = a.take((size_t)k * d * 4);
-  w.Ay = a.take(nk);
-  w.U = a.take(nk);
-  w.V = a.take(nk);
-  w.Z = a.take(nk);
-  w.T = a.take(nk);
-  w.C = a.take(nk);
-  w.Zc = a.take(nk * kLadder);
-  w.RB = a.take(nd * (kLadder + 1));
   // block partials: 64 x 64 blocks give the most
-  const size_t pk = (size_t)gemm_parts((int)n, (int)k, 64) * kPart * 8, pd = (size_t)gemm_parts((int)n, (int)d, 64) * kPart * 8;
-  w.part_g = a.take<double>(pk);
-  w.part_q = a.take<double>(pd);
-  w.part_r = a.take<double>(pd * kLadder);
-  w.part_t = a.take<double>((size_t)kEwBlocks * kPart * 8 * kLadder);
-  w.part_e = a.take<double>((size_t)kEwBlocks * kPart * 8);
-  w.ctl = a.take<Ctl>(sizeof(Ctl));
+  w.common = carve_common(a, n * k, n * d, gemm_parts((int)n, (int)k, 64), gemm_parts((int)n, (int)d, 64));
   w.bytes = a.bytes();
   return w;
 }
@@ -638,233 +67,21 @@ int solve(const float* x, int64_t ldx, const float* w, int64_t ldw, const float*
           int64_t n64, int64_t d64, int64_t k64, double alpha, const lasso_gpsr_options& o, lasso_gpsr_result* res,
           void* workspace, hipStream_t st) {
   const int n = (int)n64, d = (int)d64, k = (int)k64;
-  const int64_t nk = (int64_t)n * k, nd = (int64_t)n * d;
-  const Space ws = carve(workspace, n, d, k);
+  const LinearSpace ws = carve(workspace, n, d, k);
   const int cus = device_cus();
-  const int side_k = block_side(n, k, std::max<int64_t>({(int64_t)d, (int64_t)k, ldx}), cus);      // products [n,k]
-  const int side_d = block_side(n, d, std::max<int64_t>({(int64_t)d, (int64_t)k, ldx, ldw}), cus);  // products [n,d]
   if (std::max<int64_t>({(int64_t)d, (int64_t)k, ldx, ldw}) * 64 * 4 >= ((int64_t)1 << 31)) {
     return fail(LASSO_ERR_UNSUPPORTED, "row pitch beyond the 32-bit offsets of a 64-row block");
   }
-  const int pk = gemm_parts(n, k, side_k), pd = gemm_parts(n, d, side_d);
-  const int gk = ew_grid(nk);
-  Ctl h;
-  memset(&h, 0, sizeof(h));
-  auto fetch = [&]() -> hipError_t {
-    if (hipError_t e = hipMemcpyAsync(&h, ws.ctl, sizeof(Ctl), hipMemcpyDeviceToHost, st); e != hipSuccess) return e;
-    return hipStreamSynchronize(st);
-  };
-  res->flags = 0;
-  res->n_iter = 0;
-  res->db_iters = 0;
-  res->steps = 0;
-  res->objective = 0.0;
-
-  // ---- set-up: Wt, Ay = y W, max |Ay| ----
-  LASSO_HIP_TRY(hipMemsetAsync(ws.ctl, 0, sizeof(Ctl), st));
-  LASSO_HIP_TRY(launch_transpose_pad(w, ldw, d, k, ws.Wt, d, k, d, st));
-  Epi e0 = {};
-  e0.Out = ws.Ay; e0.ldo = k;
-  LASSO_HIP_TRY(launch_gemm<EPI_STORE>(x, ldx, ws.Wt, d, n, k, d, e0, side_k, 1, st));
-  hipLaunchKernelGGL(absstat_kernel, dim3(gk), dim3(256), 0, st, ws.Ay, nk, (float*)nullptr, ws.part_e);
-  hipLaunchKernelGGL(stat_kernel, dim3(1), dim3(256), 0, st, ws.part_e, gk, (const double*)nullptr, 0, ws.ctl);
-  LASSO_HIP_TRY(hipGetLastError());
-  LASSO_HIP_TRY(fetch());
-  const double max_tau = (double)h.absmax;
-  if (alpha >= max_tau) {                                   // gpsr.py:276-279: the solution is the zero vector
-    res->flags |= LASSO_GPSR_ZERO_SOLUTION;
-    hipLaunchKernelGGL(copy_out_kernel, dim3(gk), dim3(256), 0, st, ws.Z, zout, ldz, n, k, 1);
-    LASSO_HIP_TRY(hipGetLastError());
-    return LASSO_OK;
-  }
-  // ---- continuation factors (gpsr.py:282-295) ----
-  std::vector<double> factors(1, 1.0);
-  int steps = 1;
-  if (o.continuation) {
-    steps = o.cont_steps;
-    double first = o.first_tau_factor;
-    if (!(first > 0.0) || first * alpha >= max_tau) {
-      res->flags |= LASSO_GPSR_TAU_FACTOR_CHANGED;
-      first = (double)((0.8f * h.absmax) / (float)alpha);
-    }
-    factors.assign(steps, 1.0);
-    const double a = log10(first);
-    for (int i = 0; i < steps; ++i) {                       // 10 ** numpy.linspace(a, 0, steps)
-      const double stepv = steps > 1 ? (0.0 - a) / (steps - 1) : 0.0;
-      const double e = (i == steps - 1 && steps > 1) ? 0.0 : a + i * stepv;
-      factors[i] = pow(10.0, e);
-    }
-  }
-  const float* start = z0 ? z0 : (o.init == 2 ? ws.Ay : nullptr);
-  const int64_t ld_start = z0 ? ldz0 : k;
-  const float mu = (float)o.mu, beta = (float)o.lambda_backtrack;
-  float* rb = ws.RB;                                        // the buffer that holds rb = z W^T
-  int rb_slot = 0;
-  int n_iter = 0;
-  bool failed = false;
-  lasso_gpsr_trace* const tr = res->trace;
-  for (int step = 0; step < steps && !failed; ++step) {
-    const double tau_d = alpha * factors[step];
-    const float tau = (float)tau_d;
-    const bool last = step + 1 == steps;
-    const float tol = (float)(last ? o.tol : 1e-3);
-    const int crit_id = last ? o.stop_criterion : 3;
-    // u, v of the START (the reference hands every continuation step the pair formed before the loop), rb, f
-    hipLaunchKernelGGL(init_kernel, dim3(gk), dim3(256), 0, st, start, ld_start, ws.Z, ws.U, ws.V, n, k, step > 0 ? 1 : 0,
-                       ws.part_e);
-    LASSO_HIP_TRY(hipGetLastError());
-    Epi er = {};
-    er.Y = x; er.ldy = ldx; er.Out = rb; er.ldo = d; er.part = ws.part_r;
-    LASSO_HIP_TRY(launch_gemm<EPI_RESID>(ws.Z, k, w, ldw, n, d, k, er, side_d, 1, st));
-    hipLaunchKernelGGL(start_kernel, dim3(1), dim3(256), 0, st, ws.part_r, pd, ws.part_e, gk, tau, ws.ctl);
-    LASSO_HIP_TRY(hipGetLastError());
-    bool have_start = false;
-    while (true) {
-      // gradient, curvature, lambda0
-      Epi eg = {};
-      eg.Ay = ws.Ay; eg.U = ws.U; eg.V = ws.V; eg.T = ws.T; eg.Cc = ws.C; eg.part = ws.part_g; eg.tau = tau;
-      LASSO_HIP_TRY(launch_gemm<EPI_GRAD>(rb, d, ws.Wt, d, n, k, d, eg, side_k, 1, st));
-      Epi eq = {};
-      eq.part = ws.part_q;
-      LASSO_HIP_TRY(launch_gemm<EPI_SUMSQ>(ws.C, k, w, ldw, n, d, k, eq, side_d, 1, st));
-      hipLaunchKernelGGL(lambda_kernel, dim3(1), dim3(256), 0, st, ws.part_g, pk, ws.part_q, pd, ws.ctl);
-      LASSO_HIP_TRY(hipGetLastError());
-      // trials: rung 0 alone, then ladders of kLadder; the accept step and the criterion ride behind every batch
-      int first = 0, accepted = -1;
-      int slots[kLadder];
-      while (true) {
-        const int count = first == 0 ? 1 : std::min(kLadder, kMaxReductions + 1 - first);
-        for (int j = 0, s = 0; j < count; ++j, ++s) {       // rb+ of the rungs: the slots the current rb does not use
-          if (s == rb_slot) ++s;
-          slots[j] = s;
-        }
-        hipLaunchKernelGGL(trial_kernel, dim3(gk, count), dim3(256), 0, st, ws.U, ws.V, ws.T, ws.Z, ws.Zc, nk, tau, beta, first,
-                           ws.ctl, ws.part_t);
-        LASSO_HIP_TRY(hipGetLastError());
-        // (the rungs' slots are consecutive except around rb_slot: one launch per run of consecutive slots)
-        for (int j = 0; j < count;) {
-          int run = 1;
-          while (j + run < count && slots[j + run] == slots[j] + run) ++run;
-          Epi et = {};
-          et.Y = x; et.ldy = ldx; et.Out = ws.RB + (int64_t)slots[j] * nd; et.ldo = d; et.out_stride = nd;
-          et.a_stride = nk; et.part = ws.part_r + (int64_t)j * pd * kPart;
-          LASSO_HIP_TRY(launch_gemm<EPI_RESID>(ws.Zc + (int64_t)j * nk, k, w, ldw, n, d, k, et, side_d, run, st));
-          j += run;
-        }
-        hipLaunchKernelGGL(decide_kernel, dim3(1), dim3(256), 0, st, ws.part_t, gk, ws.part_r, pd, first, count, tau, mu, beta,
-                           ws.ctl);
-        hipLaunchKernelGGL(finish_kernel, dim3(gk), dim3(256), 0, st, ws.U, ws.V, ws.T, ws.Z, nk, tau, ws.ctl, ws.part_e);
-        hipLaunchKernelGGL(criterion_kernel, dim3(1), dim3(256), 0, st, ws.part_e, gk, crit_id, ws.ctl);
-        LASSO_HIP_TRY(hipGetLastError());
-        LASSO_HIP_TRY(fetch());                                  // the one host wait of an iteration whose first trial holds
-        if (!have_start && tr && step < tr->step_capacity) {
-          tr->step_f0[step] = h.f0;
-          tr->step_nz0[step] = h.nz0;
-        }
-        have_start = true;
-        if (h.accept >= 0) { accepted = h.accept; break; }
-        first += count;
-        if (h.bad || first > kMaxReductions) break;
-      }
-      if (accepted < 0) {                                   // the documented extension: end the solve, keep the last accepted z
-        res->flags |= LASSO_GPSR_LINESEARCH_FAILED;
-        failed = true;
-        break;
-      }
-      rb_slot = slots[accepted - first];                    // rb = rb+ of the accepted rung
-      rb = ws.RB + (int64_t)rb_slot * nd;
-      ++n_iter;
-      if (tr && n_iter <= tr->capacity) {
-        tr->lambda[n_iter - 1] = h.lam_acc;
-        tr->lambda0[n_iter - 1] = h.lam0;
-        tr->trials[n_iter - 1] = accepted + 1;
-        tr->objective[n_iter - 1] = h.f;
-        tr->criterion[n_iter - 1] = h.crit;
-        tr->nz[n_iter - 1] = h.nz;
-      }
-      res->objective = (double)h.f;
-      if ((n_iter > o.miniter && h.crit <= tol) || n_iter >= o.maxiter) break;
-    }
-    if (tr && step < tr->step_capacity) {
-      tr->step_tau[step] = tau_d;
-      tr->step_end[step] = n_iter;
-    }
-    res->steps = step + 1;
-  }
-  res->n_iter = n_iter;
-  // ---- final figures of the main phase: |y - rb|^2 (carried and recomputed from z), |z|_1, nonzeros ----
-  {
-    Epi er = {};
-    er.Y = x; er.ldy = ldx; er.Out = ws.RB + (int64_t)(rb_slot == 0 ? 1 : 0) * nd; er.ldo = d; er.part = ws.part_r;
-    // (after a failed search rb may belong to a rejected candidate: recompute from z)
-    LASSO_HIP_TRY(launch_gemm<EPI_RESID0>(ws.Z, k, w, ldw, n, d, k, er, side_d, 1, st));
-    hipLaunchKernelGGL(absstat_kernel, dim3(gk), dim3(256), 0, st, ws.Z, nk, ws.U /* mask */, ws.part_e);
-    hipLaunchKernelGGL(stat_kernel, dim3(1), dim3(256), 0, st, ws.part_e, gk, ws.part_r, pd, ws.ctl);
-    const int gd = ew_grid(nd);
-    hipLaunchKernelGGL(rb_sumsq_kernel, dim3(gd), dim3(256), 0, st, x, ldx, rb, n, d, ws.part_t);
-    hipLaunchKernelGGL(rb_stat_kernel, dim3(1), dim3(256), 0, st, ws.part_t, gd, ws.ctl);
-    LASSO_HIP_TRY(hipGetLastError());
-    LASSO_HIP_TRY(fetch());
-    res->main_rr = failed ? h.rr : h.rr_rb;
-    res->main_l1 = h.l1;
-    res->main_nz = h.nz_db;
-    res->main_objective = res->objective;
-    if (failed) res->objective = 0.5 * (double)h.rr + alpha * (double)h.l1;
-  }
-  // ---- debias: CG on the support of z (gpsr.py:132-206) ----
-  if (o.debias && !failed) {
-    float* const RES = ws.RB + (int64_t)(rb_slot == 0 ? 1 : 0) * nd;     // z W^T - y, from above
-    float* const WP = ws.RB + (int64_t)(rb_slot <= 1 ? 2 : 1) * nd;
-    float* const R = ws.T; float* const P = ws.C; float* const AP = ws.Zc; float* const MASK = ws.U;
-    const float tau = (float)alpha;
-    if ((int64_t)h.nz_db > nd || h.nz_db == 0) {
-      res->flags |= h.nz_db == 0 ? LASSO_GPSR_DEBIAS_NO_NONZEROS : LASSO_GPSR_DEBIAS_TOO_MANY;
-      res->objective = (double)(0.5f * h.rr + tau * h.l1);
-    } else {
-      Epi em = {};
-      em.Mask = MASK; em.Out = R; em.P = P; em.part = ws.part_g;
-      LASSO_HIP_TRY(launch_gemm<EPI_MASK_R>(RES, d, ws.Wt, d, n, k, d, em, side_k, 1, st));
-      hipLaunchKernelGGL(cg_start_kernel, dim3(1), dim3(256), 0, st, ws.part_g, pk, (float)o.tol_debias, ws.ctl);
-      LASSO_HIP_TRY(hipGetLastError());
-      int it = 0;
-      const int ge = ew_grid(nk + nd);
-      while (true) {
-        Epi ew = {};
-        ew.Out = WP; ew.ldo = d;
-        LASSO_HIP_TRY(launch_gemm<EPI_STORE>(P, k, w, ldw, n, d, k, ew, side_d, 1, st));
-        Epi ea = {};
-        ea.Mask = MASK; ea.Out = AP; ea.P = P; ea.part = ws.part_g;
-        LASSO_HIP_TRY(launch_gemm<EPI_MASK_AP>(WP, d, ws.Wt, d, n, k, d, ea, side_k, 1, st));
-        hipLaunchKernelGGL(cg_alpha_kernel, dim3(1), dim3(256), 0, st, ws.part_g, pk, ws.ctl);
-        hipLaunchKernelGGL(cg_axpy_kernel, dim3(ge), dim3(256), 0, st, ws.Z, R, P, AP, nk, RES, WP, nd, ws.ctl, ws.part_e);
-        hipLaunchKernelGGL(cg_beta_kernel, dim3(1), dim3(256), 0, st, ws.part_e, ge, tau, ws.ctl);
-        hipLaunchKernelGGL(cg_dir_kernel, dim3(gk), dim3(256), 0, st, P, R, nk, ws.ctl);
-        LASSO_HIP_TRY(hipGetLastError());
-        LASSO_HIP_TRY(fetch());
-        ++it;
-        if (tr && it <= tr->db_capacity) {
-          tr->db_rr[it - 1] = h.rr_db;
-          tr->db_conv[it - 1] = h.conv_db;
-        }
-        res->objective = (double)h.f_db;
-        const bool go = it <= o.miniter_debias || (h.rtr > h.thresh && it <= o.maxiter_debias);
-        if (!go) break;
-      }
-      res->db_iters = it;
-      res->n_iter = n_iter + it;
-      hipLaunchKernelGGL(absstat_kernel, dim3(gk), dim3(256), 0, st, ws.Z, nk, (float*)nullptr, ws.part_e);
-      hipLaunchKernelGGL(stat_kernel, dim3(1), dim3(256), 0, st, ws.part_e, gk, (const double*)nullptr, 0, ws.ctl);
-      LASSO_HIP_TRY(hipGetLastError());
-      LASSO_HIP_TRY(fetch());
-      res->db_rr = h.rr_db;
-      res->db_l1 = h.l1;
-      res->db_nz = h.nz_db;
-    }
-  }
-  hipLaunchKernelGGL(copy_out_kernel, dim3(gk), dim3(256), 0, st, ws.Z, zout, ldz, n, k, 0);
-  LASSO_HIP_TRY(hipGetLastError());
-  LASSO_HIP_TRY(hipStreamSynchronize(st));
-  return LASSO_OK;
+  LinearOp op;
+  op.rows = n; op.cols = k; op.nd = (int64_t)n * d;
+  op.side_k = block_side(n, k, std::max<int64_t>({(int64_t)d, (int64_t)k, ldx}), cus);       // products [n,k]
+  op.side_d = block_side(n, d, std::max<int64_t>({(int64_t)d, (int64_t)k, ldx, ldw}), cus);  // products [n,d]
+  op.pk = gemm_parts(n, k, op.side_k);
+  op.pd = gemm_parts(n, d, op.side_d);
+  op.y = x; op.ldy = ldx; op.y_rows = n; op.y_cols = d;
+  op.start = z0; op.ld_start = ldz0;
+  op.w = w; op.ldw = ldw; op.Wt = ws.Wt; op.zout = zout; op.ldz = ldz; op.d = d;
+  return solve_with(op, ws.common, alpha, o, res, st);
 }
 
 }  // namespace gpsr

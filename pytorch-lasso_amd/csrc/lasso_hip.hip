@@ -2863,17 +2863,11 @@ size_t lasso_gpsr_workspace_bytes(int64_t n, int64_t d, int64_t k, int dtype) {
   return gpsr::workspace_bytes(n, d, k);
 }
 
-int lasso_gpsr_solve(const void* x_dev, int64_t ldx, const void* w_dev, int64_t ldw, const void* z0_dev, int64_t ldz0,
-                     void* z_out_dev, int64_t ldz, int64_t n, int64_t d, int64_t k, int dtype, double alpha,
-                     const lasso_gpsr_options* o, lasso_gpsr_result* res, void* workspace_dev, size_t workspace_bytes,
-                     void* stream) {
-  if (dtype != LASSO_F32) return fail(LASSO_ERR_UNSUPPORTED, "GPSR: dtype %d (fp32 tensors only)", dtype);
-  if (!o || !res) return fail(LASSO_ERR_BAD_ARG, "null options / result");
-  if (n < 0 || d <= 0 || k <= 0 || n > INT32_MAX || d > INT32_MAX || k > INT32_MAX)
-    return fail(LASSO_ERR_BAD_ARG, "bad shape");
+// the option, trace and result checks the two GPSR entry points share; clears the result
+static int check_gpsr_request(const lasso_gpsr_options* o, lasso_gpsr_result* res, bool has_z0) {
   if (o->stop_criterion < 0 || o->stop_criterion > 4) return fail(LASSO_ERR_BAD_ARG, "Unknown stopping criterion");
-  if (!z0_dev && o->init == 1) return fail(LASSO_ERR_UNSUPPORTED, "GPSR: init=1 (random start) is passed as z0");
-  if (!z0_dev && o->init != 0 && o->init != 2) return fail(LASSO_ERR_BAD_ARG, "Unknown initialization option");
+  if (!has_z0 && o->init == 1) return fail(LASSO_ERR_UNSUPPORTED, "GPSR: init=1 (random start) is passed as z0");
+  if (!has_z0 && o->init != 0 && o->init != 2) return fail(LASSO_ERR_BAD_ARG, "Unknown initialization option");
   if (o->continuation && o->cont_steps < 1) return fail(LASSO_ERR_BAD_ARG, "cont_steps < 1");
   if (!(o->lambda_backtrack > 0.0 && o->lambda_backtrack < 1.0)) return fail(LASSO_ERR_BAD_ARG, "lambda_backtrack outside (0, 1)");
   if (const lasso_gpsr_trace* t = res->trace) {
@@ -2886,6 +2880,18 @@ int lasso_gpsr_solve(const void* x_dev, int64_t ldx, const void* w_dev, int64_t 
   res->objective = res->main_objective = 0.0;
   res->main_rr = res->main_l1 = res->db_rr = res->db_l1 = 0.0f;
   res->main_nz = res->db_nz = 0;
+  return LASSO_OK;
+}
+
+int lasso_gpsr_solve(const void* x_dev, int64_t ldx, const void* w_dev, int64_t ldw, const void* z0_dev, int64_t ldz0,
+                     void* z_out_dev, int64_t ldz, int64_t n, int64_t d, int64_t k, int dtype, double alpha,
+                     const lasso_gpsr_options* o, lasso_gpsr_result* res, void* workspace_dev, size_t workspace_bytes,
+                     void* stream) {
+  if (dtype != LASSO_F32) return fail(LASSO_ERR_UNSUPPORTED, "GPSR: dtype %d (fp32 tensors only)", dtype);
+  if (!o || !res) return fail(LASSO_ERR_BAD_ARG, "null options / result");
+  if (n < 0 || d <= 0 || k <= 0 || n > INT32_MAX || d > INT32_MAX || k > INT32_MAX)
+    return fail(LASSO_ERR_BAD_ARG, "bad shape");
+  if (int s = check_gpsr_request(o, res, z0_dev != nullptr)) return s;
   if (n == 0) return LASSO_OK;
   if (!x_dev || !w_dev || !z_out_dev || !workspace_dev) return fail(LASSO_ERR_BAD_ARG, "null pointer");
   if (ldx < d || ldw < k || ldz < k || (z0_dev && ldz0 < k)) return fail(LASSO_ERR_BAD_ARG, "leading dimension too small");
@@ -3219,6 +3225,47 @@ const char* lasso_conv_ista_kernel_name(int64_t N, int64_t C, int64_t H, int64_t
            gp > 0 ? "lasso::conv_grad_prox_kernel"
                   : "lasso::conv_patches_kernel + lasso::gemm_nt_kernel + lasso::generic_prox_kernel");
   return cname;
+}
+
+// ---- convolutional GPSR-Basic: gpsr_basic with A = conv_transpose2d, AT = conv2d (csrc/conv_gpsr.hip) ----
+// what the solve cannot address: an image row beyond int, or a pitch (the tap-major matrix has pitch M) beyond the
+// 32-bit offsets of a 64-row GEMM block
+static bool conv_gpsr_too_large(const ConvGeom& g) {
+  const int64_t M = (int64_t)g.N * g.Hz * g.Wz, ldr = ((int64_t)g.C * g.kh * g.kw + 3) / 4 * 4;
+  return (int64_t)g.C * g.H * g.W > INT32_MAX || std::max<int64_t>({M, (int64_t)g.K, ldr}) * 64 * 4 >= ((int64_t)1 << 31);
+}
+size_t lasso_conv_gpsr_workspace_bytes(int64_t N, int64_t C, int64_t H, int64_t W, int64_t K, int64_t Hz, int64_t Wz,
+                                       int kh, int kw, int sh, int sw, int ph, int pw) {
+  const ConvGeom g = make_geom(N, C, H, W, K, Hz, Wz, kh, kw, sh, sw, ph, pw);
+  if (check_conv(g, LASSO_F32) || conv_gpsr_too_large(g)) return 0;
+  return gpsr::conv_workspace_bytes(g);
+}
+
+const char* lasso_conv_gpsr_form(int64_t N, int64_t C, int64_t H, int64_t W, int64_t K, int64_t Hz, int64_t Wz, int kh,
+                                 int kw, int sh, int sw, int ph, int pw, int reserved) {
+  const ConvGeom g = make_geom(N, C, H, W, K, Hz, Wz, kh, kw, sh, sw, ph, pw);
+  if (check_conv(g, LASSO_F32) || conv_gpsr_too_large(g)) return "";
+  return gpsr::conv_form(g, reserved & 1);
+}
+
+int lasso_conv_gpsr_solve(const void* x_dev, const void* w_dev, const void* z0_dev, void* z_out_dev, int64_t N,
+                          int64_t C, int64_t H, int64_t W, int64_t K, int64_t Hz, int64_t Wz, int kh, int kw, int sh,
+                          int sw, int ph, int pw, int dtype, double tau, const lasso_gpsr_options* o,
+                          lasso_gpsr_result* res, void* workspace_dev, size_t workspace_bytes, void* stream) {
+  if (dtype != LASSO_F32) return fail(LASSO_ERR_UNSUPPORTED, "convolutional GPSR: dtype %d (fp32 tensors only)", dtype);
+  if (!o || !res) return fail(LASSO_ERR_BAD_ARG, "null options / result");
+  const ConvGeom g = make_geom(N, C, H, W, K, Hz, Wz, kh, kw, sh, sw, ph, pw);
+  if (int s = check_conv(g, dtype)) return s;
+  if (conv_gpsr_too_large(g))
+    return fail(LASSO_ERR_UNSUPPORTED, "convolutional GPSR: %lld code pixels / %lld image elements are beyond 32-bit block offsets",
+                (long long)(N * Hz * Wz), (long long)(C * H * W));
+  if (int s = check_gpsr_request(o, res, z0_dev != nullptr)) return s;
+  if (N == 0) return LASSO_OK;
+  if (!x_dev || !w_dev || !z_out_dev || !workspace_dev) return fail(LASSO_ERR_BAD_ARG, "null pointer");
+  const size_t need = gpsr::conv_workspace_bytes(g);
+  if (workspace_bytes < need) return fail(LASSO_ERR_WORKSPACE, "need %zu bytes", need);
+  return gpsr::conv_solve((const float*)x_dev, (const float*)w_dev, (const float*)z0_dev, (float*)z_out_dev, g, tau, *o, res,
+                          workspace_dev, static_cast<hipStream_t>(stream));
 }
 
 int lasso_conv_ista_solve(const void* x_dev, const void* w_dev, const void* z0_dev, void* z_out_dev, int64_t N,

@@ -435,9 +435,17 @@ const char* conv_fused_kernel_name(const ConvGeom& g, int cus);   // null: not c
 hipError_t launch_conv_fused(const void* tables, const float* x, float* Zm, const float* Yin, float* Yout, float lr,
                              float lam, const float* coefs, int iters, float* dpart, int dpart_cap, float* delta_out,
                              const ConvGeom& g, int cus, hipStream_t stream);
+// gpsr != null (conv_gpsr.hip): the same implicit GEMM with GPSR's GRAD epilogue in place of the proximal step (Zm, Ym,
+// lr, lam, coef, dpart unused); *count = the number of 8-double block partials left in gpsr->part, at most dpart_cap
+struct ConvGradGpsr {
+  const float* Ay; const float* U; const float* V;   // [M][K]
+  float* T; float* Cc;                               // out [M][K]
+  double* part;                                      // [count][8]
+  float tau;
+};
 hipError_t launch_conv_grad_prox(const float* r, const float* Wp, int ldr, float* Zm, float* Ym, float lr, float lam,
                                  float coef, float* dpart, int dpart_cap, const ConvGeom& g, int cus, int* count,
-                                 hipStream_t stream, int dry = 0);
+                                 hipStream_t stream, int dry = 0, const ConvGradGpsr* gpsr = nullptr);
 // G = add_to + conv2d(r, W) in row layout (add_to [M][K] or null)
 hipError_t launch_conv_gradient(const float* r, const float* Wp, float* rc, int ldr, float* G, const ConvGeom& g,
                                 hipStream_t stream, const float* add_to = nullptr);
@@ -544,6 +552,12 @@ size_t workspace_bytes(int64_t n, int64_t d, int64_t k);
 int solve(const float* x, int64_t ldx, const float* w, int64_t ldw, const float* z0, int64_t ldz0, float* zout, int64_t ldz,
           int64_t n, int64_t d, int64_t k, double alpha, const lasso_gpsr_options& o, lasso_gpsr_result* res, void* workspace,
           hipStream_t st);
+// conv_gpsr.hip: the same loop on A z = conv_transpose2d(z, W); contiguous NCHW tensors, the driver behind
+// lasso_conv_gpsr_solve
+size_t conv_workspace_bytes(const ConvGeom& g);
+const char* conv_form(const ConvGeom& g, int forced_general);     // "implicit" / "patches": the form conv_solve takes
+int conv_solve(const float* x, const float* w, const float* z0, float* zout, const ConvGeom& g, double tau,
+               const lasso_gpsr_options& o, lasso_gpsr_result* res, void* workspace, hipStream_t st);
 }  // namespace gpsr
 
 }  // namespace lasso

@@ -280,6 +280,13 @@ def _declare(lib):
     lib.lasso_gpsr_solve.restype = i32
     lib.lasso_gpsr_solve.argtypes = [vp, i64, vp, i64, vp, i64, vp, i64, i64, i64, i64, i32, dbl,
                                      C.POINTER(GpsrOptions), C.POINTER(GpsrResult), vp, sz, vp]
+    lib.lasso_conv_gpsr_workspace_bytes.restype = sz
+    lib.lasso_conv_gpsr_workspace_bytes.argtypes = [i64] * 7 + [i32] * 6
+    lib.lasso_conv_gpsr_form.restype = C.c_char_p
+    lib.lasso_conv_gpsr_form.argtypes = [i64] * 7 + [i32] * 7
+    lib.lasso_conv_gpsr_solve.restype = i32
+    lib.lasso_conv_gpsr_solve.argtypes = [vp, vp, vp, vp] + [i64] * 7 + [i32] * 6 + [i32, dbl, C.POINTER(GpsrOptions),
+                                                                                  C.POINTER(GpsrResult), vp, sz, vp]
     lib.lasso_cd_solve.restype = i32
     lib.lasso_cd_solve.argtypes = [vp, i64, vp, i64, vp, i64, vp, i64, i64, i64, i64, i32, dbl, i32,
                                    dbl, pi32, pi32, vp, sz, vp]

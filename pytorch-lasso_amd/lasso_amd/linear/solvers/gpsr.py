@@ -31,6 +31,82 @@ def _summary(phase, rr, l1, f, nz, verbose):
         print('     Num. non-zero components: %d' % nz)
 
 
+def _request(stop_criterion, tol, maxiter, miniter, init, continuation, debias, opt, has_z0):
+    """The options, result and trace structs of one solve (lasso_gpsr_solve and lasso_conv_gpsr_solve take the same):
+    -> (options, res, keep) where ``keep`` holds the host arrays the trace points to, for _report."""
+    steps = int(opt['cont_steps']) if continuation else 1
+    cap = int(maxiter) + steps + 1
+    dcap = (max(int(opt['maxiter_debias']), int(opt['miniter_debias'])) + 2) if debias else 0
+    lam, lam0, obj, crit = _f32(cap), _f32(cap), _f32(cap), _f32(cap)
+    trials, nz = _i32(cap), _i32(cap)
+    s_tau, s_f0, s_nz0, s_end = (C.c_double * steps)(), _f32(steps), _i32(steps), _i32(steps)
+    db_rr, db_conv = _f32(dcap), _f32(dcap)
+    trace = nat.GpsrTrace(cap, lam, lam0, trials, obj, crit, nz, steps, s_tau, s_f0, s_nz0, s_end,
+                          dcap, db_rr, db_conv)
+    first = opt['first_tau_factor']
+    options = nat.GpsrOptions(
+        int(stop_criterion), int(maxiter), int(miniter), int(init) if not has_z0 else 0,
+        int(bool(continuation)), int(bool(debias)), steps, int(opt['maxiter_debias']),
+        int(opt['miniter_debias']), 0, float(tol), float(opt['mu']), float(opt['lambda_backtrack']),
+        float(first) if first is not None else -1.0, float(opt['tol_debias']))
+    res = nat.GpsrResult()
+    res.trace = C.pointer(trace)
+    return options, res, (steps, cap, dcap, lam, lam0, obj, crit, trials, nz, s_tau, s_f0, s_nz0, s_end, db_rr, db_conv,
+                          trace)
+
+
+def _report(res, keep, stop_criterion, tol, debias, opt, verbose):
+    """The reference's warnings and prints for a finished solve (after it: the iterations ran inside one native
+    call) -> the ``return_info`` dictionary."""
+    steps, cap, dcap, lam, lam0, obj, crit, trials, nz, s_tau, s_f0, s_nz0, s_end, db_rr, db_conv, _ = keep
+    flags = res.flags
+    if flags & nat.GPSR_ZERO_SOLUTION:
+        warnings.warn('tau is too small; solution is zero vector')       # :278
+    if flags & nat.GPSR_TAU_FACTOR_CHANGED:
+        warnings.warn('parameter FirstTauFactor too large; changing')    # :290
+    its = min(res.n_iter - res.db_iters, cap)
+    info = dict(iterations=res.n_iter, objective=list(obj[:its]), accepted_lambda=list(lam[:its]),
+                trials=list(trials[:its]), criterion=list(crit[:its]), final_objective=res.objective)
+    if verbose and not flags & nat.GPSR_ZERO_SOLUTION:
+        beta32 = torch.tensor(float(opt['lambda_backtrack']), dtype=torch.float32)
+        it = 0
+        for s in range(res.steps):
+            if verbose > 1:
+                print('Setting tau = %8.4f\n' % s_tau[s])
+            print('Initial obj = %10.6e, nz = %d\n' % (s_f0[s], s_nz0[s]))
+            last = s + 1 == steps
+            name = _CRITERION_NAMES[stop_criterion if last else 3]
+            while it < min(s_end[s], cap):
+                if verbose > 1:
+                    lam_t = torch.tensor(lam0[it], dtype=torch.float32)
+                    for _ in range(trials[it] - 1):
+                        lam_t = lam_t * beta32
+                        print('    line-search reducing lambda to %6.2e' % lam_t)
+                print('It = %4d, obj = %9.5e, lambda = %6.2e, nz = %d' % (it + 1, obj[it], lam[it], nz[it]))
+                print(4 * ' ' + name + ' = %e (target = %e)' % (crit[it], tol if last else 1e-3))
+                it += 1
+        _summary('main algorithm', res.main_rr, res.main_l1, res.main_objective, res.main_nz, verbose)
+    if flags & nat.GPSR_LINESEARCH_FAILED:
+        warnings.warn('GPSR line search failed (objective not finite or lambda reduced 100 times); '
+                      'returning the last accepted iterate')
+    if debias and not flags & (nat.GPSR_ZERO_SOLUTION | nat.GPSR_LINESEARCH_FAILED):
+        if verbose:
+            print('\nStarting the debiasing phase...\n')
+        if flags & nat.GPSR_DEBIAS_NO_NONZEROS:
+            warnings.warn('Debiasing requested but not performed. x has no nonzeros.')            # :143-148
+        elif flags & nat.GPSR_DEBIAS_TOO_MANY:
+            warnings.warn('Debiasing requested but not performed. There are too many nonzeros in x.')
+        if verbose:
+            if res.db_iters:
+                for i in range(min(res.db_iters, dcap)):
+                    print(' Iter = %5d, resid = %13.8e, convergence = %8.3e' %
+                          (res.n_iter - res.db_iters + i + 1, db_rr[i], db_conv[i]))
+                _summary('debiasing phase', res.db_rr, res.db_l1, res.objective, res.db_nz, verbose)
+            else:
+                _summary('debiasing phase', res.main_rr, res.main_l1, res.objective, res.main_nz, verbose)
+    return info
+
+
 def gpsr_basic(x, weight, tau, x0=None, stop_criterion=3, tol=1e-2, maxiter=1000, miniter=5, init=0,
                continuation=False, debias=False, verbose=0, return_info=False, **kwargs):
     """GPSR-Basic (Figueiredo, Nowak, Wright 2007): min_z 0.5 ||x - z W^T||^2 + tau ||z||_1 for the whole batch
@@ -93,23 +169,8 @@ def gpsr_basic(x, weight, tau, x0=None, stop_criterion=3, tol=1e-2, maxiter=1000
     z = torch.empty((n, k), dtype=torch.float32, device=dev)
     info = dict(iterations=0, objective=[], accepted_lambda=[], trials=[], criterion=[], final_objective=float('nan'))
     if n > 0:
-        steps = int(opt['cont_steps']) if continuation else 1
-        cap = int(maxiter) + steps + 1
-        dcap = (max(int(opt['maxiter_debias']), int(opt['miniter_debias'])) + 2) if debias else 0
-        lam, lam0, obj, crit = _f32(cap), _f32(cap), _f32(cap), _f32(cap)
-        trials, nz = _i32(cap), _i32(cap)
-        s_tau, s_f0, s_nz0, s_end = (C.c_double * steps)(), _f32(steps), _i32(steps), _i32(steps)
-        db_rr, db_conv = _f32(dcap), _f32(dcap)
-        trace = nat.GpsrTrace(cap, lam, lam0, trials, obj, crit, nz, steps, s_tau, s_f0, s_nz0, s_end,
-                              dcap, db_rr, db_conv)
-        first = opt['first_tau_factor']
-        options = nat.GpsrOptions(
-            int(stop_criterion), int(maxiter), int(miniter), int(init) if x0 is None else 0,
-            int(bool(continuation)), int(bool(debias)), steps, int(opt['maxiter_debias']),
-            int(opt['miniter_debias']), 0, float(tol), float(opt['mu']), float(opt['lambda_backtrack']),
-            float(first) if first is not None else -1.0, float(opt['tol_debias']))
-        res = nat.GpsrResult()
-        res.trace = C.pointer(trace)
+        options, res, keep = _request(stop_criterion, tol, maxiter, miniter, init, continuation, debias, opt,
+                                      x0 is not None)
         L = nat.lib()
         with torch.cuda.device(dev):
             ws = nat.workspace(dev, L.lasso_gpsr_workspace_bytes(n, d, k, nat.LASSO_F32), "gpsr")
@@ -117,50 +178,6 @@ def gpsr_basic(x, weight, tau, x0=None, stop_criterion=3, tol=1e-2, maxiter=1000
                 nat.ptr(xg), xg.stride(0) if n > 1 else d, nat.ptr(wg), wg.stride(0) if d > 1 else k,
                 nat.ptr(z0g), k, nat.ptr(z), k, n, d, k, nat.LASSO_F32, float(tau),
                 C.byref(options), C.byref(res), nat.ptr(ws), ws.numel(), nat.stream_ptr(dev)))
-        flags = res.flags
-        if flags & nat.GPSR_ZERO_SOLUTION:
-            warnings.warn('tau is too small; solution is zero vector')       # :278
-        if flags & nat.GPSR_TAU_FACTOR_CHANGED:
-            warnings.warn('parameter FirstTauFactor too large; changing')    # :290
-        its = min(res.n_iter - res.db_iters, cap)
-        info = dict(iterations=res.n_iter, objective=list(obj[:its]), accepted_lambda=list(lam[:its]),
-                    trials=list(trials[:its]), criterion=list(crit[:its]), final_objective=res.objective)
-        if verbose and not flags & nat.GPSR_ZERO_SOLUTION:
-            beta32 = torch.tensor(float(opt['lambda_backtrack']), dtype=torch.float32)
-            it = 0
-            for s in range(res.steps):
-                if verbose > 1:
-                    print('Setting tau = %8.4f\n' % s_tau[s])
-                print('Initial obj = %10.6e, nz = %d\n' % (s_f0[s], s_nz0[s]))
-                last = s + 1 == steps
-                name = _CRITERION_NAMES[stop_criterion if last else 3]
-                while it < min(s_end[s], cap):
-                    if verbose > 1:
-                        lam_t = torch.tensor(lam0[it], dtype=torch.float32)
-                        for _ in range(trials[it] - 1):
-                            lam_t = lam_t * beta32
-                            print('    line-search reducing lambda to %6.2e' % lam_t)
-                    print('It = %4d, obj = %9.5e, lambda = %6.2e, nz = %d' % (it + 1, obj[it], lam[it], nz[it]))
-                    print(4 * ' ' + name + ' = %e (target = %e)' % (crit[it], tol if last else 1e-3))
-                    it += 1
-            _summary('main algorithm', res.main_rr, res.main_l1, res.main_objective, res.main_nz, verbose)
-        if flags & nat.GPSR_LINESEARCH_FAILED:
-            warnings.warn('GPSR line search failed (objective not finite or lambda reduced 100 times); '
-                          'returning the last accepted iterate')
-        if debias and not flags & (nat.GPSR_ZERO_SOLUTION | nat.GPSR_LINESEARCH_FAILED):
-            if verbose:
-                print('\nStarting the debiasing phase...\n')
-            if flags & nat.GPSR_DEBIAS_NO_NONZEROS:
-                warnings.warn('Debiasing requested but not performed. x has no nonzeros.')            # :143-148
-            elif flags & nat.GPSR_DEBIAS_TOO_MANY:
-                warnings.warn('Debiasing requested but not performed. There are too many nonzeros in x.')
-            if verbose:
-                if res.db_iters:
-                    for i in range(min(res.db_iters, dcap)):
-                        print(' Iter = %5d, resid = %13.8e, convergence = %8.3e' %
-                              (res.n_iter - res.db_iters + i + 1, db_rr[i], db_conv[i]))
-                    _summary('debiasing phase', res.db_rr, res.db_l1, res.objective, res.db_nz, verbose)
-                else:
-                    _summary('debiasing phase', res.main_rr, res.main_l1, res.objective, res.main_nz, verbose)
+        info = _report(res, keep, stop_criterion, tol, debias, opt, verbose)
     z = z.to(device=out_device, dtype=out_dtype)
     return (z, info) if return_info else z

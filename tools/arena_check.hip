@@ -12,7 +12,7 @@
 //   hipcc -std=c++17 -O1 -g --offload-arch=gfx950 -Xarch_host -fsanitize=address,undefined \
 //       -Xarch_host -fno-sanitize-recover=undefined -c ../../tools/arena_check.hip -o /tmp/arena_check.o
 //   hipcc --offload-arch=gfx950 -fsanitize=address,undefined /tmp/arena_check.o \
-//       $(ls build/*.o | grep -v -e /lasso_hip.o -e /gemm_f64.o -e /gpsr.o) -o /tmp/arena_check && /tmp/arena_check
+//       $(ls build/*.o | grep -v -e /lasso_hip.o -e /gemm_f64.o -e /gpsr.o -e /conv_gpsr.o) -o /tmp/arena_check && /tmp/arena_check
 //
 // Run it on the build machine, never on a machine whose GPU others share.
 #include <stddef.h>
@@ -27,6 +27,7 @@ static std::vector<Seen> g_seen;
 #include "../pytorch-lasso_amd/csrc/lasso_hip.hip"
 #include "../pytorch-lasso_amd/csrc/gemm_f64.hip"
 #include "../pytorch-lasso_amd/csrc/gpsr.hip"
+#include "../pytorch-lasso_amd/csrc/conv_gpsr.hip"
 
 static int g_checked = 0, g_regions = 0;
 
@@ -112,6 +113,7 @@ int main() {
   for (const ConvGeom& g : geoms) {
     check("carve_conv", [&](void* b) { return carve_conv(b, g).bytes; });
     check("carve_conv_bw", [&](void* b) { return carve_conv_bw(b, g, 256).bytes; });
+    check("gpsr::carve (conv)", [&](void* b) { return lasso::gpsr::carve(b, g).bytes; });
   }
   for (int64_t k : {512, 1024, 4096}) {      // (mstep.hip comes from the ordinary build: offsets only, nothing observed)
     const MstepPipePlan pl = mstep_pipe_plan(70000, 256, k, 256);
