@@ -42,6 +42,7 @@
  *     any d, k on fp32 tensors (bf16: fused shapes only);
  *   - GPSR-Basic has two entry points on one driver: lasso_gpsr_solve (the dictionary as the operator) and
  *     lasso_conv_gpsr_solve (conv_transpose2d / conv2d as the operator, contiguous NCHW tensors); both LASSO_F32 only.
+ *   - the orthant-wise Newton solver is lasso_own_solve: LASSO_F32, any n, d, any pitch, k <= 4096.
  */
 #ifndef LASSO_HIP_H_
 #define LASSO_HIP_H_
@@ -859,6 +860,52 @@ int lasso_conv_gpsr_solve(const void* x_dev, const void* w_dev, const void* z0_d
                           int64_t C, int64_t H, int64_t W, int64_t K, int64_t Hz, int64_t Wz, int kh, int kw, int sh,
                           int sw, int ph, int pw, int dtype, double tau, const lasso_gpsr_options* options,
                           lasso_gpsr_result* result, void* workspace_dev, size_t workspace_bytes, void* stream);
+
+/* ---- orthant-wise Newton: replaces orthant_wise_newton(), lasso/linear/solvers/orthant_wise_newton.py:33-160 ----
+ * min_z 0.5 |z W^T - x|^2 + alpha |z|_1 over the whole batch (csrc/own.hip).  Once per solve Hinv = (W^T W + 1e-4 I)^-1
+ * (lasso_gram_accumulate_f64 + lasso_ridge_solve_f64 on W in double, rounded once to fp32); per iteration v = -pseudo
+ * gradient, d = project(v Hinv^T, v), a batch-wide line search for t, z+ = project(z + t d, eta), stop once
+ * |z+ - z|_2 <= xtol.  Every sum is folded in double in a fixed order: two solves of the same arguments give the same
+ * bits.
+ *   options : maxiter >= 0; line_search 0 'brent' (bounded Brent on (0, 10), csrc/brent_host.hpp; lr unused),
+ *             1 'backtrack' (t = lr, lr ls_decay, ...: the first with f+ <= f - ls_tol <v, z+ - z> in the reference's
+ *             fp32 order, at most ls_maxiter trials, then the next rung unexamined), 2 'none' (t = lr); bit 0 of
+ *             reserved forces 128 x 128 GEMM blocks (tests).  The Brent objective is the double the fold produced, not
+ *             rounded to fp32.
+ *   result  : n_iter, flags, the objective of z0 and of z_out, cholesky_info (0, or 1 + the index of the first
+ *             non-positive pivot of W^T W + 1e-4 I: then LASSO_ERR_BAD_ARG), and -- trace non-NULL -- host arrays of the
+ *             caller: per iteration (capacity) the step t, the line-search evaluations, the objective and |dz|_2 of the
+ *             new z; per line-search evaluation (eval_capacity; eval_count is written) the iteration (1-based), t and f.
+ * Refusals before any HIP call: null pointers, n < 0, d or k < 1, a leading dimension below the row length, alpha < 0,
+ * maxiter < 0, ls_maxiter < 1 or an unknown line_search are LASSO_ERR_BAD_ARG; a dtype other than LASSO_F32 and
+ * k > 4096 LASSO_ERR_UNSUPPORTED (the workspace query returns 0); a short workspace LASSO_ERR_WORKSPACE.  n = 0 writes
+ * nothing.  z0_dev is only read; z_out_dev may not alias x or W.  The call blocks: the host reads the control block once
+ * per Brent evaluation / per batch of 8 backtracking rungs. */
+typedef struct lasso_own_options {
+  int32_t maxiter, line_search, ls_maxiter, reserved;
+  double lr, xtol, ls_tol, ls_decay;
+} lasso_own_options;
+typedef struct lasso_own_trace {
+  int32_t capacity;                       /* iterations the arrays below hold */
+  int32_t eval_capacity;                  /* line-search evaluations eval_* hold */
+  double* t; int32_t* ls_iters; double* f; double* delta_z;
+  int32_t* eval_iter; double* eval_t; double* eval_f;
+  int64_t eval_count;                     /* out: evaluations the solve made (may exceed eval_capacity) */
+} lasso_own_trace;
+#define LASSO_OWN_LS_NOT_CONVERGED 1      /* a backtracking ran out of trials ('line search did not converge.') */
+#define LASSO_OWN_NONFINITE 2             /* a non-finite objective ended the solve with the last accepted z */
+typedef struct lasso_own_result {
+  int32_t n_iter, flags;
+  double f0, f_final;
+  int32_t cholesky_info;
+  int32_t ls_failures;                    /* iterations whose backtracking ran out */
+  lasso_own_trace* trace;                 /* nullable */
+} lasso_own_result;
+size_t lasso_own_workspace_bytes(int64_t n, int64_t d, int64_t k, int dtype);
+int lasso_own_solve(const void* x_dev, int64_t ldx, const void* w_dev, int64_t ldw, const void* z0_dev, int64_t ldz0,
+                    void* z_out_dev, int64_t ldz, int64_t n, int64_t d, int64_t k, int dtype, double alpha,
+                    const lasso_own_options* options, lasso_own_result* result,
+                    void* workspace_dev, size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

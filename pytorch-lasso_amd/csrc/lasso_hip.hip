@@ -2901,6 +2901,42 @@ int lasso_gpsr_solve(const void* x_dev, int64_t ldx, const void* w_dev, int64_t 
                      ldz, n, d, k, alpha, *o, res, workspace_dev, static_cast<hipStream_t>(stream));
 }
 
+// ---- orthant-wise Newton: orthant_wise_newton.py:33-160 (csrc/own.hip) ----------------------
+size_t lasso_own_workspace_bytes(int64_t n, int64_t d, int64_t k, int dtype) {
+  if (dtype != LASSO_F32 || n < 0 || d <= 0 || k <= 0 || k > 4096 || n > INT32_MAX || d > INT32_MAX) return 0;
+  return own::workspace_bytes(n, d, k);
+}
+
+int lasso_own_solve(const void* x_dev, int64_t ldx, const void* w_dev, int64_t ldw, const void* z0_dev, int64_t ldz0,
+                    void* z_out_dev, int64_t ldz, int64_t n, int64_t d, int64_t k, int dtype, double alpha,
+                    const lasso_own_options* o, lasso_own_result* res, void* workspace_dev, size_t workspace_bytes,
+                    void* stream) {
+  if (dtype != LASSO_F32) return fail(LASSO_ERR_UNSUPPORTED, "orthant-wise Newton: dtype %d (fp32 tensors only)", dtype);
+  if (!o || !res) return fail(LASSO_ERR_BAD_ARG, "null options / result");
+  if (n < 0 || d <= 0 || k <= 0 || n > INT32_MAX || d > INT32_MAX || k > INT32_MAX)
+    return fail(LASSO_ERR_BAD_ARG, "bad shape");
+  if (k > 4096) return fail(LASSO_ERR_UNSUPPORTED, "orthant-wise Newton: k=%lld > 4096", (long long)k);
+  if (!(alpha >= 0.0)) return fail(LASSO_ERR_BAD_ARG, "alpha < 0");
+  if (o->line_search < 0 || o->line_search > 2)
+    return fail(LASSO_ERR_BAD_ARG, "line_search must be one of 0 (brent), 1 (backtrack), 2 (none)");
+  if (o->maxiter < 0 || (o->line_search == 1 && o->ls_maxiter < 1)) return fail(LASSO_ERR_BAD_ARG, "maxiter < 0 or ls_maxiter < 1");
+  if (const lasso_own_trace* t = res->trace) {
+    if (t->capacity < 0 || t->eval_capacity < 0 || (t->capacity > 0 && (!t->t || !t->ls_iters || !t->f || !t->delta_z)) ||
+        (t->eval_capacity > 0 && (!t->eval_iter || !t->eval_t || !t->eval_f)))
+      return fail(LASSO_ERR_BAD_ARG, "trace with a null array");
+  }
+  res->n_iter = res->flags = res->cholesky_info = res->ls_failures = 0;
+  res->f0 = res->f_final = 0.0;
+  if (res->trace) res->trace->eval_count = 0;
+  if (n == 0) return LASSO_OK;
+  if (!x_dev || !w_dev || !z0_dev || !z_out_dev || !workspace_dev) return fail(LASSO_ERR_BAD_ARG, "null pointer");
+  if (ldx < d || ldw < k || ldz < k || ldz0 < k) return fail(LASSO_ERR_BAD_ARG, "leading dimension too small");
+  if (workspace_bytes < lasso_own_workspace_bytes(n, d, k, dtype))
+    return fail(LASSO_ERR_WORKSPACE, "need %zu bytes", lasso_own_workspace_bytes(n, d, k, dtype));
+  return own::solve((const float*)x_dev, ldx, (const float*)w_dev, ldw, (const float*)z0_dev, ldz0, (float*)z_out_dev, ldz,
+                    n, d, k, alpha, *o, res, workspace_dev, static_cast<hipStream_t>(stream));
+}
+
 // ---- unconstrained M-step: update_dict_ridge, dict_learning.py:106-123 ---------------------
 size_t lasso_ridge_workspace_bytes(int64_t d, int64_t k) {
   if (d <= 0 || k <= 0 || k > 4096) return 0;

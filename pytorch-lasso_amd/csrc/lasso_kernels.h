@@ -12,6 +12,8 @@
 
 struct lasso_gpsr_options;
 struct lasso_gpsr_result;
+struct lasso_own_options;
+struct lasso_own_result;
 
 namespace lasso {
 
@@ -559,5 +561,13 @@ const char* conv_form(const ConvGeom& g, int forced_general);     // "implicit" 
 int conv_solve(const float* x, const float* w, const float* z0, float* zout, const ConvGeom& g, double tau,
                const lasso_gpsr_options& o, lasso_gpsr_result* res, void* workspace, hipStream_t st);
 }  // namespace gpsr
+
+// orthant-wise Newton (own.hip): the driver behind lasso_own_solve; returns a lasso_status
+namespace own {
+size_t workspace_bytes(int64_t n, int64_t d, int64_t k);
+int solve(const float* x, int64_t ldx, const float* w, int64_t ldw, const float* z0, int64_t ldz0, float* zout, int64_t ldz,
+          int64_t n, int64_t d, int64_t k, double alpha, const lasso_own_options& o, lasso_own_result* res, void* workspace,
+          hipStream_t st);
+}  // namespace own
 
 }  // namespace lasso

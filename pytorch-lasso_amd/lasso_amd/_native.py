@@ -27,6 +27,8 @@ SOLVE_DEFER_VERDICT = 0x40000       # the verdict's launch is left to lasso_fist
 LR_AUTO = -1.0
 GPSR_ZERO_SOLUTION, GPSR_TAU_FACTOR_CHANGED, GPSR_LINESEARCH_FAILED = 1, 2, 4
 GPSR_DEBIAS_NO_NONZEROS, GPSR_DEBIAS_TOO_MANY = 8, 16
+OWN_BRENT, OWN_BACKTRACK, OWN_NONE = 0, 1, 2
+OWN_LS_NOT_CONVERGED, OWN_NONFINITE = 1, 2
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = None
@@ -65,6 +67,25 @@ class GpsrResult(C.Structure):
                 ('objective', C.c_double), ('main_objective', C.c_double), ('main_rr', C.c_float), ('main_l1', C.c_float),
                 ('main_nz', C.c_int32), ('db_rr', C.c_float), ('db_l1', C.c_float), ('db_nz', C.c_int32),
                 ('trace', C.POINTER(GpsrTrace))]
+
+
+class OwnOptions(C.Structure):
+    """lasso_own_options"""
+    _fields_ = [(name, C.c_int32) for name in ('maxiter', 'line_search', 'ls_maxiter', 'reserved')] + \
+               [(name, C.c_double) for name in ('lr', 'xtol', 'ls_tol', 'ls_decay')]
+
+
+class OwnTrace(C.Structure):
+    """lasso_own_trace: host arrays of the caller"""
+    _pd, _pi = C.POINTER(C.c_double), C.POINTER(C.c_int32)
+    _fields_ = [('capacity', C.c_int32), ('eval_capacity', C.c_int32), ('t', _pd), ('ls_iters', _pi), ('f', _pd),
+                ('delta_z', _pd), ('eval_iter', _pi), ('eval_t', _pd), ('eval_f', _pd), ('eval_count', C.c_int64)]
+
+
+class OwnResult(C.Structure):
+    """lasso_own_result"""
+    _fields_ = [('n_iter', C.c_int32), ('flags', C.c_int32), ('f0', C.c_double), ('f_final', C.c_double),
+                ('cholesky_info', C.c_int32), ('ls_failures', C.c_int32), ('trace', C.POINTER(OwnTrace))]
 
 
 # int (*lasso_allreduce_fn)(void* ctx, double* sums, int count)   (include/lasso_hip.h)
@@ -287,6 +308,11 @@ def _declare(lib):
     lib.lasso_conv_gpsr_solve.restype = i32
     lib.lasso_conv_gpsr_solve.argtypes = [vp, vp, vp, vp] + [i64] * 7 + [i32] * 6 + [i32, dbl, C.POINTER(GpsrOptions),
                                                                                   C.POINTER(GpsrResult), vp, sz, vp]
+    lib.lasso_own_workspace_bytes.restype = sz
+    lib.lasso_own_workspace_bytes.argtypes = [i64, i64, i64, i32]
+    lib.lasso_own_solve.restype = i32
+    lib.lasso_own_solve.argtypes = [vp, i64, vp, i64, vp, i64, vp, i64, i64, i64, i64, i32, dbl,
+                                    C.POINTER(OwnOptions), C.POINTER(OwnResult), vp, sz, vp]
     lib.lasso_cd_solve.restype = i32
     lib.lasso_cd_solve.argtypes = [vp, i64, vp, i64, vp, i64, vp, i64, i64, i64, i64, i32, dbl, i32,
                                    dbl, pi32, pi32, vp, sz, vp]
