@@ -43,6 +43,7 @@
  *   - GPSR-Basic has two entry points on one driver: lasso_gpsr_solve (the dictionary as the operator) and
  *     lasso_conv_gpsr_solve (conv_transpose2d / conv2d as the operator, contiguous NCHW tensors); both LASSO_F32 only.
  *   - the orthant-wise Newton solver is lasso_own_solve: LASSO_F32, any n, d, any pitch, k <= 4096.
+ *   - the iterated-ridge solver is lasso_iter_ridge_solve: LASSO_F32, any n, d, any pitch, k <= 1024.
  */
 #ifndef LASSO_HIP_H_
 #define LASSO_HIP_H_
@@ -906,6 +907,61 @@ int lasso_own_solve(const void* x_dev, int64_t ldx, const void* w_dev, int64_t l
                     void* z_out_dev, int64_t ldz, int64_t n, int64_t d, int64_t k, int dtype, double alpha,
                     const lasso_own_options* options, lasso_own_result* result,
                     void* workspace_dev, size_t workspace_bytes, void* stream);
+
+/* ---- iterated ridge: replaces iterative_ridge(), lasso/linear/solvers/iterative_ridge.py:11-141 (cg=False) ----
+ * min_z 0.5 |z W^T - x|^2 + alpha |z|_1 over the whole batch by iterated ridge regression (csrc/iter_ridge.hip).  Once
+ * per solve G = W^T W and rhs = x W; per iteration every row solves
+ *   (G[S,S] + diag(alpha / |z_S| + tikhonov)) z_S = rhs_S on its own support S = {j : |z_j| >= eps}
+ * with a blocked Cholesky in LDS (supports up to 256) or in a fixed scratch of the workspace (up to 1024); entries off
+ * the support keep their value.  line_search != 0: p = z_sol - z, t from a bounded Brent search on (0, 10)
+ * (csrc/brent_host.hpp) of f(z + t p), evaluated from three sums of the residual and p W^T plus one pass over [n,k] per
+ * trial and handed to the search as an un-rounded double; z += t p on the support.  The solve stops once
+ * sum |update| <= n k tol (converged), on a NaN objective or update, or after maxiter iterations.  Every sum is folded
+ * in double in a fixed order: two solves of the same arguments give the same bits.
+ *   options : maxiter >= 0, line_search 0 / 1, tol >= 0 (per element), tikhonov >= 0, eps >= 0, reserved = 0.
+ *   result  : n_iter, status, the objective of z0 and the last fval, bad_row / bad_minor (-1 / 0, or the lowest row whose
+ *             system had a non-positive or NaN pivot and 1 + that pivot's index in the compacted system: then
+ *             LASSO_ERR_BAD_ARG and z_out is not written), and -- trace non-NULL -- host arrays of the caller: per iteration
+ *             (capacity) fval, sum |update|, t, the Brent evaluations, the largest and the mean support of the new z; per
+ *             Brent evaluation (eval_capacity; eval_count is written) the iteration (1-based), t and f.
+ * lasso_iter_ridge_rows is one masked per-row solve on its own: z_sol [n][k] from G [k][k], rhs [n][k] and z [n][k]
+ * (masked entries of z_sol are 0); its workspace is lasso_iter_ridge_workspace_bytes(n, 1, k, dtype); support_max_out is
+ * nullable.  z_sol may not alias z.
+ * Refusals before any HIP call: null pointers, n < 0, d or k < 1, a leading dimension below the row length, alpha < 0,
+ * negative options or reserved != 0 are LASSO_ERR_BAD_ARG; a dtype other than LASSO_F32 and k > 1024
+ * LASSO_ERR_UNSUPPORTED (the workspace query returns 0); a short workspace LASSO_ERR_WORKSPACE.  n = 0 writes nothing.
+ * The workspace grows linearly in n: the general tier's scratch is at most 256 triangles and 256 MiB.  The calls block. */
+typedef struct lasso_iter_ridge_options {
+  int32_t maxiter, line_search;
+  double tol, tikhonov, eps;
+  int64_t reserved;                       /* must be 0 */
+} lasso_iter_ridge_options;
+typedef struct lasso_iter_ridge_trace {
+  int32_t capacity;                       /* iterations the arrays below hold */
+  int32_t eval_capacity;                  /* Brent evaluations eval_* hold */
+  double* f; double* update; double* t; int32_t* ls_evals; int32_t* support_max; double* support_mean;
+  int32_t* eval_iter; double* eval_t; double* eval_f;
+  int64_t eval_count;                     /* out: evaluations the solve made (may exceed eval_capacity) */
+} lasso_iter_ridge_trace;
+#define LASSO_ITER_RIDGE_CONVERGED 0      /* sum |update| <= n k tol */
+#define LASSO_ITER_RIDGE_NAN 1            /* NaN objective or update */
+#define LASSO_ITER_RIDGE_MAXITER 2
+typedef struct lasso_iter_ridge_result {
+  int32_t n_iter, status;
+  double f0, f_final;
+  int64_t bad_row;
+  int32_t bad_minor, pad_;
+  lasso_iter_ridge_trace* trace;          /* nullable */
+} lasso_iter_ridge_result;
+size_t lasso_iter_ridge_workspace_bytes(int64_t n, int64_t d, int64_t k, int dtype);
+int lasso_iter_ridge_solve(const void* x_dev, int64_t ldx, const void* w_dev, int64_t ldw, const void* z0_dev,
+                           int64_t ldz0, void* z_out_dev, int64_t ldz, int64_t n, int64_t d, int64_t k, int dtype,
+                           double alpha, const lasso_iter_ridge_options* options, lasso_iter_ridge_result* result,
+                           void* workspace_dev, size_t workspace_bytes, void* stream);
+int lasso_iter_ridge_rows(const void* g_dev, int64_t ldg, const void* rhs_dev, int64_t ldr, const void* z_dev,
+                          int64_t ldz, void* z_sol_dev, int64_t ldzs, int64_t n, int64_t k, int dtype, double alpha,
+                          double tikhonov, double eps, int64_t* bad_row_out, int32_t* bad_minor_out,
+                          int32_t* support_max_out, void* workspace_dev, size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

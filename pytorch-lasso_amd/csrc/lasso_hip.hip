@@ -2937,6 +2937,68 @@ int lasso_own_solve(const void* x_dev, int64_t ldx, const void* w_dev, int64_t l
                     n, d, k, alpha, *o, res, workspace_dev, static_cast<hipStream_t>(stream));
 }
 
+// ---- iterated ridge: iterative_ridge.py:11-141 (csrc/iter_ridge.hip) -------------------------
+size_t lasso_iter_ridge_workspace_bytes(int64_t n, int64_t d, int64_t k, int dtype) {
+  if (dtype != LASSO_F32 || n < 0 || d <= 0 || k <= 0 || k > 1024 || n > INT32_MAX || d > INT32_MAX) return 0;
+  return iter_ridge::workspace_bytes(n, d, k);
+}
+
+int lasso_iter_ridge_solve(const void* x_dev, int64_t ldx, const void* w_dev, int64_t ldw, const void* z0_dev, int64_t ldz0,
+                           void* z_out_dev, int64_t ldz, int64_t n, int64_t d, int64_t k, int dtype, double alpha,
+                           const lasso_iter_ridge_options* o, lasso_iter_ridge_result* res, void* workspace_dev,
+                           size_t workspace_bytes, void* stream) {
+  if (dtype != LASSO_F32) return fail(LASSO_ERR_UNSUPPORTED, "iterated ridge: dtype %d (fp32 tensors only)", dtype);
+  if (!o || !res) return fail(LASSO_ERR_BAD_ARG, "null options / result");
+  if (n < 0 || d <= 0 || k <= 0 || n > INT32_MAX || d > INT32_MAX || k > INT32_MAX)
+    return fail(LASSO_ERR_BAD_ARG, "bad shape");
+  if (k > 1024) return fail(LASSO_ERR_UNSUPPORTED, "iterated ridge: k=%lld > 1024", (long long)k);
+  if (!(alpha >= 0.0)) return fail(LASSO_ERR_BAD_ARG, "alpha < 0");
+  if (o->reserved != 0) return fail(LASSO_ERR_BAD_ARG, "iterated ridge: reserved must be 0");
+  if (o->maxiter < 0 || o->line_search < 0 || o->line_search > 1 || !(o->tol >= 0.0) || !(o->tikhonov >= 0.0) || !(o->eps >= 0.0))
+    return fail(LASSO_ERR_BAD_ARG, "maxiter, tol, tikhonov, eps >= 0 and line_search 0 / 1 are required");
+  if (const lasso_iter_ridge_trace* t = res->trace) {
+    if (t->capacity < 0 || t->eval_capacity < 0 ||
+        (t->capacity > 0 && (!t->f || !t->update || !t->t || !t->ls_evals || !t->support_max || !t->support_mean)) ||
+        (t->eval_capacity > 0 && (!t->eval_iter || !t->eval_t || !t->eval_f)))
+      return fail(LASSO_ERR_BAD_ARG, "trace with a null array");
+  }
+  res->n_iter = 0;
+  res->status = LASSO_ITER_RIDGE_MAXITER;
+  res->f0 = res->f_final = 0.0;
+  res->bad_row = -1;
+  res->bad_minor = res->pad_ = 0;
+  if (res->trace) res->trace->eval_count = 0;
+  if (n == 0) return LASSO_OK;
+  if (!x_dev || !w_dev || !z0_dev || !z_out_dev || !workspace_dev) return fail(LASSO_ERR_BAD_ARG, "null pointer");
+  if (ldx < d || ldw < k || ldz < k || ldz0 < k) return fail(LASSO_ERR_BAD_ARG, "leading dimension too small");
+  if (workspace_bytes < lasso_iter_ridge_workspace_bytes(n, d, k, dtype))
+    return fail(LASSO_ERR_WORKSPACE, "need %zu bytes", lasso_iter_ridge_workspace_bytes(n, d, k, dtype));
+  return iter_ridge::solve((const float*)x_dev, ldx, (const float*)w_dev, ldw, (const float*)z0_dev, ldz0, (float*)z_out_dev,
+                           ldz, n, d, k, alpha, *o, res, workspace_dev, static_cast<hipStream_t>(stream));
+}
+
+int lasso_iter_ridge_rows(const void* g_dev, int64_t ldg, const void* rhs_dev, int64_t ldr, const void* z_dev, int64_t ldz,
+                          void* z_sol_dev, int64_t ldzs, int64_t n, int64_t k, int dtype, double alpha, double tikhonov,
+                          double eps, int64_t* bad_row_out, int32_t* bad_minor_out, int32_t* support_max_out,
+                          void* workspace_dev, size_t workspace_bytes, void* stream) {
+  if (dtype != LASSO_F32) return fail(LASSO_ERR_UNSUPPORTED, "iterated ridge: dtype %d (fp32 tensors only)", dtype);
+  if (!bad_row_out || !bad_minor_out) return fail(LASSO_ERR_BAD_ARG, "null result");
+  if (n < 0 || k <= 0 || n > INT32_MAX || k > INT32_MAX) return fail(LASSO_ERR_BAD_ARG, "bad shape");
+  if (k > 1024) return fail(LASSO_ERR_UNSUPPORTED, "iterated ridge: k=%lld > 1024", (long long)k);
+  if (!(alpha >= 0.0) || !(tikhonov >= 0.0) || !(eps >= 0.0)) return fail(LASSO_ERR_BAD_ARG, "alpha, tikhonov, eps >= 0 are required");
+  *bad_row_out = -1;
+  *bad_minor_out = 0;
+  if (support_max_out) *support_max_out = 0;
+  if (n == 0) return LASSO_OK;
+  if (!g_dev || !rhs_dev || !z_dev || !z_sol_dev || !workspace_dev) return fail(LASSO_ERR_BAD_ARG, "null pointer");
+  if (ldg < k || ldr < k || ldz < k || ldzs < k) return fail(LASSO_ERR_BAD_ARG, "leading dimension too small");
+  if (workspace_bytes < lasso_iter_ridge_workspace_bytes(n, 1, k, dtype))
+    return fail(LASSO_ERR_WORKSPACE, "need %zu bytes", lasso_iter_ridge_workspace_bytes(n, 1, k, dtype));
+  return iter_ridge::rows((const float*)g_dev, ldg, (const float*)rhs_dev, ldr, (const float*)z_dev, ldz, (float*)z_sol_dev,
+                          ldzs, n, k, alpha, tikhonov, eps, bad_row_out, bad_minor_out, support_max_out, workspace_dev,
+                          static_cast<hipStream_t>(stream));
+}
+
 // ---- unconstrained M-step: update_dict_ridge, dict_learning.py:106-123 ---------------------
 size_t lasso_ridge_workspace_bytes(int64_t d, int64_t k) {
   if (d <= 0 || k <= 0 || k > 4096) return 0;

@@ -14,6 +14,8 @@ struct lasso_gpsr_options;
 struct lasso_gpsr_result;
 struct lasso_own_options;
 struct lasso_own_result;
+struct lasso_iter_ridge_options;
+struct lasso_iter_ridge_result;
 
 namespace lasso {
 
@@ -569,5 +571,16 @@ int solve(const float* x, int64_t ldx, const float* w, int64_t ldw, const float*
           int64_t n, int64_t d, int64_t k, double alpha, const lasso_own_options& o, lasso_own_result* res, void* workspace,
           hipStream_t st);
 }  // namespace own
+
+// iterated ridge (iter_ridge.hip): the drivers behind lasso_iter_ridge_solve / lasso_iter_ridge_rows; return a lasso_status
+namespace iter_ridge {
+size_t workspace_bytes(int64_t n, int64_t d, int64_t k);
+int solve(const float* x, int64_t ldx, const float* w, int64_t ldw, const float* z0, int64_t ldz0, float* zout, int64_t ldz,
+          int64_t n, int64_t d, int64_t k, double alpha, const lasso_iter_ridge_options& o, lasso_iter_ridge_result* res,
+          void* workspace, hipStream_t st);
+int rows(const float* g, int64_t ldg, const float* rhs, int64_t ldr, const float* z, int64_t ldz, float* zsol, int64_t ldzs,
+         int64_t n, int64_t k, double alpha, double tikhonov, double eps, int64_t* bad_row, int32_t* bad_minor,
+         int32_t* support_max, void* workspace, hipStream_t st);
+}  // namespace iter_ridge
 
 }  // namespace lasso

@@ -29,6 +29,7 @@ GPSR_ZERO_SOLUTION, GPSR_TAU_FACTOR_CHANGED, GPSR_LINESEARCH_FAILED = 1, 2, 4
 GPSR_DEBIAS_NO_NONZEROS, GPSR_DEBIAS_TOO_MANY = 8, 16
 OWN_BRENT, OWN_BACKTRACK, OWN_NONE = 0, 1, 2
 OWN_LS_NOT_CONVERGED, OWN_NONFINITE = 1, 2
+ITER_RIDGE_CONVERGED, ITER_RIDGE_NAN, ITER_RIDGE_MAXITER = 0, 1, 2
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = None
@@ -86,6 +87,27 @@ class OwnResult(C.Structure):
     """lasso_own_result"""
     _fields_ = [('n_iter', C.c_int32), ('flags', C.c_int32), ('f0', C.c_double), ('f_final', C.c_double),
                 ('cholesky_info', C.c_int32), ('ls_failures', C.c_int32), ('trace', C.POINTER(OwnTrace))]
+
+
+class IterRidgeOptions(C.Structure):
+    """lasso_iter_ridge_options"""
+    _fields_ = [('maxiter', C.c_int32), ('line_search', C.c_int32), ('tol', C.c_double), ('tikhonov', C.c_double),
+                ('eps', C.c_double), ('reserved', C.c_int64)]
+
+
+class IterRidgeTrace(C.Structure):
+    """lasso_iter_ridge_trace: host arrays of the caller"""
+    _pd, _pi = C.POINTER(C.c_double), C.POINTER(C.c_int32)
+    _fields_ = [('capacity', C.c_int32), ('eval_capacity', C.c_int32), ('f', _pd), ('update', _pd), ('t', _pd),
+                ('ls_evals', _pi), ('support_max', _pi), ('support_mean', _pd), ('eval_iter', _pi), ('eval_t', _pd),
+                ('eval_f', _pd), ('eval_count', C.c_int64)]
+
+
+class IterRidgeResult(C.Structure):
+    """lasso_iter_ridge_result"""
+    _fields_ = [('n_iter', C.c_int32), ('status', C.c_int32), ('f0', C.c_double), ('f_final', C.c_double),
+                ('bad_row', C.c_int64), ('bad_minor', C.c_int32), ('pad_', C.c_int32),
+                ('trace', C.POINTER(IterRidgeTrace))]
 
 
 # int (*lasso_allreduce_fn)(void* ctx, double* sums, int count)   (include/lasso_hip.h)
@@ -313,6 +335,14 @@ def _declare(lib):
     lib.lasso_own_solve.restype = i32
     lib.lasso_own_solve.argtypes = [vp, i64, vp, i64, vp, i64, vp, i64, i64, i64, i64, i32, dbl,
                                     C.POINTER(OwnOptions), C.POINTER(OwnResult), vp, sz, vp]
+    lib.lasso_iter_ridge_workspace_bytes.restype = sz
+    lib.lasso_iter_ridge_workspace_bytes.argtypes = [i64, i64, i64, i32]
+    lib.lasso_iter_ridge_solve.restype = i32
+    lib.lasso_iter_ridge_solve.argtypes = [vp, i64, vp, i64, vp, i64, vp, i64, i64, i64, i64, i32, dbl,
+                                           C.POINTER(IterRidgeOptions), C.POINTER(IterRidgeResult), vp, sz, vp]
+    lib.lasso_iter_ridge_rows.restype = i32
+    lib.lasso_iter_ridge_rows.argtypes = [vp, i64, vp, i64, vp, i64, vp, i64, i64, i64, i32, dbl, dbl, dbl,
+                                          C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_int32), vp, sz, vp]
     lib.lasso_cd_solve.restype = i32
     lib.lasso_cd_solve.argtypes = [vp, i64, vp, i64, vp, i64, vp, i64, i64, i64, i64, i32, dbl, i32,
                                    dbl, pi32, pi32, vp, sz, vp]
