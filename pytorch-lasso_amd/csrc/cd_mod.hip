@@ -191,7 +191,7 @@ __global__ __launch_bounds__(256) void cd_mod_rows_kernel(const CdModParams p) {
         const unsigned j = first_from(cursor, [&](auto i) {
           constexpr int I = decltype(i)::value;
           const float zi = z[I / HN][I % HN], qi = q[I / HN][I % HN];
-          return zi != 0.0f || __builtin_fabsf(qi) > alpha;
+          return zi != 0.0f || !(__builtin_fabsf(qi) <= alpha);      // (a NaN q is visited: S(NaN) is NaN, :118-121)
         });
         if (j == kNone) break;
         const int owner = (j & 255) >> 2, slot = ((j >> 8) << 2) | (j & 3);

@@ -451,6 +451,9 @@ __global__ __launch_bounds__(256) void conv_pack_w_kernel(const float* __restric
   }
 }
 
+// max(a, b) of two powers (>= +0) that keeps a NaN like torch.max (lip_const.py:131); fmaxf drops it
+__device__ __forceinline__ float nan_max(float a, float b) { return (b > a || b != b) ? b : a; }
+
 // lip_const.py:96-135.  taps [O][I][T] (T = ksize^2; O <= I after the reference's swap).
 // One workgroup per o: power(o, f) = sum_i (sum_t tap*cos(phase[t][f]))^2 + (... sin ...)^2,
 // out[o] = max_f power.  phase[t][f] = w0[f]*h0[t] + w1[f]*h1[t] (fp32, like the reference).
@@ -479,12 +482,12 @@ __global__ __launch_bounds__(256) void conv_lip_kernel(const float* __restrict__
       }
       power += re * re + im * im;
     }
-    best = fmaxf(best, power);
+    best = nan_max(best, power);
   }
   sred[threadIdx.x] = best;
   __syncthreads();
   for (int s = 128; s > 0; s >>= 1) {
-    if ((int)threadIdx.x < s) sred[threadIdx.x] = fmaxf(sred[threadIdx.x], sred[threadIdx.x + s]);
+    if ((int)threadIdx.x < s) sred[threadIdx.x] = nan_max(sred[threadIdx.x], sred[threadIdx.x + s]);
     __syncthreads();
   }
   if (threadIdx.x == 0) out_max[o] = sred[0];

@@ -366,6 +366,9 @@ __global__ __launch_bounds__(256) void conv_axpy_f64_kernel(double* __restrict__
 // lip_const.py:96-135 in double.  taps [O][I][T] through the strides (so, si) (T = ksize^2; O <= I after the
 // reference's swap).  One workgroup per o: power(o, f) = sum_i (sum_t tap cos(phase[t][f]))^2 + (... sin ...)^2,
 // out[o] = max_f power; phase[t][f] = w0[f] h0[t] + w1[f] h1[t], the grid freq[i] = 2 pi i / (sample - 1).
+// max(a, b) of two powers (>= +0) that keeps a NaN like torch.max (lip_const.py:131); fmax drops it
+__device__ __forceinline__ double nan_max(double a, double b) { return (b > a || b != b) ? b : a; }
+
 __global__ __launch_bounds__(256) void conv_lip_grid_f64_kernel(double* __restrict__ freq, int sample) {
   for (int i = threadIdx.x; i < sample; i += 256) freq[i] = (2.0 * M_PI * (double)i) / (double)(sample - 1);
 }
@@ -392,12 +395,12 @@ __global__ __launch_bounds__(256) void conv_lip_f64_kernel(const double* __restr
       power += re * re;             // :128-130: the two sums of squares apart, then their sum
       power_im += im * im;
     }
-    best = fmax(best, power + power_im);
+    best = nan_max(best, power + power_im);
   }
   sred[threadIdx.x] = best;
   __syncthreads();
   for (int s = 128; s > 0; s >>= 1) {
-    if ((int)threadIdx.x < s) sred[threadIdx.x] = fmax(sred[threadIdx.x], sred[threadIdx.x + s]);
+    if ((int)threadIdx.x < s) sred[threadIdx.x] = nan_max(sred[threadIdx.x], sred[threadIdx.x + s]);
     __syncthreads();
   }
   if (threadIdx.x == 0) out_max[blockIdx.x] = sred[0];

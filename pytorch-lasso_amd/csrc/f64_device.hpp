@@ -20,8 +20,12 @@ __device__ __forceinline__ double block_sum(double v, double* red) {
   return red[0];
 }
 
-__device__ __forceinline__ double softshrink(double u, double lam) {      // ATen's softshrink
-  return u > lam ? u - lam : (u < -lam ? u + lam : 0.0);
+// ATen's softshrink, u > lam ? u - lam : (u < -lam ? u + lam : 0), evaluated as u - clamp(u, -lam, lam) like the fp32
+// kernels (tile_device.hpp): u - lam and u - (-lam) are the same IEEE operations, u - u is +0 (for -0 and at the ties
+// |u| == lam as well), +-Inf - (+-lam) stays +-Inf -- and a NaN u stays NaN as in ATen (fmax drops it, the subtraction
+// brings it back), where the ternary sent it to 0.
+__device__ __forceinline__ double softshrink(double u, double lam) {
+  return u - fmin(fmax(u, -lam), lam);
 }
 
 }  // namespace f64

@@ -1043,8 +1043,10 @@ int iteration_sync(BtSolve& c, bool* stop) {
     if (c.reduce(c.reduce_ctx, &dsum, 1) != 0) return fail(LASSO_ERR_HIP, "all-reduce callback failed");
     host.delta = (float)dsum;
   }
-  c.prev_trials = host.flags[2] + 1;
-  c.trace.record(c.it, host.flags[2] + 1, host.fvals[2], host.fvals[0]);
+  // (the forced step at lr0 behind kBtMaxTrials rejected trials is no trial: the reference counts 1000, ista.py:17,48-52)
+  const int trials = std::min(host.flags[2] + 1, kBtMaxTrials);
+  c.prev_trials = trials;
+  c.trace.record(c.it, trials, host.fvals[2], host.fvals[0]);
   c.last = host.delta;
   ++c.it;
   *stop = host.delta <= c.stop_budget;                                               // :93-95

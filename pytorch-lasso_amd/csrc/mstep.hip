@@ -631,6 +631,11 @@ __global__ __launch_bounds__(256) void sum_splits_kernel(const float* __restrict
   C[(idx / cols) * ldc + idx % cols] = ordered_split_sum(part + idx, split_stride, splits);
 }
 
+// clamp_(lo, None) of dict_learning.py:87-88 (lo = -Inf without `positive`): fmaxf for every non-NaN t, bit for bit,
+// and a NaN t stays NaN as in ATen -- fmaxf alone returns lo for it, which hides a NaN of the Gram matrices behind a
+// zero (or -Inf) entry of the atom
+__device__ __forceinline__ float clamp_lo(float t, float lo) { return t != t ? t : fmaxf(t, lo); }
+
 // Wave-wide sum on the ALU path (no LDS crossbar): DPP row_shr 1,2,4,8 leaves each
 // 16-lane row's total in its last lane; four readlanes + scalar-operand adds give the
 // wave total in a fixed order.  Result is wave-uniform.
@@ -755,7 +760,7 @@ __global__ __launch_bounds__(64 * NW) void sweep_block_kernel(const SweepParams 
     float v[F], ss = 0.0f;
 #pragma unroll
     for (int f = 0; f < F; ++f) {
-      v[f] = fmaxf(fmaf(cf[a], dcur[f], u[a][f]), lo);            // u_j = U_j + A_jj d_j   (:85-88)
+      v[f] = clamp_lo(fmaf(cf[a], dcur[f], u[a][f]), lo);         // u_j = U_j + A_jj d_j   (:85-88)
       ss = fmaf(v[f], v[f], ss);
     }
     ss = wave_sum_dpp(ss);
@@ -1222,7 +1227,7 @@ __global__ __launch_bounds__(256) void sweep_persist_kernel(const SweepParams p,
             float v[F], ss = 0.0f;
 #pragma unroll
             for (int f = 0; f < F; ++f) {
-              v[f] = fmaxf(fmaf(caa, dc[f], u[Q0][f][r0]), lo);            // u_j = U_j + A_jj d_j   (:85-88)
+              v[f] = clamp_lo(fmaf(caa, dc[f], u[Q0][f][r0]), lo);         // u_j = U_j + A_jj d_j   (:85-88)
               ss = fmaf(v[f], v[f], ss);
             }
 #ifndef LASSO_ABL_NORED      // (timing ablations: results invalid)
@@ -1572,7 +1577,7 @@ __global__ __launch_bounds__(256) void sweep_small_kernel(const SweepParams p) {
         for (int Q = Qs; Q < JB / 4; ++Q) cq[Q] = cqn[Q];
         const float caa = caan, dc = dcn;
         if constexpr (a + 1 < JB) fetch(std::integral_constant<int, a + 1>{});
-        const float v = fmaxf(fmaf(caa, dc, u[Q0][r0]), lo);              // u_j = U_j + A_jj d_j   (:85-88)
+        const float v = clamp_lo(fmaf(caa, dc, u[Q0][r0]), lo);           // u_j = U_j + A_jj d_j   (:85-88)
         float ss = fmaf(v, v, 0.0f);
         ss = wave_sum_dpp_bcast(ss);
         const bool deg = ss < eps2;

@@ -184,7 +184,7 @@ __global__ __launch_bounds__(64 * NW) void sweep_block_f64_kernel(const SweepF64
     for (int i = 0; i < kMB; ++i) {
       const int a = s + i;
       double v = u[i] + sA[a][a] * dold[i];                            // u_j = U_j + A_jj d_j   (:85-86)
-      if (p.positive) v = fmax(v, 0.0);                                // :87-88
+      if (p.positive) v = v != v ? v : fmax(v, 0.0);                   // :87-88 (clamp_ keeps a NaN, fmax drops it)
       const double ws = wave_sum(v * v);
       if ((tid & 63) == 0) red[i & 1][tid >> 6] = ws;
       __syncthreads();

@@ -55,14 +55,17 @@ inline int next_stop_chunk(T first, T last, T budget, int c, int it, int chunk_m
 // Size of the next chunk of the fused fp32 solve's chunked form (solve_chunked in lasso_hip.hip; its twin for row shards
 // is parallel._next_tile_chunk) -- purely a scheduling heuristic, the stop decision itself stays exact: estimate the
 // iterations left until a sum <= budget from the geometric decay over the chunk's `c` sums and approach the predicted
-// stop with short chunks so that little work is wasted or replayed.
+// stop with short chunks so that little work is wasted or replayed.  A chunk that holds a NaN sum predicts no stop
+// (NaN <= budget is false, and a NaN code stays NaN): the full chunk.  The maxima keep a NaN for that -- std::max,
+// like Python's max(), keeps or drops one depending on where it stands.
 inline int next_tile_chunk(const float* sums, int c, float budget, int chunk_max) {
   int next_chunk = chunk_max;
   if (c >= 8 && budget > 0.0f) {
     const int h = c / 2;
     float hi = 0.0f, lo = 0.0f;
-    for (int i = 0; i < h; ++i) hi = std::max(hi, sums[i]);
-    for (int i = h; i < c; ++i) lo = std::max(lo, sums[i]);
+    for (int i = 0; i < h; ++i) hi = (sums[i] > hi || sums[i] != sums[i]) ? sums[i] : hi;
+    for (int i = h; i < c; ++i) lo = (sums[i] > lo || sums[i] != sums[i]) ? sums[i] : lo;
+    if (hi != hi || lo != lo) return chunk_max;
     if (lo > budget && hi > lo) {
       const double rate = log((double)hi / lo) / h;              // per-iteration log decay
       const double left = log((double)lo / budget) / rate;       // iterations still needed

@@ -112,11 +112,14 @@ def _first_stop(hdelta, budget):        # ista.py:93 over a chunk's sums: the in
 
 def _next_tile_chunk(hdelta, c, budget):
     """Size of the chunk after one of ``c`` sums without a stop, from their geometric decay: scheduling only, and alike on
-    every rank.  Twin of next_tile_chunk in csrc/stoprule_host.hpp (tests/test_stoprule_host_cpu.py holds them equal)."""
+    every rank.  Twin of next_tile_chunk in csrc/stoprule_host.hpp (tests/test_stoprule_host_cpu.py holds them equal),
+    a chunk with a NaN sum included: no stop is coming, the full chunk (max() alone keeps a NaN only in front)."""
     chunk = 64
     if c >= 8 and budget > 0:
         h = c // 2
-        hi, lo = max(hdelta[:h]), max(hdelta[h:])
+        if any(v != v for v in hdelta[:c]):
+            return chunk
+        hi, lo = max(0.0, max(hdelta[:h])), max(0.0, max(hdelta[h:c]))
         if lo > budget and hi > lo:
             left = math.log(lo / budget) / (math.log(hi / lo) / h)
             if left < 128:

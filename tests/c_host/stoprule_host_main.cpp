@@ -3,11 +3,12 @@
 //   budget <rows> <k> <tol>                                -> "budget <f32 bits> <f64 bits>"
 //   tile <budget> <c> <c sums>                             -> "tile <next chunk>"          (next_tile_chunk, chunk_max 64)
 //   chunk <f|d> <first> <last> <budget> <c> <it>           -> "chunk <next chunk>"         (next_stop_chunk, chunk_max 64)
+//   first <f|d> <budget> <c> <c sums>                      -> "first <index or -1>"        (first_stop)
 //   spec <f|d> <maxiter> <budget> <count> <count sums>     -> the event log of speculate_stop_rule, then "spec <it> <last bits>"
 //   words <w0> <w1> <w2> <w3>                              -> "words <iterations> <last delta bits> <redo> <warned>"
 // `spec` scripts a solve: iteration i (from 0) has the sum sums[i]; the state of the solve is the number of the next
 // iteration, which `save` / `restore` checkpoint like the real solvers checkpoint z and y.
-// Numbers are read with strtod (hexadecimal floats are exact).
+// Numbers are read with strtod (hexadecimal floats are exact; "nan", "inf" and "-inf" are what they say).
 #include <cinttypes>
 #include <cstdio>
 #include <cstdlib>
@@ -34,6 +35,20 @@ static int chunk_cmd() {
   double first, last, budget, c, it;
   if (!number(&first) || !number(&last) || !number(&budget) || !number(&c) || !number(&it)) return 2;
   printf("chunk %d\n", lasso::next_stop_chunk<T>((T)first, (T)last, (T)budget, (int)c, (int)it, 64));
+  return 0;
+}
+
+template <class T>
+static int first_cmd() {
+  double budget, c;
+  if (!number(&budget) || !number(&c) || c < 1 || c > 64) return 2;
+  T sums[64];
+  for (int i = 0; i < (int)c; ++i) {
+    double v;
+    if (!number(&v)) return 2;
+    sums[i] = (T)v;
+  }
+  printf("first %d\n", lasso::first_stop<T>(sums, (int)c, (T)budget));
   return 0;
 }
 
@@ -100,12 +115,13 @@ int main() {
         sums[i] = (float)v;
       }
       printf("tile %d\n", lasso::next_tile_chunk(sums, (int)c, (float)budget, 64));
-    } else if (!strcmp(cmd, "chunk") || !strcmp(cmd, "spec")) {
+    } else if (!strcmp(cmd, "chunk") || !strcmp(cmd, "spec") || !strcmp(cmd, "first")) {
       char type[8];
       if (scanf("%7s", type) != 1) return 2;
       const bool f = type[0] == 'f';
       const int s = !strcmp(cmd, "chunk") ? (f ? chunk_cmd<float>() : chunk_cmd<double>())
-                                          : (f ? spec_cmd<float>() : spec_cmd<double>());
+                    : !strcmp(cmd, "first") ? (f ? first_cmd<float>() : first_cmd<double>())
+                                            : (f ? spec_cmd<float>() : spec_cmd<double>());
       if (s) return s;
     } else if (!strcmp(cmd, "words")) {
       lasso::StopWords words;

@@ -4,7 +4,8 @@ floats, integer for integer where it schedules, event for event where it drives 
 (tests/c_host/stoprule_host_main.cpp, host compiler only) prints what the header computes; it is built a second time
 with AddressSanitizer + UBSan and must come back clean with the same output.  The sizers are compared against ports
 that use math.log / math.log2 -- the same libm as the C++ -- and next_tile_chunk against its twin in
-lasso_amd.parallel."""
+lasso_amd.parallel.  Every function also gets chunks of non-finite sums (NONFINITE_CHUNKS: what a batch with a NaN or
+Inf sample produces): no stop, a chunk size in [1, 64], maxiter iterations with a NaN last sum, no undefined cast."""
 import math
 import os
 import subprocess
@@ -47,6 +48,26 @@ def _budget_expected():
             for r, k, tol in BUDGET_ROWS]
 
 
+# ---- chunks of non-finite sums ------------------------------------------------------------------------------------
+NAN, INF = float("nan"), float("inf")
+
+
+def _nonfinite_chunks(c):
+    """name -> c sums above a budget of 1: all NaN; NaN from some index on (a NaN code stays NaN); all +Inf; finite then
+    +Inf; +Inf then finite (an Inf sample's first sum is +Inf) -- and, for the sizers, a NaN in front of finite sums"""
+    fin = [50.0 - 0.5 * i for i in range(c)]
+    out = {"all NaN": [NAN] * c, "all +Inf": [INF] * c}
+    for at in sorted({1, c // 2 - 1, c // 2, c // 2 + 1, c - 1} & set(range(1, c))):
+        out["NaN from %d on" % at] = fin[:at] + [NAN] * (c - at)
+        out["finite then +Inf from %d" % at] = fin[:at] + [INF] * (c - at)
+        out["+Inf then finite from %d" % at] = [INF] * at + fin[at:]
+        out["NaN then finite from %d" % at] = [NAN] * at + fin[at:]
+    return out
+
+
+NONFINITE_CHUNKS = [(name, sums) for c in (1, 8, 9, 64) for name, sums in sorted(_nonfinite_chunks(c).items())]
+
+
 # ---- next_tile_chunk ----------------------------------------------------------------------------------------------
 def _decaying(left, c=8, lo=8.0, budget=1.0):
     """a chunk of c sums whose halves' maxima predict about `left` iterations to the budget"""
@@ -76,7 +97,11 @@ def _tile_rows():
         s = rng.uniform(1.0, 1e4) * np.exp(-rate * np.arange(c)) * rng.uniform(0.8, 1.2, c)
         budget = float(f32(s[-1] * rng.choice([0.9, 0.3, 0.05, 1e-3, 1e-6])))
         rows.append((budget, [float(v) for v in s.astype(f32)]))
-    return rows
+    return rows + _tile_rows_nonfinite()
+
+
+def _tile_rows_nonfinite():
+    return [(budget, sums) for budget in (1.0, 20.0, 0.0) for _, sums in NONFINITE_CHUNKS]
 
 
 def _left(budget, sums):
@@ -108,6 +133,19 @@ def _chunk_rows(T):
             for last in values:
                 for c, it in ((1, 1), (2, 3), (5, 10), (64, 64), (64, 200), (7, 2)):
                     rows.append((float(first), float(last), float(budget), c, it))
+    return rows + _chunk_rows_nonfinite(T)
+
+
+def _chunk_rows_nonfinite(T):
+    """first / last sums of the non-finite chunks (and every pairing of NaN, +Inf and finite values)"""
+    pairs = {(sums[0], sums[-1], len(sums)) for _, sums in NONFINITE_CHUNKS}
+    pairs |= {(a, b, c) for a in (NAN, INF, 0.0, 3.0, 1e30) for b in (NAN, INF, 0.0, 3.0, 1e30) for c in (1, 2, 64)
+              if a != a or b != b or INF in (a, b)}
+    rows = []
+    for first, last, c in sorted(pairs, key=repr):
+        for budget in (0.0, 1e-4, 1.0):
+            for it in (c, 3 * c, 200):
+                rows.append((float(T(first)), float(T(last)), float(T(budget)), c, it))
     return rows
 
 
@@ -182,7 +220,15 @@ def _spec_scripts(T):
     ]
     # a stop at every place of the early chunks: their last iteration (no restore) and strictly inside (restore + replay)
     scripts += [("stop at iteration %d" % (at + 1), 80, b, with_stop(at)) for at in range(1, 24)]
+    # non-finite sums: never a stop, maxiter iterations
+    for maxiter in (1, 2, 12, 70):
+        for name, sums in sorted(_nonfinite_chunks(max(maxiter, 2)).items()):
+            if "then finite" not in name:           # (finite sums behind them are covered by the scripts above)
+                scripts.append(("nonfinite: %s, maxiter %d" % (name, maxiter), maxiter, b, [T(v) for v in sums]))
     return [(name, maxiter, float(T(budget)), [float(T(v)) for v in sums]) for name, maxiter, budget, sums in scripts]
+
+
+FIRST_BUDGETS = (1.0, 0.0, 1e30)
 
 
 WORDS = [(7, 0x3F800000, 0, 0), (64, 0x7FC00000, 1, 0), (0, 0, 0, 1), (12, 0x00000001, 5, 9)]
@@ -198,6 +244,10 @@ def _script():
     for T, tag in ((f32, "f"), (f64, "d")):
         for _, maxiter, budget, sums in _spec_scripts(T):
             lines.append("spec %s %d %s %d %s" % (tag, maxiter, _hex(budget), len(sums), " ".join(_hex(s) for s in sums)))
+    for tag in ("f", "d"):
+        for budget in FIRST_BUDGETS:
+            for _, sums in NONFINITE_CHUNKS:
+                lines.append("first %s %s %d %s" % (tag, _hex(budget), len(sums), " ".join(_hex(s) for s in sums)))
     lines += ["words %d %d %d %d" % w for w in WORDS]
     return "\n".join(lines) + "\n"
 
@@ -243,6 +293,16 @@ def test_next_tile_chunk_equals_its_python_twin(printed):
     assert want[:9] == [64, 64, 8, 8, 64, 64, 24, 8, 64]
     assert want[12:20] == [8, 8, 64, 64, 64, 64, 64, 64]
     assert set(want[20:]) >= {8, 64} and len(set(want[20:])) > 10     # the seeded rows spread over the range
+    # non-finite sums: the twins agree (asserted above, row for row), stay in [1, 64], and a chunk with a NaN anywhere --
+    # in front, where Python's max() alone keeps it, or behind, where std::max alone never takes it -- is followed by a
+    # full one: no stop is coming
+    nf_rows = _tile_rows_nonfinite()
+    nf_got = got[len(rows) - len(nf_rows):]
+    assert rows[len(rows) - len(nf_rows):] == nf_rows and all(1 <= v <= CHUNK_MAX for v in got)
+    for (budget, sums), v in zip(nf_rows, nf_got):
+        if any(s != s for s in sums):
+            assert v == CHUNK_MAX, (budget, sums, v)
+    assert {8, 64} <= set(nf_got)                                      # (+Inf then finite: a steep decay, short chunks)
 
 
 @pytest.mark.parametrize("T,tag", [(f32, "f"), (f64, "d")])
@@ -252,7 +312,29 @@ def test_next_stop_chunk_equals_its_port(printed, T, tag):
     got = [int(l.split()[1]) for l in (lines[:len(rows)] if T is f32 else lines[len(rows):])]
     want = [_next_stop_chunk(first, last, budget, c, it, CHUNK_MAX) for first, last, budget, c, it in rows]
     assert len(got) == len(want) and got == want
-    assert set(want) >= {1, 2, 64} and len(set(want)) > 8 and min(want) >= 1
+    assert set(want) >= {1, 2, 64} and len(set(want)) > 8 and min(want) >= 1 and max(want) <= CHUNK_MAX
+    nf_rows = _chunk_rows_nonfinite(T)
+    for (first, last, budget, c, it), v in zip(nf_rows, got[len(rows) - len(nf_rows):]):
+        assert 1 <= v <= CHUNK_MAX
+        if last != last:
+            assert v == 1, (first, last, budget, c, it)              # a NaN last sum: the reference's own cadence
+    assert len(nf_rows) > 100
+
+
+@pytest.mark.parametrize("tag", ["f", "d"])
+def test_first_stop_on_nonfinite_sums(printed, tag):
+    """ista.py:93: NaN <= budget is False and +Inf <= budget is False for every finite budget -- no stop in a chunk of
+    such sums; a finite sum among them stops like any other"""
+    lines = [int(l.split()[1]) for l in _section(printed, "first")]
+    per = len(FIRST_BUDGETS) * len(NONFINITE_CHUNKS)
+    assert len(lines) == 2 * per
+    got = lines[:per] if tag == "f" else lines[per:]
+    want = [next((i for i, v in enumerate(sums) if v <= budget), -1) for budget in FIRST_BUDGETS for _, sums in NONFINITE_CHUNKS]
+    assert got == want
+    for (budget, (name, sums)), v in zip(((b, ns) for b in FIRST_BUDGETS for ns in NONFINITE_CHUNKS), got):
+        finite = [i for i, s in enumerate(sums) if s == s and s != INF]
+        assert v == (finite[0] if finite and budget == 1e30 else -1), (budget, name)     # (every finite sum is > 1)
+    assert any(v > 0 for v in got) and got.count(-1) > len(got) // 2
 
 
 def _spec_logs(printed):
@@ -296,6 +378,16 @@ def test_speculate_stop_rule_event_for_event(printed, T):
             seen.add("stop at a chunk's end")
         else:
             seen.add("no stop")
+        if name.startswith("nonfinite"):
+            # exactly maxiter iterations, one `iterate` each (nothing replayed), and the last sum as it came
+            assert ref < 0 and it == maxiter and sum(l.startswith("iterate") for l in got) == maxiter, name
+            assert "restore" not in got, name
+            if sums[maxiter - 1] != sums[maxiter - 1]:
+                assert np.isnan(T(sums[maxiter - 1])) and last == _bits(T(np.nan)), name
+            chunks = [int(l.split()[1]) for l in got if l.startswith("read")]
+            assert all(1 <= ch <= CHUNK_MAX for ch in chunks) and sum(chunks) == maxiter, name
+            if all(v != v for v in sums[:maxiter]):
+                assert chunks == [1] * maxiter, name                   # one host round trip per iteration: slow, bounded
     assert seen == {"replay", "stop at a chunk's end", "no stop"}
     by_name = {s[0]: l for s, l in zip(scripts, logs)}
     assert by_name["sum equal to the budget stops"][-1].split()[1] == "10"
