@@ -44,6 +44,7 @@
  *     lasso_conv_gpsr_solve (conv_transpose2d / conv2d as the operator, contiguous NCHW tensors); both LASSO_F32 only.
  *   - the orthant-wise Newton solver is lasso_own_solve: LASSO_F32, any n, d, any pitch, k <= 4096.
  *   - the iterated-ridge solver is lasso_iter_ridge_solve: LASSO_F32, any n, d, any pitch, k <= 1024.
+ *   - the Split Bregman solver is lasso_split_bregman_solve: LASSO_F32, any n, d, any pitch, k <= 4096.
  */
 #ifndef LASSO_HIP_H_
 #define LASSO_HIP_H_
@@ -962,6 +963,48 @@ int lasso_iter_ridge_rows(const void* g_dev, int64_t ldg, const void* rhs_dev, i
                           int64_t ldz, void* z_sol_dev, int64_t ldzs, int64_t n, int64_t k, int dtype, double alpha,
                           double tikhonov, double eps, int64_t* bad_row_out, int32_t* bad_minor_out,
                           int32_t* support_max_out, void* workspace_dev, size_t workspace_bytes, void* stream);
+
+/* ---- Split Bregman: replaces split_bregman(), lasso/linear/solvers/split_bregman.py:5-86 ----
+ * The reference's A is w_dev [d][k], its y is x_dev [n][d], its x0 is x0_dev [n][k] (nullable: zeros) and its x is
+ * z_out_dev [n][k] (csrc/split_bregman.hip).  Once per solve Hinv = (W^T W / alpha + lambd I)^-1
+ * (lasso_gram_accumulate_f64 + lasso_ridge_solve_f64 on W in double, rounded once to fp32) and Aty = (x W) / alpha; B = D = 0.
+ * An outer iteration is niter_inner launches of one product X = (Aty + lambd (D - B)) Hinv^T with
+ * D = softshrink(X + B, 1 / lambd) in its epilogue, the last of them also B += tau (X - D) and the partials of
+ * update = |X - Xold|_F.  The loop ends at the top of an iteration once update <= tol (compared as floats; update starts
+ * at +inf, a NaN never ends it) or after maxiter iterations.  Every sum is folded in double in a fixed order: two solves
+ * of the same arguments give the same bits.  z_out is the linear solve's X, not the shrunk D.
+ *   options : maxiter >= 1, niter_inner >= 1, lambd > 0, tol (negative: never stop), tau; bit 0 of reserved forces
+ *             128 x 128 GEMM blocks (tests), every other bit must be 0.
+ *   result  : n_iter (outer iterations executed), itn (the reference's return value: the index of the iteration at whose
+ *             top the stop fired, maxiter - 1 if it never did), stopped, cholesky_info (0, or 1 + the index of the first
+ *             pivot of W^T W / alpha + lambd I that is not positive: then LASSO_ERR_BAD_ARG and z_out is not written), and
+ *             -- trace non-NULL -- host arrays of the caller: per executed iteration (capacity) update and, where cost is
+ *             non-NULL, cost = 0.5 |X W^T - x|^2 + alpha |X|_1 (the cost product runs only then).
+ * Refusals before any HIP call: null pointers (x0_dev excepted), n < 0, d or k < 1, a leading dimension below the row
+ * length, alpha <= 0, lambd <= 0, maxiter < 1, niter_inner < 1, an undefined bit of reserved or a NaN among alpha,
+ * lambd, tol, tau are LASSO_ERR_BAD_ARG; a dtype other than LASSO_F32 and k > 4096 LASSO_ERR_UNSUPPORTED (the workspace
+ * query returns 0); a short workspace LASSO_ERR_WORKSPACE.  n = 0 writes nothing.  x0_dev is only read; z_out_dev may not
+ * alias an input.  The call blocks; the host reads the device once per outer iteration (the update, and with the first
+ * one the pivots' verdict), and with tol < 0 only once per 1024 outer iterations and at the end. */
+typedef struct lasso_split_bregman_options {
+  int32_t maxiter, niter_inner, reserved, pad_;
+  double lambd, tol, tau;
+} lasso_split_bregman_options;
+typedef struct lasso_split_bregman_trace {
+  int32_t capacity, pad_;                 /* iterations the arrays below hold */
+  double* update;                         /* nullable */
+  double* cost;                           /* nullable: NULL skips the cost product */
+} lasso_split_bregman_trace;
+typedef struct lasso_split_bregman_result {
+  int32_t n_iter, itn, stopped, cholesky_info;
+  lasso_split_bregman_trace* trace;       /* nullable */
+} lasso_split_bregman_result;
+size_t lasso_split_bregman_workspace_bytes(int64_t n, int64_t d, int64_t k, int dtype);
+int lasso_split_bregman_solve(const void* x_dev, int64_t ldx, const void* w_dev, int64_t ldw, const void* x0_dev,
+                              int64_t ldx0, void* z_out_dev, int64_t ldz, int64_t n, int64_t d, int64_t k, int dtype,
+                              double alpha, const lasso_split_bregman_options* options,
+                              lasso_split_bregman_result* result, void* workspace_dev, size_t workspace_bytes,
+                              void* stream);
 
 #ifdef __cplusplus
 }

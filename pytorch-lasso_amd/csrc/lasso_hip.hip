@@ -3001,6 +3001,38 @@ int lasso_iter_ridge_rows(const void* g_dev, int64_t ldg, const void* rhs_dev, i
                           static_cast<hipStream_t>(stream));
 }
 
+// ---- Split Bregman: split_bregman.py:5-86 (csrc/split_bregman.hip) ---------------------------
+size_t lasso_split_bregman_workspace_bytes(int64_t n, int64_t d, int64_t k, int dtype) {
+  if (dtype != LASSO_F32 || n < 0 || d <= 0 || k <= 0 || k > 4096 || n > INT32_MAX || d > INT32_MAX) return 0;
+  return split_bregman::workspace_bytes(n, d, k);
+}
+
+int lasso_split_bregman_solve(const void* x_dev, int64_t ldx, const void* w_dev, int64_t ldw, const void* x0_dev, int64_t ldx0,
+                              void* z_out_dev, int64_t ldz, int64_t n, int64_t d, int64_t k, int dtype, double alpha,
+                              const lasso_split_bregman_options* o, lasso_split_bregman_result* res, void* workspace_dev,
+                              size_t workspace_bytes, void* stream) {
+  if (dtype != LASSO_F32) return fail(LASSO_ERR_UNSUPPORTED, "Split Bregman: dtype %d (fp32 tensors only)", dtype);
+  if (!o || !res) return fail(LASSO_ERR_BAD_ARG, "null options / result");
+  if (n < 0 || d <= 0 || k <= 0 || n > INT32_MAX || d > INT32_MAX || k > INT32_MAX)
+    return fail(LASSO_ERR_BAD_ARG, "bad shape");
+  if (k > 4096) return fail(LASSO_ERR_UNSUPPORTED, "Split Bregman: k=%lld > 4096", (long long)k);
+  if (!(alpha > 0.0) || !(o->lambd > 0.0)) return fail(LASSO_ERR_BAD_ARG, "alpha > 0 and lambd > 0 are required");
+  if (o->tol != o->tol || o->tau != o->tau) return fail(LASSO_ERR_BAD_ARG, "tol or tau is not a number");
+  if (o->maxiter < 1 || o->niter_inner < 1) return fail(LASSO_ERR_BAD_ARG, "maxiter >= 1 and niter_inner >= 1 are required");
+  if (o->reserved & ~1) return fail(LASSO_ERR_BAD_ARG, "Split Bregman: only bit 0 of reserved is defined");
+  if (const lasso_split_bregman_trace* t = res->trace) {
+    if (t->capacity < 0) return fail(LASSO_ERR_BAD_ARG, "trace with a negative capacity");
+  }
+  res->n_iter = res->itn = res->stopped = res->cholesky_info = 0;
+  if (n == 0) return LASSO_OK;
+  if (!x_dev || !w_dev || !z_out_dev || !workspace_dev) return fail(LASSO_ERR_BAD_ARG, "null pointer");
+  if (ldx < d || ldw < k || ldz < k || (x0_dev && ldx0 < k)) return fail(LASSO_ERR_BAD_ARG, "leading dimension too small");
+  if (workspace_bytes < lasso_split_bregman_workspace_bytes(n, d, k, dtype))
+    return fail(LASSO_ERR_WORKSPACE, "need %zu bytes", lasso_split_bregman_workspace_bytes(n, d, k, dtype));
+  return split_bregman::solve((const float*)x_dev, ldx, (const float*)w_dev, ldw, (const float*)x0_dev, ldx0,
+                              (float*)z_out_dev, ldz, n, d, k, alpha, *o, res, workspace_dev, static_cast<hipStream_t>(stream));
+}
+
 // ---- unconstrained M-step: update_dict_ridge, dict_learning.py:106-123 ---------------------
 size_t lasso_ridge_workspace_bytes(int64_t d, int64_t k) {
   if (d <= 0 || k <= 0 || k > 4096) return 0;

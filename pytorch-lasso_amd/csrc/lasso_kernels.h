@@ -16,6 +16,8 @@ struct lasso_own_options;
 struct lasso_own_result;
 struct lasso_iter_ridge_options;
 struct lasso_iter_ridge_result;
+struct lasso_split_bregman_options;
+struct lasso_split_bregman_result;
 
 namespace lasso {
 
@@ -582,5 +584,13 @@ int rows(const float* g, int64_t ldg, const float* rhs, int64_t ldr, const float
          int64_t n, int64_t k, double alpha, double tikhonov, double eps, int64_t* bad_row, int32_t* bad_minor,
          int32_t* support_max, void* workspace, hipStream_t st);
 }  // namespace iter_ridge
+
+// Split Bregman (split_bregman.hip): the driver behind lasso_split_bregman_solve; returns a lasso_status
+namespace split_bregman {
+size_t workspace_bytes(int64_t n, int64_t d, int64_t k);
+int solve(const float* y, int64_t ldy, const float* w, int64_t ldw, const float* x0, int64_t ldx0, float* xout, int64_t ldx,
+          int64_t n, int64_t d, int64_t k, double alpha, const lasso_split_bregman_options& o,
+          lasso_split_bregman_result* res, void* workspace, hipStream_t st);
+}  // namespace split_bregman
 
 }  // namespace lasso

@@ -110,6 +110,24 @@ class IterRidgeResult(C.Structure):
                 ('trace', C.POINTER(IterRidgeTrace))]
 
 
+class SplitBregmanOptions(C.Structure):
+    """lasso_split_bregman_options"""
+    _fields_ = [(name, C.c_int32) for name in ('maxiter', 'niter_inner', 'reserved', 'pad_')] + \
+               [(name, C.c_double) for name in ('lambd', 'tol', 'tau')]
+
+
+class SplitBregmanTrace(C.Structure):
+    """lasso_split_bregman_trace: host arrays of the caller"""
+    _fields_ = [('capacity', C.c_int32), ('pad_', C.c_int32), ('update', C.POINTER(C.c_double)),
+                ('cost', C.POINTER(C.c_double))]
+
+
+class SplitBregmanResult(C.Structure):
+    """lasso_split_bregman_result"""
+    _fields_ = [('n_iter', C.c_int32), ('itn', C.c_int32), ('stopped', C.c_int32), ('cholesky_info', C.c_int32),
+                ('trace', C.POINTER(SplitBregmanTrace))]
+
+
 # int (*lasso_allreduce_fn)(void* ctx, double* sums, int count)   (include/lasso_hip.h)
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_double), C.c_int)
 
@@ -343,6 +361,11 @@ def _declare(lib):
     lib.lasso_iter_ridge_rows.restype = i32
     lib.lasso_iter_ridge_rows.argtypes = [vp, i64, vp, i64, vp, i64, vp, i64, i64, i64, i32, dbl, dbl, dbl,
                                           C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_int32), vp, sz, vp]
+    lib.lasso_split_bregman_workspace_bytes.restype = sz
+    lib.lasso_split_bregman_workspace_bytes.argtypes = [i64, i64, i64, i32]
+    lib.lasso_split_bregman_solve.restype = i32
+    lib.lasso_split_bregman_solve.argtypes = [vp, i64, vp, i64, vp, i64, vp, i64, i64, i64, i64, i32, dbl,
+                                              C.POINTER(SplitBregmanOptions), C.POINTER(SplitBregmanResult), vp, sz, vp]
     lib.lasso_cd_solve.restype = i32
     lib.lasso_cd_solve.argtypes = [vp, i64, vp, i64, vp, i64, vp, i64, i64, i64, i64, i32, dbl, i32,
                                    dbl, pi32, pi32, vp, sz, vp]
