@@ -44,6 +44,7 @@
  *     lasso_conv_gpsr_solve (conv_transpose2d / conv2d as the operator, contiguous NCHW tensors); both LASSO_F32 only.
  *   - the orthant-wise Newton solver is lasso_own_solve: LASSO_F32, any n, d, any pitch, k <= 4096.
  *   - the iterated-ridge solver is lasso_iter_ridge_solve: LASSO_F32, any n, d, any pitch, k <= 1024.
+ *   - the interior-point solver is lasso_interior_point_solve: LASSO_F32, any n, any pitch, d <= 256, k <= 4096.
  *   - the Split Bregman solver is lasso_split_bregman_solve: LASSO_F32, any n, d, any pitch, k <= 4096.
  */
 #ifndef LASSO_HIP_H_
@@ -1004,6 +1005,56 @@ int lasso_split_bregman_solve(const void* x_dev, int64_t ldx, const void* w_dev,
                               int64_t ldx0, void* z_out_dev, int64_t ldz, int64_t n, int64_t d, int64_t k, int dtype,
                               double alpha, const lasso_split_bregman_options* options,
                               lasso_split_bregman_result* result, void* workspace_dev, size_t workspace_bytes,
+                              void* stream);
+
+/* ---- interior point: replaces interior_point(), lasso/linear/solvers/interior_point.py:93-225 ----
+ * min_z 0.5 |z W^T - x|^2 + alpha |z|_1 over the whole batch by the primal-dual log-barrier method on the split
+ * z = z+ - z-, z+, z- >= 0 (csrc/interior_point.hip).  The start is the reference's: z+- = relu(+-z0) + 0.1,
+ * lambda = alpha y / omega with y = sign(z0) W^T and omega = 1.1 max_j |y W|_j per row, s+- = alpha -+ lambda W; it must
+ * be interior (z > 0, s > 0, -alpha < lambda W < alpha everywhere), otherwise the solve returns LASSO_ERR_BAD_ARG with
+ * status LASSO_INTERIOR_POINT_BAD_START and z_out is not written (an all-zero row of z0 gives omega = 0 and a NaN
+ * lambda).  Per iteration: the KKT residuals, per row the d x d system (I + W diag(c) W^T) dlambda = rhs with
+ * c = z+ / s+ + z- / s- (1 / s is 0 where |s| < eps) by a blocked Cholesky in LDS, the directions, damped steps
+ * 0.99 min(1, smallest ratio), mu *= 1 - min(beta_z, beta_s, 0.99), and z, s clamped at 0.  The solve stops once the
+ * means over rows of the three ratios prim_feas, dual_feas and gap are all < tol, or after maxiter iterations; a NaN
+ * mean never stops it, and with tol <= 0 the host reads nothing between the start's flag and the end.  A pivot that is
+ * not positive is not repaired: that row's codes are NaN.  Every sum is folded in double in a fixed order: two solves
+ * of the same arguments give the same bits.
+ *   options : maxiter >= 0, barrier_init, tol, eps >= 0, reserved = 0.
+ *   result  : n_iter, status, obj0 = alpha sum z + 0.5 sum lambda^2 of the start, and -- trace non-NULL -- host arrays
+ *             of the caller: per iteration (capacity) that objective and the three means.
+ * lasso_interior_point_rows is the per-row Newton system on its own: y [n][d] with (I + W diag(c_i) W^T) y_i = b_i from
+ * W [d][k], c [n][k] >= 0 and b [n][d].  y may alias b.  It needs no workspace.
+ * Refusals before any HIP call: null pointers, n < 0, d or k < 1, a leading dimension below the row length, alpha < 0
+ * or NaN, maxiter < 0, eps < 0, a NaN option or reserved != 0 are LASSO_ERR_BAD_ARG; a dtype other than LASSO_F32,
+ * d > 256 and k > 4096 LASSO_ERR_UNSUPPORTED (the workspace query returns 0); a short workspace LASSO_ERR_WORKSPACE.
+ * n = 0 writes nothing.  The workspace grows linearly in n: the state z, s [n][2k], lambda [n][d], five [n][k] and four
+ * [n][d] temporaries, 64 bytes per row of ratios; there is no n d^2 term.  The calls block. */
+typedef struct lasso_interior_point_options {
+  int32_t maxiter, pad_;
+  double barrier_init, tol, eps;
+  int64_t reserved;                       /* must be 0 */
+} lasso_interior_point_options;
+typedef struct lasso_interior_point_trace {
+  int32_t capacity, pad_;                 /* iterations the arrays below hold */
+  double* obj; double* prim_feas; double* dual_feas; double* gap;
+} lasso_interior_point_trace;
+#define LASSO_INTERIOR_POINT_CONVERGED 0  /* the three means < tol */
+#define LASSO_INTERIOR_POINT_MAXITER 1
+#define LASSO_INTERIOR_POINT_BAD_START 2  /* the start is not interior */
+typedef struct lasso_interior_point_result {
+  int32_t n_iter, status;
+  double obj0;
+  lasso_interior_point_trace* trace;      /* nullable */
+} lasso_interior_point_result;
+size_t lasso_interior_point_workspace_bytes(int64_t n, int64_t d, int64_t k, int dtype);
+int lasso_interior_point_solve(const void* x_dev, int64_t ldx, const void* w_dev, int64_t ldw, const void* z0_dev,
+                               int64_t ldz0, void* z_out_dev, int64_t ldz, int64_t n, int64_t d, int64_t k, int dtype,
+                               double alpha, const lasso_interior_point_options* options,
+                               lasso_interior_point_result* result, void* workspace_dev, size_t workspace_bytes,
+                               void* stream);
+int lasso_interior_point_rows(const void* w_dev, int64_t ldw, const void* c_dev, int64_t ldc, const void* b_dev,
+                              int64_t ldb, void* y_dev, int64_t ldy, int64_t n, int64_t d, int64_t k, int dtype,
                               void* stream);
 
 #ifdef __cplusplus

@@ -3033,6 +3033,55 @@ int lasso_split_bregman_solve(const void* x_dev, int64_t ldx, const void* w_dev,
                               (float*)z_out_dev, ldz, n, d, k, alpha, *o, res, workspace_dev, static_cast<hipStream_t>(stream));
 }
 
+// ---- interior point: interior_point.py:93-225 (csrc/interior_point.hip) ----------------------
+size_t lasso_interior_point_workspace_bytes(int64_t n, int64_t d, int64_t k, int dtype) {
+  if (dtype != LASSO_F32 || n < 0 || d <= 0 || k <= 0 || d > 256 || k > 4096 || n > INT32_MAX) return 0;
+  return interior_point::workspace_bytes(n, d, k);
+}
+
+int lasso_interior_point_solve(const void* x_dev, int64_t ldx, const void* w_dev, int64_t ldw, const void* z0_dev, int64_t ldz0,
+                               void* z_out_dev, int64_t ldz, int64_t n, int64_t d, int64_t k, int dtype, double alpha,
+                               const lasso_interior_point_options* o, lasso_interior_point_result* res, void* workspace_dev,
+                               size_t workspace_bytes, void* stream) {
+  if (dtype != LASSO_F32) return fail(LASSO_ERR_UNSUPPORTED, "interior point: dtype %d (fp32 tensors only)", dtype);
+  if (!o || !res) return fail(LASSO_ERR_BAD_ARG, "null options / result");
+  if (n < 0 || d <= 0 || k <= 0 || n > INT32_MAX || d > INT32_MAX || k > INT32_MAX)
+    return fail(LASSO_ERR_BAD_ARG, "bad shape");
+  if (d > 256) return fail(LASSO_ERR_UNSUPPORTED, "interior point: d=%lld > 256", (long long)d);
+  if (k > 4096) return fail(LASSO_ERR_UNSUPPORTED, "interior point: k=%lld > 4096", (long long)k);
+  if (!(alpha >= 0.0)) return fail(LASSO_ERR_BAD_ARG, "alpha < 0");
+  if (o->reserved != 0) return fail(LASSO_ERR_BAD_ARG, "interior point: reserved must be 0");
+  if (o->maxiter < 0 || !(o->eps >= 0.0) || o->tol != o->tol || o->barrier_init != o->barrier_init)
+    return fail(LASSO_ERR_BAD_ARG, "maxiter >= 0, eps >= 0 and numbers for tol and barrier_init are required");
+  if (const lasso_interior_point_trace* t = res->trace) {
+    if (t->capacity < 0 || (t->capacity > 0 && (!t->obj || !t->prim_feas || !t->dual_feas || !t->gap)))
+      return fail(LASSO_ERR_BAD_ARG, "trace with a null array");
+  }
+  res->n_iter = 0;
+  res->status = LASSO_INTERIOR_POINT_MAXITER;
+  res->obj0 = 0.0;
+  if (n == 0) return LASSO_OK;
+  if (!x_dev || !w_dev || !z0_dev || !z_out_dev || !workspace_dev) return fail(LASSO_ERR_BAD_ARG, "null pointer");
+  if (ldx < d || ldw < k || ldz < k || ldz0 < k) return fail(LASSO_ERR_BAD_ARG, "leading dimension too small");
+  if (workspace_bytes < lasso_interior_point_workspace_bytes(n, d, k, dtype))
+    return fail(LASSO_ERR_WORKSPACE, "need %zu bytes", lasso_interior_point_workspace_bytes(n, d, k, dtype));
+  return interior_point::solve((const float*)x_dev, ldx, (const float*)w_dev, ldw, (const float*)z0_dev, ldz0, (float*)z_out_dev,
+                               ldz, n, d, k, alpha, *o, res, workspace_dev, static_cast<hipStream_t>(stream));
+}
+
+int lasso_interior_point_rows(const void* w_dev, int64_t ldw, const void* c_dev, int64_t ldc, const void* b_dev, int64_t ldb,
+                              void* y_dev, int64_t ldy, int64_t n, int64_t d, int64_t k, int dtype, void* stream) {
+  if (dtype != LASSO_F32) return fail(LASSO_ERR_UNSUPPORTED, "interior point: dtype %d (fp32 tensors only)", dtype);
+  if (n < 0 || d <= 0 || k <= 0 || n > INT32_MAX || d > INT32_MAX || k > INT32_MAX) return fail(LASSO_ERR_BAD_ARG, "bad shape");
+  if (d > 256) return fail(LASSO_ERR_UNSUPPORTED, "interior point: d=%lld > 256", (long long)d);
+  if (k > 4096) return fail(LASSO_ERR_UNSUPPORTED, "interior point: k=%lld > 4096", (long long)k);
+  if (n == 0) return LASSO_OK;
+  if (!w_dev || !c_dev || !b_dev || !y_dev) return fail(LASSO_ERR_BAD_ARG, "null pointer");
+  if (ldw < k || ldc < k || ldb < d || ldy < d) return fail(LASSO_ERR_BAD_ARG, "leading dimension too small");
+  return interior_point::rows((const float*)w_dev, ldw, (const float*)c_dev, ldc, (const float*)b_dev, ldb, (float*)y_dev, ldy,
+                              n, d, k, static_cast<hipStream_t>(stream));
+}
+
 // ---- unconstrained M-step: update_dict_ridge, dict_learning.py:106-123 ---------------------
 size_t lasso_ridge_workspace_bytes(int64_t d, int64_t k) {
   if (d <= 0 || k <= 0 || k > 4096) return 0;

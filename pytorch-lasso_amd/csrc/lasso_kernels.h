@@ -16,6 +16,8 @@ struct lasso_own_options;
 struct lasso_own_result;
 struct lasso_iter_ridge_options;
 struct lasso_iter_ridge_result;
+struct lasso_interior_point_options;
+struct lasso_interior_point_result;
 struct lasso_split_bregman_options;
 struct lasso_split_bregman_result;
 
@@ -592,5 +594,16 @@ int solve(const float* y, int64_t ldy, const float* w, int64_t ldw, const float*
           int64_t n, int64_t d, int64_t k, double alpha, const lasso_split_bregman_options& o,
           lasso_split_bregman_result* res, void* workspace, hipStream_t st);
 }  // namespace split_bregman
+
+// interior point (interior_point.hip): the drivers behind lasso_interior_point_solve / lasso_interior_point_rows; return a
+// lasso_status
+namespace interior_point {
+size_t workspace_bytes(int64_t n, int64_t d, int64_t k);
+int solve(const float* x, int64_t ldx, const float* w, int64_t ldw, const float* z0, int64_t ldz0, float* zout, int64_t ldz,
+          int64_t n, int64_t d, int64_t k, double alpha, const lasso_interior_point_options& o,
+          lasso_interior_point_result* res, void* workspace, hipStream_t st);
+int rows(const float* w, int64_t ldw, const float* c, int64_t ldc, const float* b, int64_t ldb, float* y, int64_t ldy, int64_t n,
+         int64_t d, int64_t k, hipStream_t st);
+}  // namespace interior_point
 
 }  // namespace lasso

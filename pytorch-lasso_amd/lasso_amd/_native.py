@@ -30,6 +30,7 @@ GPSR_DEBIAS_NO_NONZEROS, GPSR_DEBIAS_TOO_MANY = 8, 16
 OWN_BRENT, OWN_BACKTRACK, OWN_NONE = 0, 1, 2
 OWN_LS_NOT_CONVERGED, OWN_NONFINITE = 1, 2
 ITER_RIDGE_CONVERGED, ITER_RIDGE_NAN, ITER_RIDGE_MAXITER = 0, 1, 2
+INTERIOR_POINT_CONVERGED, INTERIOR_POINT_MAXITER, INTERIOR_POINT_BAD_START = 0, 1, 2
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = None
@@ -108,6 +109,25 @@ class IterRidgeResult(C.Structure):
     _fields_ = [('n_iter', C.c_int32), ('status', C.c_int32), ('f0', C.c_double), ('f_final', C.c_double),
                 ('bad_row', C.c_int64), ('bad_minor', C.c_int32), ('pad_', C.c_int32),
                 ('trace', C.POINTER(IterRidgeTrace))]
+
+
+class InteriorPointOptions(C.Structure):
+    """lasso_interior_point_options"""
+    _fields_ = [('maxiter', C.c_int32), ('pad_', C.c_int32), ('barrier_init', C.c_double), ('tol', C.c_double),
+                ('eps', C.c_double), ('reserved', C.c_int64)]
+
+
+class InteriorPointTrace(C.Structure):
+    """lasso_interior_point_trace: host arrays of the caller"""
+    _pd = C.POINTER(C.c_double)
+    _fields_ = [('capacity', C.c_int32), ('pad_', C.c_int32), ('obj', _pd), ('prim_feas', _pd), ('dual_feas', _pd),
+                ('gap', _pd)]
+
+
+class InteriorPointResult(C.Structure):
+    """lasso_interior_point_result"""
+    _fields_ = [('n_iter', C.c_int32), ('status', C.c_int32), ('obj0', C.c_double),
+                ('trace', C.POINTER(InteriorPointTrace))]
 
 
 class SplitBregmanOptions(C.Structure):
@@ -366,6 +386,13 @@ def _declare(lib):
     lib.lasso_split_bregman_solve.restype = i32
     lib.lasso_split_bregman_solve.argtypes = [vp, i64, vp, i64, vp, i64, vp, i64, i64, i64, i64, i32, dbl,
                                               C.POINTER(SplitBregmanOptions), C.POINTER(SplitBregmanResult), vp, sz, vp]
+    lib.lasso_interior_point_workspace_bytes.restype = sz
+    lib.lasso_interior_point_workspace_bytes.argtypes = [i64, i64, i64, i32]
+    lib.lasso_interior_point_solve.restype = i32
+    lib.lasso_interior_point_solve.argtypes = [vp, i64, vp, i64, vp, i64, vp, i64, i64, i64, i64, i32, dbl,
+                                               C.POINTER(InteriorPointOptions), C.POINTER(InteriorPointResult), vp, sz, vp]
+    lib.lasso_interior_point_rows.restype = i32
+    lib.lasso_interior_point_rows.argtypes = [vp, i64, vp, i64, vp, i64, vp, i64, i64, i64, i64, i32, vp]
     lib.lasso_cd_solve.restype = i32
     lib.lasso_cd_solve.argtypes = [vp, i64, vp, i64, vp, i64, vp, i64, i64, i64, i64, i32, dbl, i32,
                                    dbl, pi32, pi32, vp, sz, vp]
