@@ -237,13 +237,13 @@ const char* conv_form(const ConvGeom& g, int forced_general) {
   int count = 0;
   const int64_t M = (int64_t)g.N * g.Hz * g.Wz;
   if (forced_general || g.N <= 0) return "patches";
-  return implicit_covered(g, device_cus(), gemm_parts((int)M, g.K, 64), &count) ? "implicit" : "patches";
+  return implicit_covered(g, solver::device_cus(), gemm_parts((int)M, g.K, 64), &count) ? "implicit" : "patches";
 }
 
 int conv_solve(const float* x, const float* w, const float* z0, float* zout, const ConvGeom& g, double tau,
                const lasso_gpsr_options& o, lasso_gpsr_result* res, void* workspace, hipStream_t st) {
   const ConvSpace ws = carve(workspace, g);
-  const int cus = device_cus();
+  const int cus = solver::device_cus();
   const int64_t M = (int64_t)g.N * g.Hz * g.Wz;
   const int ckk = g.C * g.kh * g.kw, ldr = (ckk + 3) / 4 * 4;
   // (the GEMM's epilogue addresses a 64-row block with 32-bit offsets: COLSt has pitch M)

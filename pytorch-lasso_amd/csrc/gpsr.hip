@@ -1,7 +1,7 @@
 // GPSR-Basic on the dictionary (the reference's lasso/linear/solvers/gpsr.py with A z = z W^T, AT r = r W): the operator
 // that gpsr_driver.hpp's host loop is instantiated with for lasso_gpsr_solve.  Every [n,k] x [k,d]-class product is ONE
-// launch of the driver's GEMM with the epilogue the loop asks for; the kernels, the control block and the loop itself
-// are in the header and serve the convolutional operator of conv_gpsr.hip as well.
+// launch of solver_common.hpp's GEMM with the epilogue the loop asks for; the epilogues, the decision kernels, the control
+// block and the loop itself are in the driver's header and serve the convolutional operator of conv_gpsr.hip as well.
 #include "gpsr_driver.hpp"
 
 namespace lasso {
@@ -38,7 +38,7 @@ struct LinearOp {
   }
 
   hipError_t write_out(const float* Z, int zero, hipStream_t st) const {
-    hipLaunchKernelGGL(copy_out_kernel, dim3(ew_grid((int64_t)rows * cols)), dim3(256), 0, st, Z, zout, ldz, rows, cols, zero);
+    hipLaunchKernelGGL(copy_out_kernel<>, dim3(ew_grid((int64_t)rows * cols)), dim3(256), 0, st, Z, zout, ldz, rows, cols, zero);
     return hipGetLastError();
   }
 };
@@ -68,7 +68,7 @@ int solve(const float* x, int64_t ldx, const float* w, int64_t ldw, const float*
           void* workspace, hipStream_t st) {
   const int n = (int)n64, d = (int)d64, k = (int)k64;
   const LinearSpace ws = carve(workspace, n, d, k);
-  const int cus = device_cus();
+  const int cus = solver::device_cus();
   if (std::max<int64_t>({(int64_t)d, (int64_t)k, ldx, ldw}) * 64 * 4 >= ((int64_t)1 << 31)) {
     return fail(LASSO_ERR_UNSUPPORTED, "row pitch beyond the 32-bit offsets of a 64-row block");
   }

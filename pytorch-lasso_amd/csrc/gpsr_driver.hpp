@@ -1,49 +1,36 @@
 // GPSR-Basic (Figueiredo, Nowak, Wright 2007; the reference's lasso/linear/solvers/gpsr.py) on the fp32 MFMA GEMM:
 // gradient projection on the split z = u - v, u, v >= 0 of  min 0.5 |y - A z|^2 + tau |z|_1  over the whole batch.
 //
-// This header is the solver without its operator: the GEMM with GPSR's epilogues, the element-wise and one-workgroup
-// decision kernels, the control block, and the host loop solve_with<Op>() (at the end of the file).  The loop's only contact
+// This header is the solver without its operator: GPSR's epilogues, the element-wise and one-workgroup decision
+// kernels, the control block, and the host loop solve_with<Op>() (at the end of the file).  The loop's only contact
 // with the operator A / AT is the Op it is instantiated with: gpsr.hip instantiates it for the dictionary
 // (A z = z W^T), conv_gpsr.hip for the convolution (A z = conv_transpose2d(z, W)).  Everything here sits in an
 // unnamed namespace: each of the two translation units carries its own copy of the kernels.
 //
-// Every [n,k] x [k,d]-class product is the main loop of gemm.hip (gemm_mainloop.hpp) with an epilogue of its own, so no
-// [n,k] / [n,d] intermediate makes a trip through HBM that an epilogue can absorb:
+// Every [n,k] x [k,d]-class product is solver_common.hpp's gemm_kernel (the main loop of gemm.hip) with an epilogue, so
+// no [n,k] / [n,d] intermediate makes a trip through HBM that an epilogue can absorb:
 //   EPI_GRAD   t = rb W - Ay on the accumulators; reads u, v, writes t (gu = t + tau, gv = tau - t: one array gives both)
 //              and c = cu - cv, block partials of <gu,cu>, <gv,cv> and the four infinity norms of the LCP criterion
 //   EPI_SUMSQ  |c W^T|^2: block partials only, the [n,d] product never reaches memory
 //   EPI_RESID  rb+ = z+ W^T stored, block partials of |y - rb+|^2; blockIdx.z = rung of the step-size ladder
-//   EPI_STORE / EPI_RESID0 / EPI_MASK_R / EPI_MASK_AP: Ay, and the two products of the debias CG with the support mask
-// All sums: per-thread, wave butterfly, the four waves, block partial (double) -- then ONE workgroup folds the partials
-// in a fixed order (no float atomics: two solves of the same arguments are bitwise equal).  The scalars that steer the
+//   EPI_MASK_R / EPI_MASK_AP: the two products of the debias CG with the support mask
+//   EPI_STORE / EPI_RESID0: Ay and the debias residual -- solver_common.hpp's StoreEpi and Resid0Epi
+// All sums are block partials that ONE workgroup folds in a fixed order (solver_common.hpp).  The scalars that steer the
 // iteration (lambda, the sufficient-decrease test, the stop criterion) are computed by those one-workgroup kernels with
 // the reference's fp32 operation order and land in a control block that the host reads ONCE per outer iteration: the
 // first trial, its decision, the accept step and the criterion are all enqueued behind the gradient; only a rejected
 // first trial costs another wait, for a ladder of kLadder further step sizes evaluated in one batch.
 #pragma once
-#include <hip/hip_runtime.h>
-#include <math.h>
-#include <stdint.h>
-#include <stdio.h>
-#include <string.h>
-#include <algorithm>
-#include <vector>
-
-#include "../../include/lasso_hip.h"
-#include "lasso_kernels.h"
-#include "host_util.hpp"
-#include "gemm_mainloop.hpp"
+#include "solver_common.hpp"
 
 namespace lasso {
 namespace gpsr {
 namespace {
 
-using gemm_detail::f32x4;
+using namespace solver;
 
 constexpr int kLadder = 4;            // step sizes per batch behind a rejected first trial
 constexpr int kMaxReductions = 100;   // the line search gives up after this many reductions of lambda
-constexpr int kPart = 8;              // doubles per block partial
-constexpr int kEwBlocks = 1024;       // most blocks of an element-wise launch
 
 enum { EPI_STORE = 0, EPI_GRAD, EPI_SUMSQ, EPI_RESID, EPI_RESID0, EPI_MASK_R, EPI_MASK_AP };
 
@@ -64,211 +51,121 @@ struct Epi {
   const float* Ay; const float* U; const float* V;   // GRAD
   float* T; float* Cc;                               // GRAD out (ld = nn)
   const float* Y; int64_t ldy;                       // RESID / RESID0: the data x [m][nn]
-  float* Out; int64_t ldo; int64_t out_stride;       // STORE / RESID / RESID0 / MASK_*: the product (per rung: + z * out_stride)
+  float* Out; int64_t ldo; int64_t out_stride;       // STORE / RESID / RESID0 / MASK_*: the product (RESID per rung: + z * out_stride)
   const float* Mask;                                 // MASK_*: 1 where the code is off the support
   float* P;                                          // MASK_R: -r out; MASK_AP: p in
   int64_t a_stride;                                  // per rung offset of the A operand
-  double* part;                                      // [blocks][kPart]
+  double* part;                                      // [rungs][blocks][kPart]
   float tau;
 };
 
-// sums s[NS] and maxima mx[NM] of a block of 256 threads in a fixed order -> out[NS + NM] by thread 0
-template <int NS, int NM>
-__device__ __forceinline__ void block_fold(double (&s)[NS > 0 ? NS : 1], float (&mx)[NM > 0 ? NM : 1], double* red /* [4][8] */,
-                                           double* out) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+// the epilogue of mode MODE (GRAD, SUMSQ, RESID, MASK_R, MASK_AP) for solver_common.hpp's gemm_kernel
+template <int MODE>
+struct EpiM : Epi {
+  template <int BM, int BN>
+  __device__ __forceinline__ void run(const Tile<BM, BN>& t, f32x4 (&acc)[BM / 32][BN / 32], char* smem) const {
+    constexpr int MI = BM / 32, NJ = BN / 32;
+    const Epi& ep = *this;
+    double s[2] = {0.0, 0.0};
+    float mx[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    float s0 = 0.0f, s1 = 0.0f;
+    const int64_t ldn = t.nn;
 #pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
+    for (int mi = 0; mi < MI; ++mi) {
+      if constexpr (MODE == EPI_GRAD) {
+        const __amdgpu_buffer_rsrc_t ars = t.rsrc(ep.Ay, ldn), urs = t.rsrc(ep.U, ldn), vrs = t.rsrc(ep.V, ldn);
+        const __amdgpu_buffer_rsrc_t trs = t.rsrc(ep.T, ldn), crs = t.rsrc(ep.Cc, ldn);
+        unsigned o[NJ][4];
+        t.offs(mi, ldn, o);
+        float ay[NJ][4], u[NJ][4], v[NJ][4];
 #pragma unroll
-    for (int i = 0; i < NS; ++i) s[i] += __shfl_xor(s[i], off);
+        for (int nj = 0; nj < NJ; ++nj)
 #pragma unroll
-    for (int i = 0; i < NM; ++i) mx[i] = fmaxf(mx[i], __shfl_xor(mx[i], off));
-  }
-  __syncthreads();
-  if (lane == 0) {
-#pragma unroll
-    for (int i = 0; i < NS; ++i) red[w * 8 + i] = s[i];
-#pragma unroll
-    for (int i = 0; i < NM; ++i) red[w * 8 + NS + i] = (double)mx[i];
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-#pragma unroll
-    for (int i = 0; i < NS; ++i) out[i] = (red[i] + red[8 + i]) + (red[16 + i] + red[24 + i]);
-#pragma unroll
-    for (int i = 0; i < NM; ++i) out[NS + i] = fmax(fmax(red[NS + i], red[8 + NS + i]), fmax(red[16 + NS + i], red[24 + NS + i]));
-  }
-}
-
-// C = A B^T on the block (blockIdx.y, blockIdx.x), rung blockIdx.z; A [m][kk], B [nn][kk]
-template <int BM, int BN, bool VEC, bool DMA, int MODE>
-__global__ __launch_bounds__(256, 2) void gpsr_gemm_kernel(const float* __restrict__ A, int64_t lda,
-                                                           const float* __restrict__ B, int64_t ldb, int m, int nn,
-                                                           int kk, Epi ep) {
-  constexpr int MI = BM / 32, NJ = BN / 32;
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int i0 = blockIdx.y * BM, j0 = blockIdx.x * BN;
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const int wr = w >> 1, wc = w & 1;
-  const int l15 = lane & 15, q = lane >> 4;
-  A += (int64_t)blockIdx.z * ep.a_stride;
-  f32x4 acc[MI][NJ] = {};
-  gemm_detail::gemm_nt_accumulate<BM, BN, VEC, DMA>(A, lda, B, ldb, m, nn, kk, i0, j0, smem, acc);
-  // the epilogue's operands through buffer descriptors of the tile's rows, as in gemm.hip: out of range reads 0 and
-  // drops the store
-  const int rows_valid = min(BM, m - i0);
-  auto tile_rsrc = [&](const float* base, int64_t ld) {
-    const int64_t bytes = (int64_t)rows_valid * ld * 4;
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(base + (int64_t)i0 * ld), 0,
-                                             (int)(bytes < 0x7fffffff ? bytes : 0x7fffffff), 0x00020000);
-  };
-  auto tile_off = [&](int rl, int cc, int64_t ld) {
-    unsigned o = (rl < rows_valid && cc < nn) ? (unsigned)(rl * (int)ld + cc) * 4u : 0xfffffff0u;
-    asm volatile("" : "+v"(o));
-    return o;
-  };
-  auto ld32 = [](__amdgpu_buffer_rsrc_t rs, unsigned o) {
-    return __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs, o, 0, 0));
-  };
-  auto st32 = [](float v, __amdgpu_buffer_rsrc_t rs, unsigned o) {
-    __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), rs, o, 0, 0);
-  };
-  double s[2] = {0.0, 0.0};
-  float mx[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-  float s0 = 0.0f, s1 = 0.0f;
-  const int64_t ldn = nn;
-#pragma unroll
-  for (int mi = 0; mi < MI; ++mi) {
-    unsigned o[NJ][4];
-#pragma unroll
-    for (int nj = 0; nj < NJ; ++nj)
-#pragma unroll
-      for (int rg = 0; rg < 4; ++rg)
-        o[nj][rg] = tile_off((BM / 2) * wr + 16 * mi + 4 * q + rg, j0 + (BN / 2) * wc + 16 * nj + l15, ldn);
-    if constexpr (MODE == EPI_GRAD) {
-      const __amdgpu_buffer_rsrc_t ars = tile_rsrc(ep.Ay, ldn), urs = tile_rsrc(ep.U, ldn), vrs = tile_rsrc(ep.V, ldn);
-      const __amdgpu_buffer_rsrc_t trs = tile_rsrc(ep.T, ldn), crs = tile_rsrc(ep.Cc, ldn);
-      float ay[NJ][4], u[NJ][4], v[NJ][4];
-#pragma unroll
-      for (int nj = 0; nj < NJ; ++nj)
-#pragma unroll
-        for (int rg = 0; rg < 4; ++rg) {
-          ay[nj][rg] = ld32(ars, o[nj][rg]);
-          u[nj][rg] = ld32(urs, o[nj][rg]);
-          v[nj][rg] = ld32(vrs, o[nj][rg]);
-        }
-#pragma unroll
-      for (int nj = 0; nj < NJ; ++nj)
-#pragma unroll
-        for (int rg = 0; rg < 4; ++rg) {
-          const bool in = o[nj][rg] != 0xfffffff0u;
-          const float t = __fsub_rn(acc[mi][nj][rg], ay[nj][rg]);
-          const float gu = __fadd_rn(t, ep.tau), gv = __fadd_rn(-t, ep.tau);
-          const float uu = u[nj][rg], vv = v[nj][rg];
-          const float cu = (uu <= 0.0f && gu >= 0.0f) ? 0.0f : gu;
-          const float cv = (vv <= 0.0f && gv >= 0.0f) ? 0.0f : gv;
-          if (in) {
-            s0 += __fmul_rn(gu, cu);
-            s1 += __fmul_rn(gv, cv);
-            mx[0] = fmaxf(mx[0], fabsf(fminf(gu, uu)));
-            mx[1] = fmaxf(mx[1], fabsf(fminf(gv, vv)));
-            mx[2] = fmaxf(mx[2], fabsf(uu));
-            mx[3] = fmaxf(mx[3], fabsf(vv));
+          for (int rg = 0; rg < 4; ++rg) {
+            ay[nj][rg] = t.ld32(ars, o[nj][rg]);
+            u[nj][rg] = t.ld32(urs, o[nj][rg]);
+            v[nj][rg] = t.ld32(vrs, o[nj][rg]);
           }
-          st32(t, trs, o[nj][rg]);
-          st32(__fsub_rn(cu, cv), crs, o[nj][rg]);
-        }
-    } else if constexpr (MODE == EPI_SUMSQ) {
 #pragma unroll
-      for (int nj = 0; nj < NJ; ++nj)
+        for (int nj = 0; nj < NJ; ++nj)
 #pragma unroll
-        for (int rg = 0; rg < 4; ++rg)       // (the LDS-DMA form clamps rows beyond the operand instead of zeroing them)
-          if (o[nj][rg] != 0xfffffff0u) s0 += __fmul_rn(acc[mi][nj][rg], acc[mi][nj][rg]);
-    } else if constexpr (MODE == EPI_STORE) {
-      const __amdgpu_buffer_rsrc_t ors = tile_rsrc(ep.Out, ep.ldo);
-#pragma unroll
-      for (int nj = 0; nj < NJ; ++nj)
-#pragma unroll
-        for (int rg = 0; rg < 4; ++rg) {
-          const int rl = (BM / 2) * wr + 16 * mi + 4 * q + rg, cc = j0 + (BN / 2) * wc + 16 * nj + l15;
-          st32(acc[mi][nj][rg], ors, tile_off(rl, cc, ep.ldo));
-        }
-    } else if constexpr (MODE == EPI_RESID || MODE == EPI_RESID0) {
-      // RESID: store rb+, sum (y - rb+)^2;  RESID0 (debias): store rb - y, sum of its squares
-      const __amdgpu_buffer_rsrc_t yrs = tile_rsrc(ep.Y, ep.ldy);
-      const __amdgpu_buffer_rsrc_t ors = tile_rsrc(ep.Out + (int64_t)blockIdx.z * ep.out_stride, ep.ldo);
-      float y[NJ][4];
-      unsigned oo[NJ][4];
-#pragma unroll
-      for (int nj = 0; nj < NJ; ++nj)
-#pragma unroll
-        for (int rg = 0; rg < 4; ++rg) {
-          const int rl = (BM / 2) * wr + 16 * mi + 4 * q + rg, cc = j0 + (BN / 2) * wc + 16 * nj + l15;
-          y[nj][rg] = ld32(yrs, tile_off(rl, cc, ep.ldy));
-          oo[nj][rg] = tile_off(rl, cc, ep.ldo);
-        }
-#pragma unroll
-      for (int nj = 0; nj < NJ; ++nj)
-#pragma unroll
-        for (int rg = 0; rg < 4; ++rg) {
-          const float r = MODE == EPI_RESID ? __fsub_rn(y[nj][rg], acc[mi][nj][rg]) : __fsub_rn(acc[mi][nj][rg], y[nj][rg]);
-          if (oo[nj][rg] != 0xfffffff0u) s0 += __fmul_rn(r, r);
-          st32(MODE == EPI_RESID ? acc[mi][nj][rg] : r, ors, oo[nj][rg]);
-        }
-    } else {                                   // EPI_MASK_R, EPI_MASK_AP
-      const __amdgpu_buffer_rsrc_t mrs = tile_rsrc(ep.Mask, ldn), ors = tile_rsrc(ep.Out, ldn), prs = tile_rsrc(ep.P, ldn);
-      float mk[NJ][4], p[NJ][4];
-#pragma unroll
-      for (int nj = 0; nj < NJ; ++nj)
-#pragma unroll
-        for (int rg = 0; rg < 4; ++rg) {
-          mk[nj][rg] = ld32(mrs, o[nj][rg]);
-          p[nj][rg] = MODE == EPI_MASK_AP ? ld32(prs, o[nj][rg]) : 0.0f;
-        }
-#pragma unroll
-      for (int nj = 0; nj < NJ; ++nj)
-#pragma unroll
-        for (int rg = 0; rg < 4; ++rg) {
-          const float val = mk[nj][rg] != 0.0f ? 0.0f : acc[mi][nj][rg];
-          st32(val, ors, o[nj][rg]);
-          const bool in = o[nj][rg] != 0xfffffff0u;
-          if constexpr (MODE == EPI_MASK_R) {
-            st32(-val, prs, o[nj][rg]);
-            if (in) s0 += __fmul_rn(val, val);
-          } else {
-            if (in) s0 += __fmul_rn(p[nj][rg], val);
+          for (int rg = 0; rg < 4; ++rg) {
+            const float tt = __fsub_rn(acc[mi][nj][rg], ay[nj][rg]);
+            const float gu = __fadd_rn(tt, ep.tau), gv = __fadd_rn(-tt, ep.tau);
+            const float uu = u[nj][rg], vv = v[nj][rg];
+            const float cu = (uu <= 0.0f && gu >= 0.0f) ? 0.0f : gu;
+            const float cv = (vv <= 0.0f && gv >= 0.0f) ? 0.0f : gv;
+            if (t.inside(o[nj][rg])) {
+              s0 += __fmul_rn(gu, cu);
+              s1 += __fmul_rn(gv, cv);
+              mx[0] = fmaxf(mx[0], fabsf(fminf(gu, uu)));
+              mx[1] = fmaxf(mx[1], fabsf(fminf(gv, vv)));
+              mx[2] = fmaxf(mx[2], fabsf(uu));
+              mx[3] = fmaxf(mx[3], fabsf(vv));
+            }
+            t.st32(tt, trs, o[nj][rg]);
+            t.st32(__fsub_rn(cu, cv), crs, o[nj][rg]);
           }
-        }
+      } else if constexpr (MODE == EPI_SUMSQ) {
+#pragma unroll
+        for (int nj = 0; nj < NJ; ++nj)
+#pragma unroll
+          for (int rg = 0; rg < 4; ++rg)
+            if (t.inside(t.off(mi, nj, rg, ldn))) s0 += __fmul_rn(acc[mi][nj][rg], acc[mi][nj][rg]);
+      } else if constexpr (MODE == EPI_RESID) {            // store rb+, sum (y - rb+)^2
+        const __amdgpu_buffer_rsrc_t yrs = t.rsrc(ep.Y, ep.ldy);
+        const __amdgpu_buffer_rsrc_t ors = t.rsrc(ep.Out + (int64_t)blockIdx.z * ep.out_stride, ep.ldo);
+        float y[NJ][4];
+        unsigned oo[NJ][4];
+#pragma unroll
+        for (int nj = 0; nj < NJ; ++nj)
+#pragma unroll
+          for (int rg = 0; rg < 4; ++rg) {
+            y[nj][rg] = t.ld32(yrs, t.off(mi, nj, rg, ep.ldy));
+            oo[nj][rg] = t.off(mi, nj, rg, ep.ldo);
+          }
+#pragma unroll
+        for (int nj = 0; nj < NJ; ++nj)
+#pragma unroll
+          for (int rg = 0; rg < 4; ++rg) {
+            const float r = __fsub_rn(y[nj][rg], acc[mi][nj][rg]);
+            if (t.inside(oo[nj][rg])) s0 += __fmul_rn(r, r);
+            t.st32(acc[mi][nj][rg], ors, oo[nj][rg]);
+          }
+      } else {                                   // EPI_MASK_R, EPI_MASK_AP
+        static_assert(MODE == EPI_MASK_R || MODE == EPI_MASK_AP, "STORE and RESID0 are solver_common.hpp's");
+        const __amdgpu_buffer_rsrc_t mrs = t.rsrc(ep.Mask, ldn), ors = t.rsrc(ep.Out, ldn), prs = t.rsrc(ep.P, ldn);
+        unsigned o[NJ][4];
+        t.offs(mi, ldn, o);
+        float mk[NJ][4], p[NJ][4];
+#pragma unroll
+        for (int nj = 0; nj < NJ; ++nj)
+#pragma unroll
+          for (int rg = 0; rg < 4; ++rg) {
+            mk[nj][rg] = t.ld32(mrs, o[nj][rg]);
+            p[nj][rg] = MODE == EPI_MASK_AP ? t.ld32(prs, o[nj][rg]) : 0.0f;
+          }
+#pragma unroll
+        for (int nj = 0; nj < NJ; ++nj)
+#pragma unroll
+          for (int rg = 0; rg < 4; ++rg) {
+            const float val = mk[nj][rg] != 0.0f ? 0.0f : acc[mi][nj][rg];
+            t.st32(val, ors, o[nj][rg]);
+            const bool in = t.inside(o[nj][rg]);
+            if constexpr (MODE == EPI_MASK_R) {
+              t.st32(-val, prs, o[nj][rg]);
+              if (in) s0 += __fmul_rn(val, val);
+            } else {
+              if (in) s0 += __fmul_rn(p[nj][rg], val);
+            }
+          }
+      }
     }
-  }
-  if constexpr (MODE != EPI_STORE) {
     s[0] = (double)s0;
     s[1] = (double)s1;
-    double* const out = ep.part + ((int64_t)(blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x) * kPart;
-    block_fold<2, 4>(s, mx, reinterpret_cast<double*>(smem), out);
+    block_fold<2, 4>(s, mx, reinterpret_cast<double*>(smem), t.partial(ep.part));
   }
-}
-
-// ---- one-workgroup folds of the block partials (fixed order) --------------------------------------------------------
-// out[i] (shared) = sum (i < ns) or max over the blocks' partial i
-__device__ __forceinline__ void fold_partials(const double* __restrict__ part, int nblocks, int ns, int nm, double* red /* [256] */,
-                                              double* out /* [kPart] */) {
-  for (int i = 0; i < ns + nm; ++i) {
-    double a = 0.0;
-    for (int b = threadIdx.x; b < nblocks; b += 256) {
-      const double v = part[(int64_t)b * kPart + i];
-      a = i < ns ? a + v : fmax(a, v);
-    }
-    red[threadIdx.x] = a;
-    __syncthreads();
-    for (int h = 128; h > 0; h >>= 1) {
-      if ((int)threadIdx.x < h) red[threadIdx.x] = i < ns ? red[threadIdx.x] + red[threadIdx.x + h] : fmax(red[threadIdx.x], red[threadIdx.x + h]);
-      __syncthreads();
-    }
-    if (threadIdx.x == 0) out[i] = red[0];
-    __syncthreads();
-  }
-}
+};
 
 // start of a solve / continuation step: f = 0.5 |y - rb|^2 + tau (sum u + sum v); nz of the start
 __global__ __launch_bounds__(256) void start_kernel(const double* __restrict__ part_r, int nb_r, const double* __restrict__ part_uv,
@@ -551,58 +448,18 @@ __global__ __launch_bounds__(256) void cg_dir_kernel(float* __restrict__ P, cons
     P[i] = __fadd_rn(-R[i], __fmul_rn(b, P[i]));
 }
 
-__global__ __launch_bounds__(256) void copy_out_kernel(const float* __restrict__ Z, float* __restrict__ out, int64_t ldo, int n,
-                                                       int k, int zero) {
-  const int64_t total = (int64_t)n * k;
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256)
-    out[(i / k) * ldo + (i % k)] = zero ? 0.0f : Z[i];
-}
-
 // ---- launchers -------------------------------------------------------------------------------------------------------
-int ew_grid(int64_t total) { return (int)std::max<int64_t>(1, std::min<int64_t>(kEwBlocks, (total + 1023) / 1024)); }
-
-int device_cus() {
-  int dev = 0, cus = 0;
-  if (hipGetDevice(&dev) != hipSuccess ||
-      hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1)
-    cus = 1;
-  return cus;
-}
-
-// 128 x 128 blocks while they still give every CU two workgroups, 64 x 64 otherwise (and for a very wide row pitch)
-int block_side(int m, int nn, int64_t ldmax, int cus) {
-  const int64_t blocks = (int64_t)((m + 127) / 128) * ((nn + 127) / 128);
-  return (blocks >= 2 * (int64_t)cus && ldmax * 128 * 4 < ((int64_t)1 << 31)) ? 128 : 64;
-}
-int gemm_parts(int m, int nn, int side) { return ((m + side - 1) / side) * ((nn + side - 1) / side); }
-
-template <int BS, bool VEC, bool DMA, int MODE>
-hipError_t launch_one(const float* A, int64_t lda, const float* B, int64_t ldb, int m, int nn, int kk, const Epi& ep, int rungs,
-                      hipStream_t st) {
-  constexpr int lds = 2 * (BS + BS) * 128;
-  if (lds > 48 * 1024)
-    if (hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(&gpsr_gemm_kernel<BS, BS, VEC, DMA, MODE>), lds);
-        e != hipSuccess)
-      return e;
-  const dim3 grid((nn + BS - 1) / BS, (m + BS - 1) / BS, rungs);
-  hipLaunchKernelGGL((gpsr_gemm_kernel<BS, BS, VEC, DMA, MODE>), grid, dim3(256), lds, st, A, lda, B, ldb, m, nn, kk, ep);
-  return hipGetLastError();
-}
-
+// the product with the epilogue of mode MODE: `rungs` of them in one launch, ep.a_stride apart
 template <int MODE>
 hipError_t launch_gemm(const float* A, int64_t lda, const float* B, int64_t ldb, int m, int nn, int kk, const Epi& ep, int side,
                        int rungs, hipStream_t st) {
-  const bool vec = kk % 4 == 0 && lda % 4 == 0 && ldb % 4 == 0 && ((uintptr_t)A & 15) == 0 && ((uintptr_t)B & 15) == 0 &&
-                   (ep.a_stride % 4) == 0;
-  const bool dma = vec && kk % 32 == 0 && lda * side * 4 < ((int64_t)1 << 31) && ldb * side * 4 < ((int64_t)1 << 31);
-  if (side == 128) {
-    if (dma) return launch_one<128, true, true, MODE>(A, lda, B, ldb, m, nn, kk, ep, rungs, st);
-    if (vec) return launch_one<128, true, false, MODE>(A, lda, B, ldb, m, nn, kk, ep, rungs, st);
-    return launch_one<128, false, false, MODE>(A, lda, B, ldb, m, nn, kk, ep, rungs, st);
-  }
-  if (dma) return launch_one<64, true, true, MODE>(A, lda, B, ldb, m, nn, kk, ep, rungs, st);
-  if (vec) return launch_one<64, true, false, MODE>(A, lda, B, ldb, m, nn, kk, ep, rungs, st);
-  return launch_one<64, false, false, MODE>(A, lda, B, ldb, m, nn, kk, ep, rungs, st);
+  if constexpr (MODE == EPI_STORE)
+    return solver::launch_gemm(A, lda, B, ldb, m, nn, kk, StoreEpi{ep.Out, ep.ldo, ep.a_stride}, side, rungs, st);
+  else if constexpr (MODE == EPI_RESID0)
+    return solver::launch_gemm(A, lda, B, ldb, m, nn, kk, Resid0Epi{ep.Y, ep.ldy, ep.Out, ep.ldo, ep.part, ep.a_stride}, side,
+                               rungs, st);
+  else
+    return solver::launch_gemm(A, lda, B, ldb, m, nn, kk, EpiM<MODE>{ep}, side, rungs, st);
 }
 
 // ---- the operator-independent workspace -------------------------------------------------------------------------------

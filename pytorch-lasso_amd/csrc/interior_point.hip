@@ -20,26 +20,19 @@
 // repaired: its root is NaN and so is that row's result.
 //
 // The four batch products of an iteration (lambda W, (z+ - z-) W^T, the rhs product, dlambda W) are the GEMM of
-// gemm_mainloop.hpp with gpsr_driver.hpp's launch rules.  The element-wise steps are two passes: pre_kernel (residuals,
+// solver_common.hpp with its store epilogue.  The element-wise steps are two passes: pre_kernel (residuals,
 // the generalised inverse, c and the operand of the rhs product) and update_kernel, one workgroup per row (directions,
 // ratio minima, the damped steps, clamps, mu and the row's three ratios).  stat_kernel, one workgroup, folds the rows'
 // ratios in double in a fixed order into the iteration's record: no float atomics, two solves of the same arguments are
 // bitwise equal.  The host reads one record per iteration, and with tol <= 0 (the stop test cannot pass) none at all:
 // the records stay on the device and are fetched in batches for the trace.
-#include "gpsr_driver.hpp"
+#include "solver_common.hpp"
 
 namespace lasso {
 namespace interior_point {
 namespace {
 
-using gemm_detail::f32x4;
-using gpsr::block_fold;
-using gpsr::block_side;
-using gpsr::device_cus;
-using gpsr::ew_grid;
-using gpsr::fold_partials;
-using gpsr::kEwBlocks;
-using gpsr::kPart;
+using namespace solver;
 
 constexpr int kNB = 32;                       // block side of the packed triangle
 constexpr int kRS = 33;                       // row stride of a block in LDS (floats)
@@ -668,14 +661,10 @@ int solve(const float* x, int64_t ldx, const float* w, int64_t ldw, const float*
 
   // [n][d] x W -> [n][k] (on W^T [k][d]) and [n][k] x W^T -> [n][d]
   auto times_w = [&](const float* A, float* out) -> hipError_t {
-    gpsr::Epi e = {};
-    e.Out = out; e.ldo = k;
-    return gpsr::launch_gemm<gpsr::EPI_STORE>(A, d, ws.Wt, d, n, k, d, e, side_k, 1, st);
+    return launch_gemm(A, d, ws.Wt, d, n, k, d, StoreEpi{out, k, 0}, side_k, 1, st);
   };
   auto times_wt = [&](const float* A, float* out) -> hipError_t {
-    gpsr::Epi e = {};
-    e.Out = out; e.ldo = d;
-    return gpsr::launch_gemm<gpsr::EPI_STORE>(A, k, w, ldw, n, d, k, e, side_d, 1, st);
+    return launch_gemm(A, k, w, ldw, n, d, k, StoreEpi{out, d, 0}, side_d, 1, st);
   };
 
   // ---- the start ----

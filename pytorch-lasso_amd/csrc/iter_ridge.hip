@@ -21,27 +21,19 @@
 // A pivot that is not positive (or NaN) is recorded per row as 1 + its index in the compacted system and replaced by
 // 1: the kernel has no data-dependent loop and cannot fault on bad data.  The driver folds the flags (lowest row wins).
 //
-// Everything else is the GEMM of gemm_mainloop.hpp with the epilogues of gpsr_driver.hpp (G, x W, the residual with
+// Everything else is the GEMM of solver_common.hpp with its two plain epilogues (G, x W, the residual with
 // its sum of squares, q = p W^T) and element-wise passes whose sums are folded in double in a fixed order: no float
 // atomics, two solves of the same arguments are bitwise equal.  The host reads one control block per iteration (and one
 // per Brent evaluation).  With the line search, f(t) = 0.5 (|r|^2 + 2 t <r,q> + t^2 |q|^2) + alpha sum |z + t p| from
 // three sums taken once per iteration: a Brent evaluation is one pass over [n,k], never a product.
-#include "gpsr_driver.hpp"
+#include "solver_common.hpp"
 #include "brent_host.hpp"
 
 namespace lasso {
 namespace iter_ridge {
 namespace {
 
-using gemm_detail::f32x4;
-using gpsr::block_fold;
-using gpsr::block_side;
-using gpsr::device_cus;
-using gpsr::ew_grid;
-using gpsr::fold_partials;
-using gpsr::gemm_parts;
-using gpsr::kEwBlocks;
-using gpsr::kPart;
+using namespace solver;
 
 constexpr int kNB = 32;                       // block side of the packed triangle
 constexpr int kRS = 33;                       // row stride of a block in LDS (floats)
@@ -341,13 +333,6 @@ __global__ __launch_bounds__(256) void rows_kernel(RowsArgs a) {
   }
 }
 
-// z = z0 (pitch ld0), packed
-__global__ __launch_bounds__(256) void init_kernel(const float* __restrict__ S, int64_t ld0, float* __restrict__ Z, int n, int k) {
-  const int64_t total = (int64_t)n * k;
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256)
-    Z[i] = S[(i / k) * ld0 + (i % k)];
-}
-
 // p = z_sol - z over every entry (in place in the z_sol buffer)
 __global__ __launch_bounds__(256) void dir_kernel(float* __restrict__ ZS, const float* __restrict__ Z, int64_t total) {
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256)
@@ -584,21 +569,14 @@ int solve(const float* x, int64_t ldx, const float* w, int64_t ldw, const float*
 
   // ---- once per solve: G = W^T W, rhs = x W ----
   LASSO_HIP_TRY(launch_transpose_pad(w, ldw, d, k, ws.Wt, d, k, d, st));
-  {
-    gpsr::Epi e = {};
-    e.Out = ws.G; e.ldo = k;
-    LASSO_HIP_TRY(gpsr::launch_gemm<gpsr::EPI_STORE>(ws.Wt, d, ws.Wt, d, k, k, d, e, 64, 1, st));
-    e.Out = ws.RHS;
-    LASSO_HIP_TRY(gpsr::launch_gemm<gpsr::EPI_STORE>(x, ldx, ws.Wt, d, n, k, d, e, side_k, 1, st));
-  }
+  LASSO_HIP_TRY(launch_gemm(ws.Wt, d, ws.Wt, d, k, k, d, StoreEpi{ws.G, k, 0}, 64, 1, st));
+  LASSO_HIP_TRY(launch_gemm(x, ldx, ws.Wt, d, n, k, d, StoreEpi{ws.RHS, k, 0}, side_k, 1, st));
   Ctl h;
   memset(&h, 0, sizeof(h));
   auto fetch = [&]() -> int { return read_back(&h, ws.ctl, sizeof(Ctl), st); };
   // r = z W^T - x with the block partials of |r|^2
   auto residual = [&]() -> hipError_t {
-    gpsr::Epi e = {};
-    e.Y = x; e.ldy = ldx; e.Out = ws.R; e.ldo = d; e.part = ws.part_r;
-    return gpsr::launch_gemm<gpsr::EPI_RESID0>(ws.Z, k, w, ldw, n, d, k, e, side_d, 1, st);
+    return launch_gemm(ws.Z, k, w, ldw, n, d, k, Resid0Epi{x, ldx, ws.R, d, ws.part_r, 0}, side_d, 1, st);
   };
   auto stat = [&](bool flags) -> int {
     hipLaunchKernelGGL(stat_kernel, dim3(1), dim3(256), 0, st, ws.part_a, ga, (const double*)ws.part_r, pd,
@@ -607,7 +585,7 @@ int solve(const float* x, int64_t ldx, const float* w, int64_t ldw, const float*
     return fetch();
   };
 
-  hipLaunchKernelGGL(init_kernel, dim3(gk), dim3(256), 0, st, z0, ldz0, ws.Z, n, k);
+  hipLaunchKernelGGL(init_packed_kernel<>, dim3(gk), dim3(256), 0, st, z0, ldz0, ws.Z, n, k);
   hipLaunchKernelGGL(accept_kernel, dim3(ga), dim3(256), 0, st, ws.Z, (int64_t)k, (const float*)nullptr, n, k, eps, 2, 0.0f,
                      ws.part_a);
   LASSO_HIP_TRY(hipGetLastError());
@@ -627,9 +605,7 @@ int solve(const float* x, int64_t ldx, const float* w, int64_t ldw, const float*
     if (o.line_search) {
       hipLaunchKernelGGL(dir_kernel, dim3(gk), dim3(256), 0, st, ws.ZS, ws.Z, nk);
       LASSO_HIP_TRY(hipGetLastError());
-      gpsr::Epi e = {};
-      e.Out = ws.Q; e.ldo = d;
-      LASSO_HIP_TRY(gpsr::launch_gemm<gpsr::EPI_STORE>(ws.ZS, k, w, ldw, n, d, k, e, side_d, 1, st));
+      LASSO_HIP_TRY(launch_gemm(ws.ZS, k, w, ldw, n, d, k, StoreEpi{ws.Q, d, 0}, side_d, 1, st));
       hipLaunchKernelGGL(quad_kernel, dim3(gd), dim3(256), 0, st, ws.R, ws.Q, nd, ws.part_e);
       hipLaunchKernelGGL(quad_fold_kernel, dim3(1), dim3(256), 0, st, ws.part_e, gd, ws.ctl);
       LASSO_HIP_TRY(hipGetLastError());
@@ -691,7 +667,7 @@ int solve(const float* x, int64_t ldx, const float* w, int64_t ldw, const float*
   }
   res->n_iter = n_iter;
   res->status = status;
-  hipLaunchKernelGGL(gpsr::copy_out_kernel, dim3(gk), dim3(256), 0, st, ws.Z, zout, ldz, n, k, 0);
+  hipLaunchKernelGGL(copy_out_kernel<>, dim3(gk), dim3(256), 0, st, ws.Z, zout, ldz, n, k, 0);
   LASSO_HIP_TRY(hipGetLastError());
   LASSO_HIP_TRY(hipStreamSynchronize(st));
   return LASSO_OK;

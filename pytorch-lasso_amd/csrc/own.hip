@@ -2,7 +2,7 @@
 // behind lasso_own_solve.  min 0.5 |z W^T - x|^2 + alpha |z|_1 over the whole batch with the explicit Hessian
 // W^T W + 1e-4 I, whose inverse is one k x k matrix for the whole batch (computed once, in double, rounded once).
 //
-// Every product is the main loop of gemm.hip (gemm_mainloop.hpp) with an epilogue of its own, as in gpsr_driver.hpp:
+// Every product is solver_common.hpp's gemm_kernel (the main loop of gemm.hip) with an epilogue of its own:
 //   EPI_RESID  resid = z W^T - x stored, block partials of |resid|^2
 //   EPI_PGRAD  g = resid W on the accumulators; reads z, stores v = -pseudo-gradient, block partials of sum |z|
 //   EPI_DIR    d = project(v Hinv^T, v) stored
@@ -14,22 +14,14 @@
 // eta = where(z == 0, sign(v), sign(z)) is never stored: trial_kernel recomputes it from z and v.  No float atomics: two
 // solves of the same arguments are bitwise equal.  One line-search evaluation is trial_kernel + the TRIAL product +
 // decide_kernel and one host read of the control block; a backtracking ladder evaluates kRungs step sizes per read.
-#include "gpsr_driver.hpp"
+#include "hinv_f64.hpp"
 #include "brent_host.hpp"
 
 namespace lasso {
 namespace own {
 namespace {
 
-using gemm_detail::f32x4;
-using gpsr::block_fold;
-using gpsr::block_side;
-using gpsr::device_cus;
-using gpsr::ew_grid;
-using gpsr::fold_partials;
-using gpsr::gemm_parts;
-using gpsr::kEwBlocks;
-using gpsr::kPart;
+using namespace solver;
 
 constexpr int kRungs = 8;             // step sizes of a backtracking ladder per host read
 constexpr double kShift = 1e-4;       // the reference's hess.diagonal().add_(1e-4)
@@ -66,117 +58,85 @@ __device__ __forceinline__ float keep_sign(float u, bool w_pos, bool w_neg) {
   return ((u > 0.0f && w_pos) || (u < 0.0f && w_neg)) ? u : 0.0f;
 }
 
-// C = A B^T on the block (blockIdx.y, blockIdx.x), rung blockIdx.z; A [m][kk], B [nn][kk]
-template <int BM, int BN, bool VEC, bool DMA, int MODE>
-__global__ __launch_bounds__(256, 2) void own_gemm_kernel(const float* __restrict__ A, int64_t lda,
-                                                          const float* __restrict__ B, int64_t ldb, int m, int nn,
-                                                          int kk, Epi ep) {
-  constexpr int MI = BM / 32, NJ = BN / 32;
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int i0 = blockIdx.y * BM, j0 = blockIdx.x * BN;
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const int wr = w >> 1, wc = w & 1;
-  const int l15 = lane & 15, q = lane >> 4;
-  A += (int64_t)blockIdx.z * ep.a_stride;
-  f32x4 acc[MI][NJ] = {};
-  gemm_detail::gemm_nt_accumulate<BM, BN, VEC, DMA>(A, lda, B, ldb, m, nn, kk, i0, j0, smem, acc);
-  // the epilogue's operands through buffer descriptors of the tile's rows, as in gpsr_gemm_kernel: out of range reads 0
-  // and drops the store
-  const int rows_valid = min(BM, m - i0);
-  auto tile_rsrc = [&](const float* base, int64_t ld) {
-    const int64_t bytes = (int64_t)rows_valid * ld * 4;
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(base + (int64_t)i0 * ld), 0,
-                                             (int)(bytes < 0x7fffffff ? bytes : 0x7fffffff), 0x00020000);
-  };
-  auto tile_off = [&](int rl, int cc, int64_t ld) {
-    unsigned o = (rl < rows_valid && cc < nn) ? (unsigned)(rl * (int)ld + cc) * 4u : 0xfffffff0u;
-    asm volatile("" : "+v"(o));
-    return o;
-  };
-  auto ld32 = [](__amdgpu_buffer_rsrc_t rs, unsigned o) {
-    return __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs, o, 0, 0));
-  };
-  auto st32 = [](float v, __amdgpu_buffer_rsrc_t rs, unsigned o) {
-    __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), rs, o, 0, 0);
-  };
-  float s0 = 0.0f;
-  const int64_t ldn = nn;
+// the epilogue of mode MODE for solver_common.hpp's gemm_kernel
+template <int MODE>
+struct EpiM : Epi {
+  template <int BM, int BN>
+  __device__ __forceinline__ void run(const Tile<BM, BN>& t, f32x4 (&acc)[BM / 32][BN / 32], char* smem) const {
+    constexpr int MI = BM / 32, NJ = BN / 32;
+    const Epi& ep = *this;
+    float s0 = 0.0f;
+    const int64_t ldn = t.nn;
 #pragma unroll
-  for (int mi = 0; mi < MI; ++mi) {
-    unsigned o[NJ][4];
+    for (int mi = 0; mi < MI; ++mi) {
+      unsigned o[NJ][4];
+      t.offs(mi, ldn, o);
+      if constexpr (MODE == EPI_RESID || MODE == EPI_TRIAL) {
+        const __amdgpu_buffer_rsrc_t xrs = t.rsrc(ep.X, ep.ldx);
+        float x[NJ][4];
 #pragma unroll
-    for (int nj = 0; nj < NJ; ++nj)
+        for (int nj = 0; nj < NJ; ++nj)
 #pragma unroll
-      for (int rg = 0; rg < 4; ++rg)
-        o[nj][rg] = tile_off((BM / 2) * wr + 16 * mi + 4 * q + rg, j0 + (BN / 2) * wc + 16 * nj + l15, ldn);
-    if constexpr (MODE == EPI_RESID || MODE == EPI_TRIAL) {
-      const __amdgpu_buffer_rsrc_t xrs = tile_rsrc(ep.X, ep.ldx);
-      float x[NJ][4];
+          for (int rg = 0; rg < 4; ++rg) x[nj][rg] = t.ld32(xrs, t.off(mi, nj, rg, ep.ldx));
+        __amdgpu_buffer_rsrc_t ors = xrs;
+        if constexpr (MODE == EPI_RESID) ors = t.rsrc(ep.Out, ldn);
 #pragma unroll
-      for (int nj = 0; nj < NJ; ++nj)
+        for (int nj = 0; nj < NJ; ++nj)
 #pragma unroll
-        for (int rg = 0; rg < 4; ++rg)
-          x[nj][rg] = ld32(xrs, tile_off((BM / 2) * wr + 16 * mi + 4 * q + rg, j0 + (BN / 2) * wc + 16 * nj + l15, ep.ldx));
-      __amdgpu_buffer_rsrc_t ors = xrs;
-      if constexpr (MODE == EPI_RESID) ors = tile_rsrc(ep.Out, ldn);
+          for (int rg = 0; rg < 4; ++rg) {
+            const float r = __fsub_rn(acc[mi][nj][rg], x[nj][rg]);
+            if (t.inside(o[nj][rg])) s0 += __fmul_rn(r, r);
+            if constexpr (MODE == EPI_RESID) t.st32(r, ors, o[nj][rg]);
+          }
+      } else if constexpr (MODE == EPI_PGRAD) {
+        const __amdgpu_buffer_rsrc_t zrs = t.rsrc(ep.Z, ldn), ors = t.rsrc(ep.Out, ldn);
+        float z[NJ][4];
 #pragma unroll
-      for (int nj = 0; nj < NJ; ++nj)
+        for (int nj = 0; nj < NJ; ++nj)
 #pragma unroll
-        for (int rg = 0; rg < 4; ++rg) {       // (the LDS-DMA form clamps rows beyond the operand instead of zeroing them)
-          const float r = __fsub_rn(acc[mi][nj][rg], x[nj][rg]);
-          if (o[nj][rg] != 0xfffffff0u) s0 += __fmul_rn(r, r);
-          if constexpr (MODE == EPI_RESID) st32(r, ors, o[nj][rg]);
-        }
-    } else if constexpr (MODE == EPI_PGRAD) {
-      const __amdgpu_buffer_rsrc_t zrs = tile_rsrc(ep.Z, ldn), ors = tile_rsrc(ep.Out, ldn);
-      float z[NJ][4];
+          for (int rg = 0; rg < 4; ++rg) z[nj][rg] = t.ld32(zrs, o[nj][rg]);
 #pragma unroll
-      for (int nj = 0; nj < NJ; ++nj)
+        for (int nj = 0; nj < NJ; ++nj)
 #pragma unroll
-        for (int rg = 0; rg < 4; ++rg) z[nj][rg] = ld32(zrs, o[nj][rg]);
+          for (int rg = 0; rg < 4; ++rg) {
+            // pseudo_grad(), orthant_wise_newton.py:10-17: the right derivative if it is negative, the left if it is
+            // positive, else 0
+            const float zz = z[nj][rg], g = acc[mi][nj][rg];
+            const float sg = zz > 0.0f ? ep.alpha : (zz < 0.0f ? -ep.alpha : 0.0f);      // alpha * sign(z)
+            const float right = __fadd_rn(g, zz == 0.0f ? ep.alpha : sg);
+            const float left = __fadd_rn(g, zz == 0.0f ? -ep.alpha : sg);
+            float pg = 0.0f;
+            if (right < 0.0f) pg = right;
+            if (left > 0.0f) pg = left;
+            if (t.inside(o[nj][rg])) s0 += fabsf(zz);
+            t.st32(-pg, ors, o[nj][rg]);
+          }
+      } else {                                   // EPI_DIR
+        const __amdgpu_buffer_rsrc_t vrs = t.rsrc(ep.V, ldn), ors = t.rsrc(ep.Out, ldn);
+        float v[NJ][4];
 #pragma unroll
-      for (int nj = 0; nj < NJ; ++nj)
+        for (int nj = 0; nj < NJ; ++nj)
 #pragma unroll
-        for (int rg = 0; rg < 4; ++rg) {
-          // pseudo_grad(), orthant_wise_newton.py:10-17: the right derivative if it is negative, the left if it is
-          // positive, else 0
-          const float zz = z[nj][rg], g = acc[mi][nj][rg];
-          const float sg = zz > 0.0f ? ep.alpha : (zz < 0.0f ? -ep.alpha : 0.0f);      // alpha * sign(z)
-          const float right = __fadd_rn(g, zz == 0.0f ? ep.alpha : sg);
-          const float left = __fadd_rn(g, zz == 0.0f ? -ep.alpha : sg);
-          float pg = 0.0f;
-          if (right < 0.0f) pg = right;
-          if (left > 0.0f) pg = left;
-          if (o[nj][rg] != 0xfffffff0u) s0 += fabsf(zz);
-          st32(-pg, ors, o[nj][rg]);
-        }
-    } else {                                   // EPI_DIR
-      const __amdgpu_buffer_rsrc_t vrs = tile_rsrc(ep.V, ldn), ors = tile_rsrc(ep.Out, ldn);
-      float v[NJ][4];
+          for (int rg = 0; rg < 4; ++rg) v[nj][rg] = t.ld32(vrs, o[nj][rg]);
 #pragma unroll
-      for (int nj = 0; nj < NJ; ++nj)
+        for (int nj = 0; nj < NJ; ++nj)
 #pragma unroll
-        for (int rg = 0; rg < 4; ++rg) v[nj][rg] = ld32(vrs, o[nj][rg]);
-#pragma unroll
-      for (int nj = 0; nj < NJ; ++nj)
-#pragma unroll
-        for (int rg = 0; rg < 4; ++rg)
-          st32(keep_sign(acc[mi][nj][rg], v[nj][rg] > 0.0f, v[nj][rg] < 0.0f), ors, o[nj][rg]);
+          for (int rg = 0; rg < 4; ++rg)
+            t.st32(keep_sign(acc[mi][nj][rg], v[nj][rg] > 0.0f, v[nj][rg] < 0.0f), ors, o[nj][rg]);
+      }
+    }
+    if constexpr (MODE != EPI_DIR) {
+      double s[1] = {(double)s0};
+      float nomax[1] = {0.0f};
+      block_fold<1, 0>(s, nomax, reinterpret_cast<double*>(smem), t.partial(ep.part));
     }
   }
-  if constexpr (MODE != EPI_DIR) {
-    double s[1] = {(double)s0};
-    float nomax[1] = {0.0f};
-    double* const out = ep.part + ((int64_t)(blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x) * kPart;
-    block_fold<1, 0>(s, nomax, reinterpret_cast<double*>(smem), out);
-  }
-}
+};
 
-// z = z0 (pitch ld0), packed
-__global__ __launch_bounds__(256) void init_kernel(const float* __restrict__ S, int64_t ld0, float* __restrict__ Z, int n, int k) {
-  const int64_t total = (int64_t)n * k;
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256)
-    Z[i] = S[(i / k) * ld0 + (i % k)];
+template <int MODE>
+hipError_t launch_gemm(const float* A, int64_t lda, const float* B, int64_t ldb, int m, int nn, int kk, const Epi& ep, int side,
+                       int rungs, hipStream_t st) {
+  return solver::launch_gemm(A, lda, B, ldb, m, nn, kk, EpiM<MODE>{ep}, side, rungs, st);
 }
 
 // candidates of the rungs blockIdx.y: z_t = project(z + t d, eta); partials {sum |z_t|, <v, z_t - z>, |z_t - z|^2}
@@ -265,69 +225,18 @@ __global__ __launch_bounds__(256) void accept_kernel(const float* __restrict__ Z
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) Z[i] = zc[i];
 }
 
-// ---- Hinv: W in double, the identity, the inverse rounded once ----------------------------------------------------------
-__global__ __launch_bounds__(256) void widen_kernel(const float* __restrict__ W, int64_t ldw, double* __restrict__ Wd, int d, int k) {
-  const int64_t total = (int64_t)d * k;
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256)
-    Wd[i] = (double)W[(i / k) * ldw + (i % k)];
-}
-
-__global__ __launch_bounds__(256) void identity_kernel(double* __restrict__ I, int k) {
-  const int64_t total = (int64_t)k * k;
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256)
-    I[i] = (i / k) == (i % k) ? 1.0 : 0.0;
-}
-
-__global__ __launch_bounds__(256) void narrow_kernel(const double* __restrict__ S, float* __restrict__ Dst, int64_t total) {
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) Dst[i] = (float)S[i];
-}
-
-// ---- launchers -------------------------------------------------------------------------------------------------------
-template <int BS, bool VEC, bool DMA, int MODE>
-hipError_t launch_one(const float* A, int64_t lda, const float* B, int64_t ldb, int m, int nn, int kk, const Epi& ep, int rungs,
-                      hipStream_t st) {
-  constexpr int lds = 2 * (BS + BS) * 128;
-  if (lds > 48 * 1024)
-    if (hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(&own_gemm_kernel<BS, BS, VEC, DMA, MODE>), lds);
-        e != hipSuccess)
-      return e;
-  const dim3 grid((nn + BS - 1) / BS, (m + BS - 1) / BS, rungs);
-  hipLaunchKernelGGL((own_gemm_kernel<BS, BS, VEC, DMA, MODE>), grid, dim3(256), lds, st, A, lda, B, ldb, m, nn, kk, ep);
-  return hipGetLastError();
-}
-
-// the three operand forms of gpsr's launch_gemm: LDS-DMA, 16-byte buffer loads, scalar loads
-template <int MODE>
-hipError_t launch_gemm(const float* A, int64_t lda, const float* B, int64_t ldb, int m, int nn, int kk, const Epi& ep, int side,
-                       int rungs, hipStream_t st) {
-  const bool vec = kk % 4 == 0 && lda % 4 == 0 && ldb % 4 == 0 && ((uintptr_t)A & 15) == 0 && ((uintptr_t)B & 15) == 0 &&
-                   (ep.a_stride % 4) == 0;
-  const bool dma = vec && kk % 32 == 0 && lda * side * 4 < ((int64_t)1 << 31) && ldb * side * 4 < ((int64_t)1 << 31);
-  if (side == 128) {
-    if (dma) return launch_one<128, true, true, MODE>(A, lda, B, ldb, m, nn, kk, ep, rungs, st);
-    if (vec) return launch_one<128, true, false, MODE>(A, lda, B, ldb, m, nn, kk, ep, rungs, st);
-    return launch_one<128, false, false, MODE>(A, lda, B, ldb, m, nn, kk, ep, rungs, st);
-  }
-  if (dma) return launch_one<64, true, true, MODE>(A, lda, B, ldb, m, nn, kk, ep, rungs, st);
-  if (vec) return launch_one<64, true, false, MODE>(A, lda, B, ldb, m, nn, kk, ep, rungs, st);
-  return launch_one<64, false, false, MODE>(A, lda, B, ldb, m, nn, kk, ep, rungs, st);
-}
-
 struct Space {
   float *Wt, *Hinv, *Z, *V, *D, *R, *Zc;
   double *part_r, *part_p, *part_t;
   Ctl* ctl;
-  // the double stage of Hinv
-  double *Wd, *A, *B, *I, *Hd;
-  void* ridge;
-  size_t ridge_bytes;
+  HinvStage hinv;
   size_t bytes;
 };
 
 Space carve(void* base, int64_t n, int64_t d, int64_t k) {
   Space w;
   Arena a(base);
-  const size_t nk = (size_t)n * k * 4, nd = (size_t)n * d * 4, kk8 = (size_t)k * k * 8;
+  const size_t nk = (size_t)n * k * 4, nd = (size_t)n * d * 4;
   w.Wt = a.take((size_t)k * d * 4);
   w.Hinv = a.take((size_t)k * k * 4);
   w.Z = a.take(nk);
@@ -340,13 +249,7 @@ Space carve(void* base, int64_t n, int64_t d, int64_t k) {
   w.part_p = a.take<double>((size_t)gemm_parts((int)n, (int)k, 64) * kPart * 8);
   w.part_t = a.take<double>((size_t)kEwBlocks * kPart * 8 * kRungs);
   w.ctl = a.take<Ctl>(sizeof(Ctl));
-  w.Wd = a.take<double>((size_t)d * k * 8);
-  w.A = a.take<double>(kk8);
-  w.B = a.take<double>((size_t)k * 8);
-  w.I = a.take<double>(kk8);
-  w.Hd = a.take<double>(kk8);
-  w.ridge_bytes = lasso_ridge_f64_workspace_bytes(k, k);
-  w.ridge = a.take<char>(w.ridge_bytes);
+  w.hinv = carve_hinv(a, d, k);
   w.bytes = a.bytes();
   return w;
 }
@@ -372,20 +275,13 @@ int solve(const float* x, int64_t ldx, const float* w, int64_t ldw, const float*
   lasso_own_trace* const tr = res->trace;
   if (tr) tr->eval_count = 0;
 
-  // ---- Hinv = (W^T W + 1e-4 I)^-1 in double through the library's own Gram and Cholesky, rounded once ----
-  hipLaunchKernelGGL(widen_kernel, dim3(ew_grid((int64_t)d * k)), dim3(256), 0, st, w, ldw, ws.Wd, d, k);
-  hipLaunchKernelGGL(identity_kernel, dim3(ew_grid((int64_t)k * k)), dim3(256), 0, st, ws.I, k);
-  LASSO_HIP_TRY(hipGetLastError());
-  // (the Gram entry point also forms Z^T X: one column of W stands for X, its product is not used)
-  if (int s = lasso_gram_accumulate_f64(ws.Wd, k, ws.Wd, k, d, 1, k, ws.A, ws.B, nullptr, 0, st)) return s;
+  // ---- Hinv = (W^T W + 1e-4 I)^-1 (hinv_f64.hpp), the pivots' verdict read at once ----
   int32_t info = 0;
-  const int rs = lasso_ridge_solve_f64(ws.A, ws.I, ws.Hd, k, k, k, kShift, &info, ws.ridge, ws.ridge_bytes, st);
+  const int rs = build_hinv(w, ldw, d, k, 1.0, kShift, ws.hinv, ws.Hinv, &info, st);
   res->cholesky_info = info;
   if (rs == LASSO_ERR_BAD_ARG && info != 0)
     return fail(LASSO_ERR_BAD_ARG, "W^T W + 1e-4 I is not positive definite (pivot %d)", (int)info);
   if (rs) return rs;
-  hipLaunchKernelGGL(narrow_kernel, dim3(ew_grid((int64_t)k * k)), dim3(256), 0, st, ws.Hd, ws.Hinv, (int64_t)k * k);
-  LASSO_HIP_TRY(hipGetLastError());
   LASSO_HIP_TRY(launch_transpose_pad(w, ldw, d, k, ws.Wt, d, k, d, st));
 
   Ctl h;
@@ -432,7 +328,7 @@ int solve(const float* x, int64_t ldx, const float* w, int64_t ldw, const float*
     ++tr->eval_count;
   };
 
-  hipLaunchKernelGGL(init_kernel, dim3(gk), dim3(256), 0, st, z0, ldz0, ws.Z, n, k);
+  hipLaunchKernelGGL(init_packed_kernel<>, dim3(gk), dim3(256), 0, st, z0, ldz0, ws.Z, n, k);
   LASSO_HIP_TRY(hipGetLastError());
   if (int s = evaluate()) return s;
   res->f0 = res->f_final = h.f;
@@ -516,7 +412,7 @@ int solve(const float* x, int64_t ldx, const float* w, int64_t ldw, const float*
     if ((float)delta <= (float)o.xtol) break;               // the reference compares float32 values
   }
   res->n_iter = n_iter;
-  hipLaunchKernelGGL(gpsr::copy_out_kernel, dim3(gk), dim3(256), 0, st, ws.Z, zout, ldz, n, k, 0);
+  hipLaunchKernelGGL(copy_out_kernel<>, dim3(gk), dim3(256), 0, st, ws.Z, zout, ldz, n, k, 0);
   LASSO_HIP_TRY(hipGetLastError());
   LASSO_HIP_TRY(hipStreamSynchronize(st));
   return LASSO_OK;

@@ -5,7 +5,7 @@
 //   X = (Aty + lambd (D - B)) Hinv^T,  D = softshrink(X + B, 1 / lambd)
 // with B += tau (X - D) and update = |X - Xold|_F behind the last inner iteration of an outer one.
 //
-// Every product is the main loop of gemm.hip (gemm_mainloop.hpp) with an epilogue of its own, as in own.hip:
+// Every product is solver_common.hpp's gemm_kernel (the main loop of gemm.hip) with an epilogue of its own:
 //   EPI_ATY    Aty = (y Wt^T) / alpha stored
 //   EPI_INNER  x = T Hinv^T on the accumulators; reads B and Aty at the element, stores ONLY
 //              T+ = Aty + lambd (softshrink(x + B) - B): neither X nor D of an inner iteration reaches memory
@@ -17,20 +17,13 @@
 // never exists in memory: T carries all of it that the next product needs.  All sums: per thread, wave butterfly, the
 // four waves, block partial (double), then ONE workgroup folds the partials in a fixed order -- no float atomics, two
 // solves of the same arguments are bitwise equal.  No kernel has a data-dependent loop.
-#include "gpsr_driver.hpp"
+#include "hinv_f64.hpp"
 
 namespace lasso {
 namespace split_bregman {
 namespace {
 
-using gemm_detail::f32x4;
-using gpsr::block_fold;
-using gpsr::block_side;
-using gpsr::device_cus;
-using gpsr::ew_grid;
-using gpsr::fold_partials;
-using gpsr::gemm_parts;
-using gpsr::kPart;
+using namespace solver;
 
 constexpr int kLog = 1024;            // outer iterations whose figures the device keeps between two host reads
 
@@ -46,6 +39,7 @@ struct Epi {
   float* Out;                         // ATY: Aty; INNER / LAST: T+ (ld nn)
   const float* Y; int64_t ldy;        // COST: the data y [m][nn]
   double* part;                       // [blocks][kPart]
+  int64_t a_stride;                   // 0: every launch is one product (rungs = 1)
   float lambd, lam, tau, alpha;       // lam = 1 / lambd, the shrinkage threshold
 };
 
@@ -53,119 +47,95 @@ __device__ __forceinline__ float shrink(float v, float lam) {
   return v - __builtin_amdgcn_fmed3f(v, -lam, lam);    // == softshrink bit for bit (lam >= 0), as in cd.hip
 }
 
-// C = A B^T on the block (blockIdx.y, blockIdx.x); A [m][kk], B [nn][kk]
-template <int BM, int BN, bool VEC, bool DMA, int MODE>
-__global__ __launch_bounds__(256, 2) void sb_gemm_kernel(const float* __restrict__ A, int64_t lda,
-                                                         const float* __restrict__ B, int64_t ldb, int m, int nn,
-                                                         int kk, Epi ep) {
-  constexpr int MI = BM / 32, NJ = BN / 32;
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int i0 = blockIdx.y * BM, j0 = blockIdx.x * BN;
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const int wr = w >> 1, wc = w & 1;
-  const int l15 = lane & 15, q = lane >> 4;
-  f32x4 acc[MI][NJ] = {};
-  gemm_detail::gemm_nt_accumulate<BM, BN, VEC, DMA>(A, lda, B, ldb, m, nn, kk, i0, j0, smem, acc);
-  // the epilogue's operands through buffer descriptors of the tile's rows, as in gpsr_gemm_kernel: out of range reads 0
-  // and drops the store
-  const int rows_valid = min(BM, m - i0);
-  auto tile_rsrc = [&](const float* base, int64_t ld) {
-    const int64_t bytes = (int64_t)rows_valid * ld * 4;
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(base + (int64_t)i0 * ld), 0,
-                                             (int)(bytes < 0x7fffffff ? bytes : 0x7fffffff), 0x00020000);
-  };
-  auto tile_off = [&](int rl, int cc, int64_t ld) {
-    unsigned o = (rl < rows_valid && cc < nn) ? (unsigned)(rl * (int)ld + cc) * 4u : 0xfffffff0u;
-    asm volatile("" : "+v"(o));
-    return o;
-  };
-  auto ld32 = [](__amdgpu_buffer_rsrc_t rs, unsigned o) {
-    return __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs, o, 0, 0));
-  };
-  auto st32 = [](float v, __amdgpu_buffer_rsrc_t rs, unsigned o) {
-    __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), rs, o, 0, 0);
-  };
-  float s0 = 0.0f, s1 = 0.0f;
-  const int64_t ldn = nn;
+// the epilogue of mode MODE for solver_common.hpp's gemm_kernel
+template <int MODE>
+struct EpiM : Epi {
+  template <int BM, int BN>
+  __device__ __forceinline__ void run(const Tile<BM, BN>& t, f32x4 (&acc)[BM / 32][BN / 32], char* smem) const {
+    constexpr int MI = BM / 32, NJ = BN / 32;
+    const Epi& ep = *this;
+    float s0 = 0.0f, s1 = 0.0f;
+    const int64_t ldn = t.nn;
 #pragma unroll
-  for (int mi = 0; mi < MI; ++mi) {
-    unsigned o[NJ][4];
+    for (int mi = 0; mi < MI; ++mi) {
+      unsigned o[NJ][4];
+      t.offs(mi, ldn, o);
+      if constexpr (MODE == EPI_ATY) {
+        const __amdgpu_buffer_rsrc_t ors = t.rsrc(ep.Out, ldn);
 #pragma unroll
-    for (int nj = 0; nj < NJ; ++nj)
+        for (int nj = 0; nj < NJ; ++nj)
 #pragma unroll
-      for (int rg = 0; rg < 4; ++rg)
-        o[nj][rg] = tile_off((BM / 2) * wr + 16 * mi + 4 * q + rg, j0 + (BN / 2) * wc + 16 * nj + l15, ldn);
-    if constexpr (MODE == EPI_ATY) {
-      const __amdgpu_buffer_rsrc_t ors = tile_rsrc(ep.Out, ldn);
+          for (int rg = 0; rg < 4; ++rg) t.st32(__fdiv_rn(acc[mi][nj][rg], ep.alpha), ors, o[nj][rg]);
+      } else if constexpr (MODE == EPI_COST) {
+        const __amdgpu_buffer_rsrc_t yrs = t.rsrc(ep.Y, ep.ldy);
+        float y[NJ][4];
 #pragma unroll
-      for (int nj = 0; nj < NJ; ++nj)
+        for (int nj = 0; nj < NJ; ++nj)
 #pragma unroll
-        for (int rg = 0; rg < 4; ++rg) st32(__fdiv_rn(acc[mi][nj][rg], ep.alpha), ors, o[nj][rg]);
-    } else if constexpr (MODE == EPI_COST) {
-      const __amdgpu_buffer_rsrc_t yrs = tile_rsrc(ep.Y, ep.ldy);
-      float y[NJ][4];
-#pragma unroll
-      for (int nj = 0; nj < NJ; ++nj)
-#pragma unroll
-        for (int rg = 0; rg < 4; ++rg)
-          y[nj][rg] = ld32(yrs, tile_off((BM / 2) * wr + 16 * mi + 4 * q + rg, j0 + (BN / 2) * wc + 16 * nj + l15, ep.ldy));
-#pragma unroll
-      for (int nj = 0; nj < NJ; ++nj)
-#pragma unroll
-        for (int rg = 0; rg < 4; ++rg) {       // (the LDS-DMA form clamps rows beyond the operand instead of zeroing them)
-          const float r = __fsub_rn(acc[mi][nj][rg], y[nj][rg]);
-          if (o[nj][rg] != 0xfffffff0u) s0 += __fmul_rn(r, r);
-        }
-    } else {                                   // EPI_INNER, EPI_LAST
-      const __amdgpu_buffer_rsrc_t ars = tile_rsrc(ep.Aty, ldn), brs = tile_rsrc(ep.Bb, ldn), trs = tile_rsrc(ep.Out, ldn);
-      float aty[NJ][4], b[NJ][4], xo[NJ][4];
-#pragma unroll
-      for (int nj = 0; nj < NJ; ++nj)
-#pragma unroll
-        for (int rg = 0; rg < 4; ++rg) {
-          aty[nj][rg] = ld32(ars, o[nj][rg]);
-          b[nj][rg] = ld32(brs, o[nj][rg]);
-        }
-      if constexpr (MODE == EPI_INNER) {
+          for (int rg = 0; rg < 4; ++rg) y[nj][rg] = t.ld32(yrs, t.off(mi, nj, rg, ep.ldy));
 #pragma unroll
         for (int nj = 0; nj < NJ; ++nj)
 #pragma unroll
           for (int rg = 0; rg < 4; ++rg) {
-            const float bb = b[nj][rg];
-            const float dn = shrink(__fadd_rn(acc[mi][nj][rg], bb), ep.lam);
-            st32(__fmaf_rn(ep.lambd, __fsub_rn(dn, bb), aty[nj][rg]), trs, o[nj][rg]);
+            const float r = __fsub_rn(acc[mi][nj][rg], y[nj][rg]);
+            if (t.inside(o[nj][rg])) s0 += __fmul_rn(r, r);
           }
-      } else {
-        const __amdgpu_buffer_rsrc_t xrs = tile_rsrc(ep.X, ldn);
-#pragma unroll
-        for (int nj = 0; nj < NJ; ++nj)
-#pragma unroll
-          for (int rg = 0; rg < 4; ++rg) xo[nj][rg] = ld32(xrs, o[nj][rg]);
+      } else {                                   // EPI_INNER, EPI_LAST
+        const __amdgpu_buffer_rsrc_t ars = t.rsrc(ep.Aty, ldn), brs = t.rsrc(ep.Bb, ldn), trs = t.rsrc(ep.Out, ldn);
+        float aty[NJ][4], b[NJ][4], xo[NJ][4];
 #pragma unroll
         for (int nj = 0; nj < NJ; ++nj)
 #pragma unroll
           for (int rg = 0; rg < 4; ++rg) {
-            const float x = acc[mi][nj][rg], bb = b[nj][rg];
-            const float dn = shrink(__fadd_rn(x, bb), ep.lam);
-            const float bn = __fmaf_rn(ep.tau, __fsub_rn(x, dn), bb);            // b.add_(x - d, alpha=tau)
-            const float dx = __fsub_rn(x, xo[nj][rg]);
-            if (o[nj][rg] != 0xfffffff0u) {
-              s0 += __fmul_rn(dx, dx);
-              s1 += fabsf(x);
+            aty[nj][rg] = t.ld32(ars, o[nj][rg]);
+            b[nj][rg] = t.ld32(brs, o[nj][rg]);
+          }
+        if constexpr (MODE == EPI_INNER) {
+#pragma unroll
+          for (int nj = 0; nj < NJ; ++nj)
+#pragma unroll
+            for (int rg = 0; rg < 4; ++rg) {
+              const float bb = b[nj][rg];
+              const float dn = shrink(__fadd_rn(acc[mi][nj][rg], bb), ep.lam);
+              t.st32(__fmaf_rn(ep.lambd, __fsub_rn(dn, bb), aty[nj][rg]), trs, o[nj][rg]);
             }
-            st32(x, xrs, o[nj][rg]);
-            st32(bn, brs, o[nj][rg]);
-            st32(__fmaf_rn(ep.lambd, __fsub_rn(dn, bn), aty[nj][rg]), trs, o[nj][rg]);
-          }
+        } else {
+          const __amdgpu_buffer_rsrc_t xrs = t.rsrc(ep.X, ldn);
+#pragma unroll
+          for (int nj = 0; nj < NJ; ++nj)
+#pragma unroll
+            for (int rg = 0; rg < 4; ++rg) xo[nj][rg] = t.ld32(xrs, o[nj][rg]);
+#pragma unroll
+          for (int nj = 0; nj < NJ; ++nj)
+#pragma unroll
+            for (int rg = 0; rg < 4; ++rg) {
+              const float x = acc[mi][nj][rg], bb = b[nj][rg];
+              const float dn = shrink(__fadd_rn(x, bb), ep.lam);
+              const float bn = __fmaf_rn(ep.tau, __fsub_rn(x, dn), bb);            // b.add_(x - d, alpha=tau)
+              const float dx = __fsub_rn(x, xo[nj][rg]);
+              if (t.inside(o[nj][rg])) {
+                s0 += __fmul_rn(dx, dx);
+                s1 += fabsf(x);
+              }
+              t.st32(x, xrs, o[nj][rg]);
+              t.st32(bn, brs, o[nj][rg]);
+              t.st32(__fmaf_rn(ep.lambd, __fsub_rn(dn, bn), aty[nj][rg]), trs, o[nj][rg]);
+            }
+        }
       }
     }
+    if constexpr (MODE == EPI_LAST || MODE == EPI_COST) {
+      double s[2] = {(double)s0, (double)s1};
+      float nomax[1] = {0.0f};
+      block_fold<2, 0>(s, nomax, reinterpret_cast<double*>(smem), t.partial(ep.part));
+    }
   }
-  if constexpr (MODE == EPI_LAST || MODE == EPI_COST) {
-    double s[2] = {(double)s0, (double)s1};
-    float nomax[1] = {0.0f};
-    double* const out = ep.part + ((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * kPart;
-    block_fold<2, 0>(s, nomax, reinterpret_cast<double*>(smem), out);
-  }
+};
+
+template <int MODE>
+hipError_t launch_gemm(const float* A, int64_t lda, const float* B, int64_t ldb, int m, int nn, int kk, const Epi& ep, int side,
+                       hipStream_t st) {
+  return solver::launch_gemm(A, lda, B, ldb, m, nn, kk, EpiM<MODE>{ep}, side, 1, st);
 }
 
 // X = x0 (pitch ld0; null: zeros), B = 0
@@ -190,71 +160,18 @@ __global__ __launch_bounds__(256) void fold_kernel(const double* __restrict__ pa
   }
 }
 
-// ---- Hinv: W in double, its Gram over alpha, the identity, the inverse rounded once --------------------------------------
-__global__ __launch_bounds__(256) void widen_kernel(const float* __restrict__ W, int64_t ldw, double* __restrict__ Wd, int d, int k) {
-  const int64_t total = (int64_t)d * k;
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256)
-    Wd[i] = (double)W[(i / k) * ldw + (i % k)];
-}
-
-// G = G / alpha, I = the identity
-__global__ __launch_bounds__(256) void scale_identity_kernel(double* __restrict__ G, double* __restrict__ I, int k, double alpha) {
-  const int64_t total = (int64_t)k * k;
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
-    G[i] = G[i] / alpha;
-    I[i] = (i / k) == (i % k) ? 1.0 : 0.0;
-  }
-}
-
-__global__ __launch_bounds__(256) void narrow_kernel(const double* __restrict__ S, float* __restrict__ Dst, int64_t total) {
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) Dst[i] = (float)S[i];
-}
-
-// ---- launchers -------------------------------------------------------------------------------------------------------
-template <int BS, bool VEC, bool DMA, int MODE>
-hipError_t launch_one(const float* A, int64_t lda, const float* B, int64_t ldb, int m, int nn, int kk, const Epi& ep,
-                      hipStream_t st) {
-  constexpr int lds = 2 * (BS + BS) * 128;
-  if (lds > 48 * 1024)
-    if (hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(&sb_gemm_kernel<BS, BS, VEC, DMA, MODE>), lds);
-        e != hipSuccess)
-      return e;
-  const dim3 grid((nn + BS - 1) / BS, (m + BS - 1) / BS);
-  hipLaunchKernelGGL((sb_gemm_kernel<BS, BS, VEC, DMA, MODE>), grid, dim3(256), lds, st, A, lda, B, ldb, m, nn, kk, ep);
-  return hipGetLastError();
-}
-
-// the three operand forms of gpsr's launch_gemm: LDS-DMA, 16-byte buffer loads, scalar loads
-template <int MODE>
-hipError_t launch_gemm(const float* A, int64_t lda, const float* B, int64_t ldb, int m, int nn, int kk, const Epi& ep, int side,
-                       hipStream_t st) {
-  const bool vec = kk % 4 == 0 && lda % 4 == 0 && ldb % 4 == 0 && ((uintptr_t)A & 15) == 0 && ((uintptr_t)B & 15) == 0;
-  const bool dma = vec && kk % 32 == 0 && lda * side * 4 < ((int64_t)1 << 31) && ldb * side * 4 < ((int64_t)1 << 31);
-  if (side == 128) {
-    if (dma) return launch_one<128, true, true, MODE>(A, lda, B, ldb, m, nn, kk, ep, st);
-    if (vec) return launch_one<128, true, false, MODE>(A, lda, B, ldb, m, nn, kk, ep, st);
-    return launch_one<128, false, false, MODE>(A, lda, B, ldb, m, nn, kk, ep, st);
-  }
-  if (dma) return launch_one<64, true, true, MODE>(A, lda, B, ldb, m, nn, kk, ep, st);
-  if (vec) return launch_one<64, true, false, MODE>(A, lda, B, ldb, m, nn, kk, ep, st);
-  return launch_one<64, false, false, MODE>(A, lda, B, ldb, m, nn, kk, ep, st);
-}
-
 struct Space {
   float *Wt, *Hinv, *Aty, *T[2], *Bb, *X;
   double *part_x, *part_c;
   Log* log;
-  // the double stage of Hinv
-  double *Wd, *G, *Gx, *I, *Hd;
-  void* ridge;
-  size_t ridge_bytes;
+  HinvStage hinv;
   size_t bytes;
 };
 
 Space carve(void* base, int64_t n, int64_t d, int64_t k) {
   Space w;
   Arena a(base);
-  const size_t nk = (size_t)n * k * 4, kk8 = (size_t)k * k * 8;
+  const size_t nk = (size_t)n * k * 4;
   w.Wt = a.take((size_t)k * d * 4);
   w.Hinv = a.take((size_t)k * k * 4);
   w.Aty = a.take(nk);
@@ -266,13 +183,7 @@ Space carve(void* base, int64_t n, int64_t d, int64_t k) {
   w.part_x = a.take<double>((size_t)gemm_parts((int)n, (int)k, 64) * kPart * 8);
   w.part_c = a.take<double>((size_t)gemm_parts((int)n, (int)d, 64) * kPart * 8);
   w.log = a.take<Log>(sizeof(Log) * kLog);
-  w.Wd = a.take<double>((size_t)d * k * 8);
-  w.G = a.take<double>(kk8);
-  w.Gx = a.take<double>((size_t)k * 8);
-  w.I = a.take<double>(kk8);
-  w.Hd = a.take<double>(kk8);
-  w.ridge_bytes = lasso_ridge_f64_workspace_bytes(k, k);
-  w.ridge = a.take<char>(w.ridge_bytes);
+  w.hinv = carve_hinv(a, d, k);
   w.bytes = a.bytes();
   return w;
 }
@@ -293,24 +204,15 @@ int solve(const float* y, int64_t ldy, const float* w, int64_t ldw, const float*
   const int side_k = force128 ? 128 : block_side(n, k, ldmax, cus);      // products [n,k]
   const int side_d = force128 ? 128 : block_side(n, d, ldmax, cus);      // the cost product [n,d]
   const int pk = gemm_parts(n, k, side_k), pd = gemm_parts(n, d, side_d);
-  const int64_t nk = (int64_t)n * k, kk = (int64_t)k * k;
-  const int gk = ew_grid(nk);
+  const int gk = ew_grid((int64_t)n * k);
   lasso_split_bregman_trace* const tr = res->trace;
   const bool want_cost = tr && tr->cost;
 
-  // ---- Hinv = (W^T W / alpha + lambd I)^-1 in double through the library's own Gram and Cholesky, rounded once ----
-  hipLaunchKernelGGL(widen_kernel, dim3(ew_grid((int64_t)d * k)), dim3(256), 0, st, w, ldw, ws.Wd, d, k);
-  LASSO_HIP_TRY(hipGetLastError());
-  // (the Gram entry point also forms Z^T X: one column of W stands for X, its product is not used)
-  if (int s = lasso_gram_accumulate_f64(ws.Wd, k, ws.Wd, k, d, 1, k, ws.G, ws.Gx, nullptr, 0, st)) return s;
-  hipLaunchKernelGGL(scale_identity_kernel, dim3(ew_grid(kk)), dim3(256), 0, st, ws.G, ws.I, k, alpha);
-  LASSO_HIP_TRY(hipGetLastError());
-  // (no info_out: the verdict on the pivots stays in the word behind the working matrix until the first host read of the
-  // loop below -- a bad pivot is replaced by 1 and the factorisation goes on, nothing faults meanwhile)
-  if (int s = lasso_ridge_solve_f64(ws.G, ws.I, ws.Hd, k, k, k, o.lambd, nullptr, ws.ridge, ws.ridge_bytes, st)) return s;
-  const int* const info_dev = reinterpret_cast<const int*>(static_cast<const char*>(ws.ridge) + f64::ridge_workspace_bytes(k, k));
-  hipLaunchKernelGGL(narrow_kernel, dim3(ew_grid(kk)), dim3(256), 0, st, ws.Hd, ws.Hinv, kk);
-  LASSO_HIP_TRY(hipGetLastError());
+  // ---- Hinv = (W^T W / alpha + lambd I)^-1 (hinv_f64.hpp).  No info_out: the pivots' verdict waits behind the ridge
+  // workspace for the first host read of the loop below ----
+  if (int s = build_hinv(w, ldw, d, k, alpha, o.lambd, ws.hinv, ws.Hinv, nullptr, st)) return s;
+  const int* const info_dev =
+      reinterpret_cast<const int*>(static_cast<const char*>(ws.hinv.ridge) + f64::ridge_workspace_bytes(k, k));
   LASSO_HIP_TRY(launch_transpose_pad(w, ldw, d, k, ws.Wt, d, k, d, st));
   // ---- Aty = (y W) / alpha; X = x0, B = 0 (D = 0: the first T is Aty itself) ----
   Epi e0 = {};
@@ -390,7 +292,7 @@ int solve(const float* y, int64_t ldy, const float* w, int64_t ldw, const float*
   res->n_iter = done;
   res->itn = itn;
   res->stopped = stopped ? 1 : 0;
-  hipLaunchKernelGGL(gpsr::copy_out_kernel, dim3(gk), dim3(256), 0, st, ws.X, xout, ldx, n, k, 0);
+  hipLaunchKernelGGL(copy_out_kernel<>, dim3(gk), dim3(256), 0, st, ws.X, xout, ldx, n, k, 0);
   LASSO_HIP_TRY(hipGetLastError());
   LASSO_HIP_TRY(hipStreamSynchronize(st));
   return LASSO_OK;
