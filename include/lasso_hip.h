@@ -46,6 +46,8 @@
  *   - the iterated-ridge solver is lasso_iter_ridge_solve: LASSO_F32, any n, d, any pitch, k <= 1024.
  *   - the interior-point solver is lasso_interior_point_solve: LASSO_F32, any n, any pitch, d <= 256, k <= 4096.
  *   - the Split Bregman solver is lasso_split_bregman_solve: LASSO_F32, any n, d, any pitch, k <= 4096.
+ *   - conjugate gradients are lasso_cg_solve (dense; LASSO_F32 or LASSO_F64, any n, k, any pitch) and
+ *     lasso_conv_cg_solve (conv2d o conv_transpose2d + tik I; LASSO_F32, contiguous NCHW tensors).
  */
 #ifndef LASSO_HIP_H_
 #define LASSO_HIP_H_
@@ -1056,6 +1058,68 @@ int lasso_interior_point_solve(const void* x_dev, int64_t ldx, const void* w_dev
 int lasso_interior_point_rows(const void* w_dev, int64_t ldw, const void* c_dev, int64_t ldc, const void* b_dev,
                               int64_t ldb, void* y_dev, int64_t ldy, int64_t n, int64_t d, int64_t k, int dtype,
                               void* stream);
+
+/* ---- conjugate gradients: replace cg(), batch_cg(), batch_cg_conv2d(), lasso/conjgrad.py:13-107 ----
+ * x with Adot(x) = b for a whole batch of right-hand sides by the reference's conjgrad() (csrc/conjgrad.hip): x = 0,
+ * r = -b, p = b; alpha = rs_old / curv and rs_new / rs_old are one number per row (per image), the exits test sums over
+ * the whole batch, in the reference's order inside iteration i:
+ *   status 1  sum |r| <= termcond = rtol |b|_1 min(sqrt(|b|_1), 0.5), before the product
+ *   status 2  0 <= curv_sum <= 3 eps,  status 3  curv_sum < 0 (at i = 0 with x = -(rs_old / curv) b), before x moves
+ *   status 0  sqrt(sum rs_new) < tol, after x and r moved;  status 4  maxiter iterations ran
+ * Nothing is checked or repaired: a row whose curv is 0 gets 0 / 0, and with a NaN in the batch no exit fires.  The
+ * sums are folded in double in a fixed order and rounded once to the dtype, in which termcond and the comparisons are
+ * evaluated: two solves of the same arguments give the same bits.
+ * lasso_cg_solve: the dense operator Adot(v) = v A^T with a_dev [k][k] (not assumed symmetric), b_dev [n][k], x_dev
+ * [n][k], any pitch; LASSO_F32 (one fp32-MFMA product per iteration whose epilogue takes the per-row curv) or LASSO_F64
+ * (all three matrices double, leading dimensions in doubles; the fp64-MFMA product).  tik must be 0.
+ * lasso_conv_cg_solve: Adot(v) = conv2d(conv_transpose2d(v, w), w) + tik v (the tik term only where tik > 0) with w_dev
+ * [K][C][kh][kw], b_dev and z_out_dev [N][K][Hz][Wz], contiguous; the geometry as lasso_conv_gpsr_solve takes it
+ * (H = (Hz - 1) sh - 2 ph + kh, likewise W); LASSO_F32 only.
+ *   options : maxiter >= 0, tol >= 0, rtol >= 0, tik >= 0.  Bit 0 of reserved takes the plain forms -- dense: the
+ *             product stores Ap and a pass of its own takes curv; convolutional: conv_transpose2d as GEMM + overlap-add
+ *             also where an implicit kernel covers the geometry -- every other bit must be 0.
+ *   result  : n_iter (the index i of the iteration an exit fired in; maxiter for status 4), status, host_reads (waits
+ *             of the host for the device's control record: one per chunk of iterations; with rtol = 0 and tol = 0 one
+ *             at the end), form (LASSO_CG_FORM_*: what ran), termcond, and -- trace non-NULL -- host arrays of the
+ *             caller with, per iteration (capacity), sum |r| at its top, curv_sum and sqrt(sum rs_new), as the dtype
+ *             holds them.  Iteration i has its r_abs once exit 1 was tested, its curv_sum once the product ran, its rs
+ *             once x moved; entries beyond those are unspecified.
+ * Refusals before any HIP call: null pointers, n < 0, k < 1, a leading dimension below the row length, a bad geometry,
+ * maxiter < 0, a negative or NaN tol, rtol or tik, tik != 0 in the dense form or an undefined bit of reserved are
+ * LASSO_ERR_BAD_ARG; any other dtype LASSO_ERR_UNSUPPORTED (the workspace query returns 0); a short workspace
+ * LASSO_ERR_WORKSPACE.  n = 0 writes nothing.  The inputs are only read; the output may not alias one.  The calls block. */
+typedef struct lasso_cg_options {
+  int32_t maxiter, reserved;
+  double tol, rtol, tik;
+} lasso_cg_options;
+typedef struct lasso_cg_trace {
+  int32_t capacity, pad_;                 /* iterations the arrays below hold */
+  double* r_abs; double* curv_sum; double* rs;      /* each nullable */
+} lasso_cg_trace;
+#define LASSO_CG_ABS_TOL 0
+#define LASSO_CG_REL_TOL 1
+#define LASSO_CG_CURV_CONVERGED 2
+#define LASSO_CG_CURV_NEGATIVE 3
+#define LASSO_CG_MAXITER 4
+#define LASSO_CG_FORM_FUSED 0             /* dense fp32: curv in the product's epilogue */
+#define LASSO_CG_FORM_UNFUSED 1           /* dense: product, then a pass that takes curv (fp64 always) */
+#define LASSO_CG_FORM_CONV_IMPLICIT 2     /* conv_transpose2d by an implicit-GEMM kernel; conv2d as patches + GEMM */
+#define LASSO_CG_FORM_CONV_PATCHES 3      /* both convolutions as GEMMs around patch matrices */
+typedef struct lasso_cg_result {
+  int32_t n_iter, status, host_reads, form;
+  double termcond;
+  lasso_cg_trace* trace;                  /* nullable */
+} lasso_cg_result;
+size_t lasso_cg_workspace_bytes(int64_t n, int64_t k, int dtype);
+int lasso_cg_solve(const void* a_dev, int64_t lda, const void* b_dev, int64_t ldb, void* x_dev, int64_t ldx, int64_t n,
+                   int64_t k, int dtype, const lasso_cg_options* options, lasso_cg_result* result, void* workspace_dev,
+                   size_t workspace_bytes, void* stream);
+size_t lasso_conv_cg_workspace_bytes(int64_t N, int64_t C, int64_t H, int64_t W, int64_t K, int64_t Hz, int64_t Wz, int kh,
+                                     int kw, int sh, int sw, int ph, int pw);
+int lasso_conv_cg_solve(const void* w_dev, const void* b_dev, void* z_out_dev, int64_t N, int64_t C, int64_t H, int64_t W,
+                        int64_t K, int64_t Hz, int64_t Wz, int kh, int kw, int sh, int sw, int ph, int pw, int dtype,
+                        const lasso_cg_options* options, lasso_cg_result* result, void* workspace_dev,
+                        size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

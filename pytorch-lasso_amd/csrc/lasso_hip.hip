@@ -3082,6 +3082,81 @@ int lasso_interior_point_rows(const void* w_dev, int64_t ldw, const void* c_dev,
                               n, d, k, static_cast<hipStream_t>(stream));
 }
 
+// ---- conjugate gradients: conjgrad.py:13-107 (csrc/conjgrad.hip) -----------------------------
+static int check_cg_request(const lasso_cg_options* o, lasso_cg_result* res, bool dense) {
+  if (!o || !res) return fail(LASSO_ERR_BAD_ARG, "null options / result");
+  if (o->maxiter < 0 || !(o->tol >= 0.0) || !(o->rtol >= 0.0) || !(o->tik >= 0.0))
+    return fail(LASSO_ERR_BAD_ARG, "conjugate gradients: maxiter, tol, rtol, tik >= 0 are required");
+  if (dense && o->tik != 0.0) return fail(LASSO_ERR_BAD_ARG, "conjugate gradients: the dense form takes tik = 0");
+  if (o->reserved & ~1) return fail(LASSO_ERR_BAD_ARG, "conjugate gradients: only bit 0 of reserved is defined");
+  if (const lasso_cg_trace* t = res->trace)
+    if (t->capacity < 0) return fail(LASSO_ERR_BAD_ARG, "trace with a negative capacity");
+  res->n_iter = 0;
+  res->status = LASSO_CG_MAXITER;
+  res->host_reads = 0;
+  res->form = 0;
+  res->termcond = 0.0;
+  return LASSO_OK;
+}
+
+size_t lasso_cg_workspace_bytes(int64_t n, int64_t k, int dtype) {
+  if ((dtype != LASSO_F32 && dtype != LASSO_F64) || n < 0 || k <= 0 || n > INT32_MAX || k > INT32_MAX) return 0;
+  return conjgrad::workspace_bytes(n, k, dtype);
+}
+
+int lasso_cg_solve(const void* a_dev, int64_t lda, const void* b_dev, int64_t ldb, void* x_dev, int64_t ldx, int64_t n,
+                   int64_t k, int dtype, const lasso_cg_options* o, lasso_cg_result* res, void* workspace_dev,
+                   size_t workspace_bytes, void* stream) {
+  if (dtype != LASSO_F32 && dtype != LASSO_F64)
+    return fail(LASSO_ERR_UNSUPPORTED, "conjugate gradients: dtype %d (LASSO_F32 and LASSO_F64 are implemented)", dtype);
+  if (n < 0 || k <= 0 || n > INT32_MAX || k > INT32_MAX) return fail(LASSO_ERR_BAD_ARG, "bad shape");
+  if (int s = check_cg_request(o, res, true)) return s;
+  if (n == 0) return LASSO_OK;
+  if (!a_dev || !b_dev || !x_dev || !workspace_dev) return fail(LASSO_ERR_BAD_ARG, "null pointer");
+  if (lda < k || ldb < k || ldx < k) return fail(LASSO_ERR_BAD_ARG, "leading dimension too small");
+  if (workspace_bytes < lasso_cg_workspace_bytes(n, k, dtype))
+    return fail(LASSO_ERR_WORKSPACE, "need %zu bytes", lasso_cg_workspace_bytes(n, k, dtype));
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (dtype == LASSO_F64)
+    return conjgrad::solve_f64((const double*)a_dev, lda, (const double*)b_dev, ldb, (double*)x_dev, ldx, n, k, *o, res,
+                               workspace_dev, st);
+  return conjgrad::solve_f32((const float*)a_dev, lda, (const float*)b_dev, ldb, (float*)x_dev, ldx, n, k, *o, res,
+                             workspace_dev, st);
+}
+
+// what the convolutional form cannot address: the limits of the two GEMMs around the patch matrices (as convolutional GPSR)
+static bool conv_cg_too_large(const ConvGeom& g) {
+  const int64_t M = (int64_t)g.N * g.Hz * g.Wz, ldr = ((int64_t)g.C * g.kh * g.kw + 3) / 4 * 4;
+  return (int64_t)g.C * g.H * g.W > INT32_MAX || std::max<int64_t>({M, (int64_t)g.K, ldr}) * 64 * 4 >= ((int64_t)1 << 31);
+}
+
+size_t lasso_conv_cg_workspace_bytes(int64_t N, int64_t C, int64_t H, int64_t W, int64_t K, int64_t Hz, int64_t Wz, int kh,
+                                     int kw, int sh, int sw, int ph, int pw) {
+  const ConvGeom g = make_geom(N, C, H, W, K, Hz, Wz, kh, kw, sh, sw, ph, pw);
+  if (check_conv(g, LASSO_F32) || conv_cg_too_large(g)) return 0;
+  return conjgrad::conv_workspace_bytes(g);
+}
+
+int lasso_conv_cg_solve(const void* w_dev, const void* b_dev, void* z_out_dev, int64_t N, int64_t C, int64_t H, int64_t W,
+                        int64_t K, int64_t Hz, int64_t Wz, int kh, int kw, int sh, int sw, int ph, int pw, int dtype,
+                        const lasso_cg_options* o, lasso_cg_result* res, void* workspace_dev, size_t workspace_bytes,
+                        void* stream) {
+  if (dtype != LASSO_F32)
+    return fail(LASSO_ERR_UNSUPPORTED, "convolutional conjugate gradients: dtype %d (fp32 tensors only)", dtype);
+  const ConvGeom g = make_geom(N, C, H, W, K, Hz, Wz, kh, kw, sh, sw, ph, pw);
+  if (int s = check_conv(g, dtype)) return s;
+  if (conv_cg_too_large(g))
+    return fail(LASSO_ERR_UNSUPPORTED, "convolutional conjugate gradients: %lld code pixels / %lld image elements are beyond 32-bit block offsets",
+                (long long)(N * Hz * Wz), (long long)(C * H * W));
+  if (int s = check_cg_request(o, res, false)) return s;
+  if (N == 0) return LASSO_OK;
+  if (!w_dev || !b_dev || !z_out_dev || !workspace_dev) return fail(LASSO_ERR_BAD_ARG, "null pointer");
+  const size_t need = conjgrad::conv_workspace_bytes(g);
+  if (workspace_bytes < need) return fail(LASSO_ERR_WORKSPACE, "need %zu bytes", need);
+  return conjgrad::conv_solve((const float*)w_dev, (const float*)b_dev, (float*)z_out_dev, g, *o, res, workspace_dev,
+                              static_cast<hipStream_t>(stream));
+}
+
 // ---- unconstrained M-step: update_dict_ridge, dict_learning.py:106-123 ---------------------
 size_t lasso_ridge_workspace_bytes(int64_t d, int64_t k) {
   if (d <= 0 || k <= 0 || k > 4096) return 0;

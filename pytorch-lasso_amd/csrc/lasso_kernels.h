@@ -20,6 +20,8 @@ struct lasso_interior_point_options;
 struct lasso_interior_point_result;
 struct lasso_split_bregman_options;
 struct lasso_split_bregman_result;
+struct lasso_cg_options;
+struct lasso_cg_result;
 
 namespace lasso {
 
@@ -605,5 +607,17 @@ int solve(const float* x, int64_t ldx, const float* w, int64_t ldw, const float*
 int rows(const float* w, int64_t ldw, const float* c, int64_t ldc, const float* b, int64_t ldb, float* y, int64_t ldy, int64_t n,
          int64_t d, int64_t k, hipStream_t st);
 }  // namespace interior_point
+
+// conjugate gradients (conjgrad.hip): the drivers behind lasso_cg_solve / lasso_conv_cg_solve; return a lasso_status
+namespace conjgrad {
+size_t workspace_bytes(int64_t n, int64_t k, int dtype);
+int solve_f32(const float* A, int64_t lda, const float* b, int64_t ldb, float* xout, int64_t ldx, int64_t n, int64_t k,
+              const lasso_cg_options& o, lasso_cg_result* res, void* workspace, hipStream_t st);
+int solve_f64(const double* A, int64_t lda, const double* b, int64_t ldb, double* xout, int64_t ldx, int64_t n, int64_t k,
+              const lasso_cg_options& o, lasso_cg_result* res, void* workspace, hipStream_t st);
+size_t conv_workspace_bytes(const ConvGeom& g);
+int conv_solve(const float* w, const float* b, float* zout, const ConvGeom& g, const lasso_cg_options& o, lasso_cg_result* res,
+               void* workspace, hipStream_t st);
+}  // namespace conjgrad
 
 }  // namespace lasso

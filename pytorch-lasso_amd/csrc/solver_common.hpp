@@ -18,6 +18,8 @@
 #include <stdio.h>
 #include <string.h>
 #include <algorithm>
+#include <type_traits>
+#include <utility>
 #include <vector>
 
 #include "../../include/lasso_hip.h"
@@ -129,6 +131,11 @@ struct Tile {
   }
 };
 
+// An epilogue may have `__device__ bool skip() const`: true -> the whole launch does nothing (a stop flag on the device,
+// conjgrad.hip).  Epilogues without it compile to what they were.
+template <class E, class = void> struct has_skip : std::false_type {};
+template <class E> struct has_skip<E, std::void_t<decltype(std::declval<const E&>().skip())>> : std::true_type {};
+
 // C = A B^T on the block (blockIdx.y, blockIdx.x), rung blockIdx.z; A [m][kk], B [nn][kk]; C goes to the epilogue
 template <int BM, int BN, bool VEC, bool DMA, class E>
 __global__ __launch_bounds__(256, 2) void gemm_kernel(const float* __restrict__ A, int64_t lda, const float* __restrict__ B,
@@ -137,6 +144,8 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(const float* __restrict__ 
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int i0 = blockIdx.y * BM, j0 = blockIdx.x * BN;
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  if constexpr (has_skip<E>::value)
+    if (ep.skip()) return;
   A += (int64_t)blockIdx.z * ep.a_stride;
   f32x4 acc[MI][NJ] = {};
   gemm_detail::gemm_nt_accumulate<BM, BN, VEC, DMA>(A, lda, B, ldb, m, nn, kk, i0, j0, smem, acc);

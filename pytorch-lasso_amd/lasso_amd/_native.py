@@ -31,6 +31,9 @@ OWN_BRENT, OWN_BACKTRACK, OWN_NONE = 0, 1, 2
 OWN_LS_NOT_CONVERGED, OWN_NONFINITE = 1, 2
 ITER_RIDGE_CONVERGED, ITER_RIDGE_NAN, ITER_RIDGE_MAXITER = 0, 1, 2
 INTERIOR_POINT_CONVERGED, INTERIOR_POINT_MAXITER, INTERIOR_POINT_BAD_START = 0, 1, 2
+CG_ABS_TOL, CG_REL_TOL, CG_CURV_CONVERGED, CG_CURV_NEGATIVE, CG_MAXITER = 0, 1, 2, 3, 4
+CG_FORMS = ('fused', 'unfused', 'conv-implicit', 'conv-patches')      # LASSO_CG_FORM_*
+CG_PLAIN_FORM = 1                                                     # bit 0 of lasso_cg_options.reserved
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = None
@@ -146,6 +149,24 @@ class SplitBregmanResult(C.Structure):
     """lasso_split_bregman_result"""
     _fields_ = [('n_iter', C.c_int32), ('itn', C.c_int32), ('stopped', C.c_int32), ('cholesky_info', C.c_int32),
                 ('trace', C.POINTER(SplitBregmanTrace))]
+
+
+class CgOptions(C.Structure):
+    """lasso_cg_options"""
+    _fields_ = [('maxiter', C.c_int32), ('reserved', C.c_int32), ('tol', C.c_double), ('rtol', C.c_double),
+                ('tik', C.c_double)]
+
+
+class CgTrace(C.Structure):
+    """lasso_cg_trace: host arrays of the caller"""
+    _pd = C.POINTER(C.c_double)
+    _fields_ = [('capacity', C.c_int32), ('pad_', C.c_int32), ('r_abs', _pd), ('curv_sum', _pd), ('rs', _pd)]
+
+
+class CgResult(C.Structure):
+    """lasso_cg_result"""
+    _fields_ = [('n_iter', C.c_int32), ('status', C.c_int32), ('host_reads', C.c_int32), ('form', C.c_int32),
+                ('termcond', C.c_double), ('trace', C.POINTER(CgTrace))]
 
 
 # int (*lasso_allreduce_fn)(void* ctx, double* sums, int count)   (include/lasso_hip.h)
@@ -393,6 +414,16 @@ def _declare(lib):
                                                C.POINTER(InteriorPointOptions), C.POINTER(InteriorPointResult), vp, sz, vp]
     lib.lasso_interior_point_rows.restype = i32
     lib.lasso_interior_point_rows.argtypes = [vp, i64, vp, i64, vp, i64, vp, i64, i64, i64, i64, i32, vp]
+    lib.lasso_cg_workspace_bytes.restype = sz
+    lib.lasso_cg_workspace_bytes.argtypes = [i64, i64, i32]
+    lib.lasso_cg_solve.restype = i32
+    lib.lasso_cg_solve.argtypes = [vp, i64, vp, i64, vp, i64, i64, i64, i32, C.POINTER(CgOptions), C.POINTER(CgResult),
+                                   vp, sz, vp]
+    lib.lasso_conv_cg_workspace_bytes.restype = sz
+    lib.lasso_conv_cg_workspace_bytes.argtypes = [i64] * 7 + [i32] * 6
+    lib.lasso_conv_cg_solve.restype = i32
+    lib.lasso_conv_cg_solve.argtypes = [vp, vp, vp] + [i64] * 7 + [i32] * 6 + [i32, C.POINTER(CgOptions),
+                                                                             C.POINTER(CgResult), vp, sz, vp]
     lib.lasso_cd_solve.restype = i32
     lib.lasso_cd_solve.argtypes = [vp, i64, vp, i64, vp, i64, vp, i64, i64, i64, i64, i32, dbl, i32,
                                    dbl, pi32, pi32, vp, sz, vp]
