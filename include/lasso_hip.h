@@ -1121,6 +1121,50 @@ int lasso_conv_cg_solve(const void* w_dev, const void* b_dev, void* z_out_dev, i
                         const lasso_cg_options* options, lasso_cg_result* result, void* workspace_dev,
                         size_t workspace_bytes, void* stream);
 
+/* ---- exact Lipschitz constant of a convolutional dictionary: replace lip_constant(), lasso/conv2d/lip_const.py:8-31 ----
+ * The largest eigenvalue of conv_transpose2d o conv2d (equally of conv2d o conv_transpose2d: the nonzero spectra
+ * coincide) for w_dev [K][C][kh][kw], contiguous, by Lanczos with full reorthogonalisation on the device
+ * (csrc/conv_lanczos.hip); LASSO_F32 or LASSO_F64, the value is computed in that dtype.
+ * (H, W) is the reference's imsize: with transpose == 0 the size of the IMAGE (C x H x W vectors; it must round-trip,
+ * (H + 2 ph - kh) % sh == 0 and likewise the width), with transpose != 0 the size of the CODE (K x H x W vectors).  The
+ * iteration runs in whichever of the two spaces is smaller (result.space); the start vector is a fixed counter-based
+ * pseudo-random vector, every sum is folded in double in a fixed order: the same arguments give the same bits.
+ *   options : maxiter >= 1 Lanczos steps at most; tol >= 0, relative: the first step j with
+ *             beta_j |s_j| <= tol theta_j stops (theta_j the largest Ritz value, s_j the last component of its vector);
+ *             tol = 0 runs to maxiter or to breakdown.  reserved must be 0.
+ *   result  : theta (the value; NaN for a non-finite kernel, 0 for a zero one), residual = beta_j |s_j| (some eigenvalue
+ *             lies within it of theta), steps (Lanczos steps the value rests on), matvecs (operator applications
+ *             launched), host_reads (waits of the host for the device: one per chunk of 8, 16, 32, 32, ... steps),
+ *             space (LASSO_LIP_SPACE_*), dim (of that space), status (LASSO_LIP_*), restarts (times the basis was full
+ *             and the iteration went on from the Ritz vector: more than 512 steps, or a basis beyond 1 GiB), and --
+ *             history non-NULL -- theta_1 .. theta_steps in a host array of the caller (history_capacity entries).
+ * Refusals before any HIP call: null pointers, a bad or non-round-tripping geometry, maxiter < 1, a negative or NaN
+ * tol or reserved != 0 are LASSO_ERR_BAD_ARG; any other dtype and geometries beyond the 32-bit block offsets of the
+ * convolution kernels LASSO_ERR_UNSUPPORTED (the workspace query returns 0); a short workspace LASSO_ERR_WORKSPACE.
+ * The call blocks. */
+typedef struct lasso_conv_lip_options {
+  int32_t maxiter, reserved;
+  double tol;
+} lasso_conv_lip_options;
+#define LASSO_LIP_CONVERGED 0
+#define LASSO_LIP_BREAKDOWN 1             /* an invariant subspace was found (or the basis spans the space): exact */
+#define LASSO_LIP_MAXITER 2
+#define LASSO_LIP_NONFINITE 3             /* a NaN or Inf reached the recurrence: theta is NaN */
+#define LASSO_LIP_SPACE_IMAGE 0
+#define LASSO_LIP_SPACE_CODE 1
+typedef struct lasso_conv_lip_result {
+  double theta, residual;
+  int64_t dim;
+  int32_t steps, matvecs, host_reads, space, status, restarts;
+  int32_t history_capacity, pad_;
+  double* history;                        /* nullable */
+} lasso_conv_lip_result;
+size_t lasso_conv_lip_constant_workspace_bytes(int64_t K, int64_t C, int kh, int kw, int64_t H, int64_t W, int sh, int sw,
+                                               int ph, int pw, int transpose, int dtype, int maxiter);
+int lasso_conv_lip_constant(const void* w_dev, int64_t K, int64_t C, int kh, int kw, int64_t H, int64_t W, int sh, int sw,
+                            int ph, int pw, int transpose, int dtype, const lasso_conv_lip_options* options,
+                            lasso_conv_lip_result* result, void* workspace_dev, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -523,6 +523,19 @@ size_t conv_lip_workspace_bytes(int64_t K, int64_t C, int sample) {
   return align_up((size_t)sample * 8) + align_up((size_t)std::min(K, C) * 8) + 256;
 }
 
+// The two products as another driver takes them (conv_lanczos.hip): the very launches conv_backward makes, one image or
+// many.  img = conv_transpose2d(Ym, W) through cols [M][C kh kw]; G [M][K] = conv2d(img, W).
+int launch_conv_synthesis(const double* Ym, const double* w, double* cols, double* img, const ConvGeom& g, hipStream_t st) {
+  if (int s = check_reach(g)) return s;
+  return synthesis(Ym, w, nullptr, cols, img, g, st);
+}
+int launch_conv_gradient(const double* img, const double* w, double* G, const ConvGeom& g, hipStream_t st) {
+  if (int s = check_reach(g)) return s;
+  const Dims d(g);
+  const ConvGradArgs a{img, w, nullptr, G, nullptr, nullptr, 0.0, 0.0, 0.0, nullptr, g, (int)d.M, (int)d.ckk};
+  return gradient<EPI_ADD>(a, st);
+}
+
 // The stop rule (ista.py:44-46) is read once per chunk of speculated iterations (speculate_stop_rule);
 // a stop inside a chunk restores the chunk's head and replays exactly the iterations up to the stop.  With a trace the
 // count is fixed (no stop rule) and every iterate is kept.

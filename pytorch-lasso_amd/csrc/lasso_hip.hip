@@ -3157,6 +3157,70 @@ int lasso_conv_cg_solve(const void* w_dev, const void* b_dev, void* z_out_dev, i
                               static_cast<hipStream_t>(stream));
 }
 
+// ---- exact Lipschitz constant of a convolutional dictionary: lip_const.py:8-31 (csrc/conv_lanczos.hip) -------
+// The geometry of a batch of one from the reference's imsize: the image's size (transpose == 0, it must round-trip) or
+// the code's.  false: no such geometry.
+static bool conv_lip_geom(int64_t K, int64_t C, int kh, int kw, int64_t H, int64_t W, int sh, int sw, int ph, int pw,
+                          int transpose, ConvGeom* g) {
+  if (K <= 0 || C <= 0 || kh <= 0 || kw <= 0 || H <= 0 || W <= 0 || sh <= 0 || sw <= 0 || ph < 0 || pw < 0 ||
+      K > INT32_MAX || C > INT32_MAX || H > INT32_MAX / 2 || W > INT32_MAX / 2)
+    return false;
+  int64_t Hi, Wi, Hz, Wz;
+  if (transpose) {
+    Hz = H; Wz = W;
+    Hi = (Hz - 1) * sh - 2 * (int64_t)ph + kh;
+    Wi = (Wz - 1) * sw - 2 * (int64_t)pw + kw;
+  } else {
+    Hi = H; Wi = W;
+    const int64_t eh = Hi + 2 * (int64_t)ph - kh, ew = Wi + 2 * (int64_t)pw - kw;
+    if (eh < 0 || ew < 0 || eh % sh != 0 || ew % sw != 0) return false;
+    Hz = eh / sh + 1; Wz = ew / sw + 1;
+  }
+  if (Hi <= 0 || Wi <= 0 || Hi > INT32_MAX / 2 || Wi > INT32_MAX / 2) return false;
+  *g = make_geom(1, C, Hi, Wi, K, Hz, Wz, kh, kw, sh, sw, ph, pw);
+  return true;
+}
+
+static int conv_lip_code_space(const ConvGeom& g) {       // the smaller space; a tie goes to the images
+  return (int64_t)g.K * g.Hz * g.Wz < (int64_t)g.C * g.H * g.W;
+}
+
+size_t lasso_conv_lip_constant_workspace_bytes(int64_t K, int64_t C, int kh, int kw, int64_t H, int64_t W, int sh, int sw,
+                                               int ph, int pw, int transpose, int dtype, int maxiter) {
+  ConvGeom g;
+  if ((dtype != LASSO_F32 && dtype != LASSO_F64) || maxiter < 1) return 0;
+  if (!conv_lip_geom(K, C, kh, kw, H, W, sh, sw, ph, pw, transpose, &g)) return 0;
+  if (check_conv(g, dtype) || conv_cg_too_large(g)) return 0;
+  return lanczos::workspace_bytes(g, conv_lip_code_space(g), maxiter, dtype);
+}
+
+int lasso_conv_lip_constant(const void* w_dev, int64_t K, int64_t C, int kh, int kw, int64_t H, int64_t W, int sh, int sw,
+                            int ph, int pw, int transpose, int dtype, const lasso_conv_lip_options* o,
+                            lasso_conv_lip_result* res, void* workspace_dev, size_t workspace_bytes, void* stream) {
+  if (dtype != LASSO_F32 && dtype != LASSO_F64)
+    return fail(LASSO_ERR_UNSUPPORTED, "lip_constant: dtype %d (LASSO_F32 and LASSO_F64 are implemented)", dtype);
+  if (!o || !res || !w_dev || !workspace_dev) return fail(LASSO_ERR_BAD_ARG, "null pointer");
+  if (o->maxiter < 1 || !(o->tol >= 0.0) || o->reserved != 0)
+    return fail(LASSO_ERR_BAD_ARG, "lip_constant: maxiter >= 1, tol >= 0 and reserved == 0 are required");
+  if (res->history && res->history_capacity < 0) return fail(LASSO_ERR_BAD_ARG, "history with a negative capacity");
+  ConvGeom g;
+  if (!conv_lip_geom(K, C, kh, kw, H, W, sh, sw, ph, pw, transpose, &g))
+    return fail(LASSO_ERR_BAD_ARG, "lip_constant: no convolution of a %lldx%lld %s by a %dx%d kernel, stride %d,%d padding %d,%d%s",
+                (long long)H, (long long)W, transpose ? "code" : "image", kh, kw, sh, sw, ph, pw,
+                transpose ? "" : " (the image size must round-trip)");
+  if (int s = check_conv(g, dtype)) return s;
+  if (conv_cg_too_large(g))
+    return fail(LASSO_ERR_UNSUPPORTED, "lip_constant: %lld code pixels / %lld image elements are beyond 32-bit block offsets",
+                (long long)g.Hz * g.Wz, (long long)C * g.H * g.W);
+  res->theta = res->residual = NAN;
+  res->steps = res->matvecs = res->host_reads = res->restarts = 0;
+  res->status = LASSO_LIP_MAXITER;
+  const int code_space = conv_lip_code_space(g);
+  const size_t need = lanczos::workspace_bytes(g, code_space, o->maxiter, dtype);
+  if (workspace_bytes < need) return fail(LASSO_ERR_WORKSPACE, "need %zu bytes", need);
+  return lanczos::run(w_dev, g, code_space, dtype, *o, res, workspace_dev, static_cast<hipStream_t>(stream));
+}
+
 // ---- unconstrained M-step: update_dict_ridge, dict_learning.py:106-123 ---------------------
 size_t lasso_ridge_workspace_bytes(int64_t d, int64_t k) {
   if (d <= 0 || k <= 0 || k > 4096) return 0;

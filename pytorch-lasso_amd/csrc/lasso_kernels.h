@@ -22,6 +22,8 @@ struct lasso_split_bregman_options;
 struct lasso_split_bregman_result;
 struct lasso_cg_options;
 struct lasso_cg_result;
+struct lasso_conv_lip_options;
+struct lasso_conv_lip_result;
 
 namespace lasso {
 
@@ -537,6 +539,10 @@ int conv_backward(const double* x, const double* w, const double* trace, const d
                   hipStream_t st);
 int conv_lip_bound(const double* w, int64_t K, int64_t C, int ksize, int padding, int sample, int take_sqrt, double* l_out,
                    void* workspace, size_t ws_bytes, hipStream_t st);
+// the two products of the solve on their own (conv_lanczos.hip): img [N][C][H][W] = conv_transpose2d(Ym [M][K], W) through
+// cols [M][C kh kw], and G [M][K] = conv2d(img, W); a lasso_status each
+int launch_conv_synthesis(const double* Ym, const double* w, double* cols, double* img, const ConvGeom& g, hipStream_t st);
+int launch_conv_gradient(const double* img, const double* w, double* G, const ConvGeom& g, hipStream_t st);
 // float64 M-step (mstep_f64.hip): Gram products, atom sweep, ridge solve in double on the fp64 MFMA
 constexpr int kGramF64MaxSplits = 16;
 int gram_splits(int64_t n, int64_t d, int64_t k, int cus);      // row splits of both products (1: no partial slabs)
@@ -619,5 +625,15 @@ size_t conv_workspace_bytes(const ConvGeom& g);
 int conv_solve(const float* w, const float* b, float* zout, const ConvGeom& g, const lasso_cg_options& o, lasso_cg_result* res,
                void* workspace, hipStream_t st);
 }  // namespace conjgrad
+
+// Lanczos for the largest eigenvalue of conv_transpose2d o conv2d (conv_lanczos.hip): the driver behind
+// lasso_conv_lip_constant; g.N == 1; returns a lasso_status
+namespace lanczos {
+// code_space: iterate on K x Hz x Wz vectors, else on C x H x W ones; basis: vectors of one cycle (basis_size)
+int basis_size(int64_t dim, int maxiter, int dtype);
+size_t workspace_bytes(const ConvGeom& g, int code_space, int maxiter, int dtype);
+int run(const void* w, const ConvGeom& g, int code_space, int dtype, const lasso_conv_lip_options& o,
+        lasso_conv_lip_result* res, void* workspace, hipStream_t st);
+}  // namespace lanczos
 
 }  // namespace lasso

@@ -33,6 +33,8 @@ ITER_RIDGE_CONVERGED, ITER_RIDGE_NAN, ITER_RIDGE_MAXITER = 0, 1, 2
 INTERIOR_POINT_CONVERGED, INTERIOR_POINT_MAXITER, INTERIOR_POINT_BAD_START = 0, 1, 2
 CG_ABS_TOL, CG_REL_TOL, CG_CURV_CONVERGED, CG_CURV_NEGATIVE, CG_MAXITER = 0, 1, 2, 3, 4
 CG_FORMS = ('fused', 'unfused', 'conv-implicit', 'conv-patches')      # LASSO_CG_FORM_*
+LIP_STATUS = ('converged', 'breakdown', 'maxiter', 'nonfinite')         # LASSO_LIP_*
+LIP_SPACES = ('image', 'code')                                        # LASSO_LIP_SPACE_*
 CG_PLAIN_FORM = 1                                                     # bit 0 of lasso_cg_options.reserved
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -167,6 +169,19 @@ class CgResult(C.Structure):
     """lasso_cg_result"""
     _fields_ = [('n_iter', C.c_int32), ('status', C.c_int32), ('host_reads', C.c_int32), ('form', C.c_int32),
                 ('termcond', C.c_double), ('trace', C.POINTER(CgTrace))]
+
+
+class ConvLipOptions(C.Structure):
+    """lasso_conv_lip_options"""
+    _fields_ = [('maxiter', C.c_int32), ('reserved', C.c_int32), ('tol', C.c_double)]
+
+
+class ConvLipResult(C.Structure):
+    """lasso_conv_lip_result; history: a host array of the caller"""
+    _fields_ = [('theta', C.c_double), ('residual', C.c_double), ('dim', C.c_int64), ('steps', C.c_int32),
+                ('matvecs', C.c_int32), ('host_reads', C.c_int32), ('space', C.c_int32), ('status', C.c_int32),
+                ('restarts', C.c_int32), ('history_capacity', C.c_int32), ('pad_', C.c_int32),
+                ('history', C.POINTER(C.c_double))]
 
 
 # int (*lasso_allreduce_fn)(void* ctx, double* sums, int count)   (include/lasso_hip.h)
@@ -424,6 +439,11 @@ def _declare(lib):
     lib.lasso_conv_cg_solve.restype = i32
     lib.lasso_conv_cg_solve.argtypes = [vp, vp, vp] + [i64] * 7 + [i32] * 6 + [i32, C.POINTER(CgOptions),
                                                                              C.POINTER(CgResult), vp, sz, vp]
+    lib.lasso_conv_lip_constant_workspace_bytes.restype = sz
+    lib.lasso_conv_lip_constant_workspace_bytes.argtypes = [i64, i64, i32, i32, i64, i64] + [i32] * 7
+    lib.lasso_conv_lip_constant.restype = i32
+    lib.lasso_conv_lip_constant.argtypes = [vp, i64, i64, i32, i32, i64, i64] + [i32] * 6 + [
+        C.POINTER(ConvLipOptions), C.POINTER(ConvLipResult), vp, sz, vp]
     lib.lasso_cd_solve.restype = i32
     lib.lasso_cd_solve.argtypes = [vp, i64, vp, i64, vp, i64, vp, i64, i64, i64, i64, i32, dbl, i32,
                                    dbl, pi32, pi32, vp, sz, vp]

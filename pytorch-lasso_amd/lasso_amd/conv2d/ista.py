@@ -7,7 +7,7 @@ import torch
 from torch.autograd.function import once_differentiable
 
 from .. import _native as nat
-from .lip_const import lip_bound_conv2d
+from .lip_const import lip_bound_conv2d, lip_constant
 
 
 def _pair(v):
@@ -202,7 +202,10 @@ def ista_conv2d(x, z0, weight, alpha=1.0, stride=1, padding=0, fast=True,
                 maxiter=10, lr='auto', tol=1e-5, verbose=False, return_info=False):
     """x [N,C,H,W], z0 [N,K,Hz,Wz], weight [K,C,kh,kw] -> z [N,K,Hz,Wz] (a new tensor;
     ``maxiter=0`` returns ``z0`` itself, ista.py:32,49).  ``lr='auto'`` uses the Toeplitz
-    bound and, like the reference, needs ``stride == 1`` (:9-15).  ``return_info``
+    bound and, like the reference, needs ``stride == 1`` (:9-15).  ``lr='exact'`` (extension)
+    takes the step ``1 / (theta + residual)`` from ``lip_constant`` of the detached weight at x's
+    size: the exact constant instead of its bound (up to 11x longer steps for dictionaries with
+    many channels), for any stride; like ``'auto'`` it is a constant of the graph.  ``return_info``
     (extension) also returns ``dict(iterations=..., last_delta=...)``.  No CPU fallback.
 
     x, z0 and weight are all float32 or all float64.  float64 tensors run in IEEE double throughout
@@ -227,6 +230,10 @@ def ista_conv2d(x, z0, weight, alpha=1.0, stride=1, padding=0, fast=True,
             lr = float(np.float32(1.0) / np.float32(Lb.item()))                         # :15 (fp32 like the tensor op)
     geom = _geometry(x, z0, weight, stride, padding)
     P = _path("ista_conv2d", x, z0, weight)
+    if isinstance(lr, str) and lr == 'exact':
+        # theta approaches lambda_max from below and some eigenvalue lies within `residual` of it: L = theta + residual
+        _, linfo = lip_constant(weight.detach(), x.shape[-2:], stride=stride, padding=padding, return_info=True)
+        lr = 1.0 / (linfo['theta'] + linfo['residual'])
     if maxiter == 0:
         return (z0, dict(iterations=0, last_delta=float('nan'))) if return_info else z0
     out_device = z0.device
