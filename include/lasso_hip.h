@@ -24,6 +24,30 @@
  *   - `stream` is a hipStream_t passed as void* (NULL = the null stream); work is
  *     enqueued on it; a call only blocks the host where a host-visible result
  *     (iteration count, stop decision) is produced -- stated per function;
+ *   - scratch and stream contract, for every function that takes (workspace_dev, workspace_bytes, stream):
+ *       * the CONTENTS of the workspace on entry are unspecified.  Every word a call waits on, counts with, indexes
+ *         with or accumulates into is written by that call, on `stream`, before it is read (a memset, or a launch in
+ *         front that clears it); the bytes may be NaN patterns, another solver's state or this function's own last
+ *         state, and the result -- tensors and every reported value -- is bit for bit the same;
+ *       * workspace_bytes equal to what the function's *_workspace_bytes answers for the same shape is sufficient, and a
+ *         larger buffer changes nothing: every region is placed from the shape, never from workspace_bytes;
+ *       * nothing outside [workspace_dev, workspace_dev + the size function's answer) and the outputs named in the
+ *         signature is written;
+ *       * every launch, memset and copy of a call is enqueued on `stream`, and only there: a call made behind other work
+ *         of that stream sees that work's results, whatever the null stream or any other stream is doing.  (The calls
+ *         that name a second stream's word -- started_word, gate_word, lasso_stream_wait_word, the lasso_mstep_pipe_*
+ *         family -- say so themselves.)
+ *     Two kinds of workspace are exceptions, by name:
+ *       * the lasso_mstep_pipe_* workspace is zeroed ONCE by the caller when it is allocated (its tickets and sequence
+ *         words count up over the steps of a loop) and carries them from call to call;
+ *       * the multi-call protocols keep state in their workspace between their calls, so its contents are unspecified
+ *         only before the FIRST call and must be left alone until the last: lasso_fista_prepare -> lasso_fista_run
+ *         (the packed dictionary and the momentum table); lasso_cd_prepare -> lasso_cd_run -> lasso_cd_finish (S, W^T,
+ *         b, the tracked code, the rows' flags and counts); an asynchronous lasso_fista_solve (LASSO_PENDING*) ->
+ *         lasso_fista_solve_deltas / _collect / _verdict / _verdict_mapped / _verdict_deferred / _finish (the
+ *         per-iteration sums and the four result words); lasso_dict_sweep_async* -> lasso_dict_sweep_count.
+ *     (tests/test_workspace_gpu.py holds every Python entry point to this on scratch filled with 0x00, 0xFF and 0x55,
+ *     with 1 MiB + 4 bytes of room, between guard bands, and on a side stream whose operands arrive late.)
  *   - return value: lasso_status (0 = ok).  No exceptions cross the boundary;
  *     lasso_hip_last_error() gives the detail string for the calling thread;
  *   - dtype: LASSO_F32; LASSO_BF16 (x, W, z0, z_out all bf16, leading dimensions in bf16
