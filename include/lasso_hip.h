@@ -72,6 +72,8 @@
  *   - the Split Bregman solver is lasso_split_bregman_solve: LASSO_F32, any n, d, any pitch, k <= 4096.
  *   - conjugate gradients are lasso_cg_solve (dense; LASSO_F32 or LASSO_F64, any n, k, any pitch) and
  *     lasso_conv_cg_solve (conv2d o conv_transpose2d + tik I; LASSO_F32, contiguous NCHW tensors).
+ *   - one dense system per batch entry: lasso_batch_chol_solve and lasso_batch_lu_solve; LASSO_F32 (d <= 1024) or
+ *     LASSO_F64 (d <= 512), any batch, any pitch.
  */
 #ifndef LASSO_HIP_H_
 #define LASSO_HIP_H_
@@ -1188,6 +1190,45 @@ size_t lasso_conv_lip_constant_workspace_bytes(int64_t K, int64_t C, int kh, int
 int lasso_conv_lip_constant(const void* w_dev, int64_t K, int64_t C, int kh, int kw, int64_t H, int64_t W, int sh, int sw,
                             int ph, int pw, int transpose, int dtype, const lasso_conv_lip_options* options,
                             lasso_conv_lip_result* result, void* workspace_dev, size_t workspace_bytes, void* stream);
+
+/* ---- one dense system per batch entry: replace batch_cholesky_solve(), lasso/linear/utils.py:43-58 ----
+ * x_i with A_i x_i = b_i for a_dev [nbatch][d][d] (system i at a_dev + i batch_stride, rows lda apart), b_dev [nbatch][d]
+ * (rows ldb apart) and x_dev [nbatch][d] (rows ldx apart); strides and leading dimensions in elements; LASSO_F32 or
+ * LASSO_F64 (csrc/batch_solve.hip).  batch_stride may be 0: one matrix for every system.  Any lda, ldb, ldx >= d and any
+ * element-aligned base pointers are taken as they are.
+ * lasso_batch_chol_solve: by Cholesky.  Only the LOWER triangle of each A_i is read (the strict upper triangle may hold
+ * anything).  A pivot that is not positive (or NaN) is replaced by 1 and recorded: result.bad_system is the lowest
+ * system that met one (-1: none, x_dev holds every solution) and result.bad_minor 1 + the index of its first such pivot;
+ * with a bad system x_dev is not a solution for it -- the reference then solves the WHOLE batch by
+ * lasso_batch_lu_solve: LU with partial pivoting (the first entry of largest magnitude) on a copy of the full matrix.  A
+ * pivot that is exactly zero is recorded the same way (the system is singular) and replaced by 1; a NaN pivot is no
+ * error: that system's x is NaN.
+ * result.tier (LASSO_BATCH_TIER_*) is the Cholesky kernel that d selects: one wave per system (d <= 32), one workgroup
+ * with the packed triangle in LDS (float d <= 256, double d <= 160), or a fixed number of workgroups with their
+ * triangles in the workspace (float d <= 1024, double d <= 512): lasso_batch_solve_tier_cap(dtype, tier) is the largest d
+ * of a tier, lasso_batch_solve_workgroups(...) the workgroups of the last one (0 for the other two).
+ * Every system is solved on its own and in a fixed order of operations: the same arguments give the same bits, and a
+ * system's solution does not depend on the rest of the batch.  The calls enqueue on `stream` only, read one record
+ * back and block for it.  lasso_batch_solve_workspace_bytes covers both routes.
+ * Refusals before any HIP call: null pointers, nbatch < 1, d < 1, a negative batch_stride or a leading dimension below
+ * d are LASSO_ERR_BAD_ARG; any other dtype and d beyond the last tier LASSO_ERR_UNSUPPORTED (the workspace query
+ * returns 0); a short workspace LASSO_ERR_WORKSPACE.  The inputs are only read; x_dev may not alias one. */
+#define LASSO_BATCH_TIER_WAVE 0
+#define LASSO_BATCH_TIER_LDS 1
+#define LASSO_BATCH_TIER_GENERAL 2
+typedef struct lasso_batch_solve_result {
+  int64_t bad_system;                     /* -1: none */
+  int32_t bad_minor, tier;
+} lasso_batch_solve_result;
+int lasso_batch_solve_tier_cap(int dtype, int tier);
+int lasso_batch_solve_workgroups(int64_t nbatch, int64_t d, int dtype);
+size_t lasso_batch_solve_workspace_bytes(int64_t nbatch, int64_t d, int dtype);
+int lasso_batch_chol_solve(const void* a_dev, int64_t batch_stride, int64_t lda, const void* b_dev, int64_t ldb, void* x_dev,
+                           int64_t ldx, int64_t nbatch, int64_t d, int dtype, lasso_batch_solve_result* result,
+                           void* workspace_dev, size_t workspace_bytes, void* stream);
+int lasso_batch_lu_solve(const void* a_dev, int64_t batch_stride, int64_t lda, const void* b_dev, int64_t ldb, void* x_dev,
+                         int64_t ldx, int64_t nbatch, int64_t d, int dtype, lasso_batch_solve_result* result,
+                         void* workspace_dev, size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -3082,6 +3082,65 @@ int lasso_interior_point_rows(const void* w_dev, int64_t ldw, const void* c_dev,
                               n, d, k, static_cast<hipStream_t>(stream));
 }
 
+// ---- one dense system per batch entry: utils.py:43-58 (csrc/batch_solve.hip) -----------------
+int lasso_batch_solve_tier_cap(int dtype, int tier) {
+  if (dtype != LASSO_F32 && dtype != LASSO_F64) return 0;
+  return batch_solve::tier_cap(dtype, tier);
+}
+
+static bool batch_solve_shape_ok(int64_t nbatch, int64_t d, int dtype) {
+  return (dtype == LASSO_F32 || dtype == LASSO_F64) && nbatch >= 1 && nbatch <= INT32_MAX && d >= 1 &&
+         d <= batch_solve::tier_cap(dtype, LASSO_BATCH_TIER_GENERAL);
+}
+
+int lasso_batch_solve_workgroups(int64_t nbatch, int64_t d, int dtype) {
+  return batch_solve_shape_ok(nbatch, d, dtype) ? batch_solve::general_workgroups(nbatch, d, dtype) : 0;
+}
+
+size_t lasso_batch_solve_workspace_bytes(int64_t nbatch, int64_t d, int dtype) {
+  return batch_solve_shape_ok(nbatch, d, dtype) ? batch_solve::workspace_bytes(nbatch, d, dtype) : 0;
+}
+
+static int check_batch_solve(const void* a_dev, int64_t batch_stride, int64_t lda, const void* b_dev, int64_t ldb,
+                             const void* x_dev, int64_t ldx, int64_t nbatch, int64_t d, int dtype,
+                             lasso_batch_solve_result* res, const void* workspace_dev, size_t workspace_bytes) {
+  if (!a_dev || !b_dev || !x_dev || !res || !workspace_dev) return fail(LASSO_ERR_BAD_ARG, "batch solve: null pointer");
+  if (nbatch < 1 || d < 1 || nbatch > INT32_MAX) return fail(LASSO_ERR_BAD_ARG, "batch solve: bad shape");
+  if (batch_stride < 0 || lda < d || ldb < d || ldx < d)
+    return fail(LASSO_ERR_BAD_ARG, "batch solve: a negative batch stride or a leading dimension below d");
+  if (dtype != LASSO_F32 && dtype != LASSO_F64)
+    return fail(LASSO_ERR_UNSUPPORTED, "batch solve: dtype %d (LASSO_F32 and LASSO_F64 are implemented)", dtype);
+  if (d > batch_solve::tier_cap(dtype, LASSO_BATCH_TIER_GENERAL))
+    return fail(LASSO_ERR_UNSUPPORTED, "batch solve: d = %lld is beyond the cap of %d for this dtype", (long long)d,
+                batch_solve::tier_cap(dtype, LASSO_BATCH_TIER_GENERAL));
+  if (workspace_bytes < lasso_batch_solve_workspace_bytes(nbatch, d, dtype))
+    return fail(LASSO_ERR_WORKSPACE, "need %zu bytes", lasso_batch_solve_workspace_bytes(nbatch, d, dtype));
+  res->bad_system = -1;
+  res->bad_minor = 0;
+  res->tier = 0;
+  return LASSO_OK;
+}
+
+int lasso_batch_chol_solve(const void* a_dev, int64_t batch_stride, int64_t lda, const void* b_dev, int64_t ldb, void* x_dev,
+                           int64_t ldx, int64_t nbatch, int64_t d, int dtype, lasso_batch_solve_result* res,
+                           void* workspace_dev, size_t workspace_bytes, void* stream) {
+  if (int s = check_batch_solve(a_dev, batch_stride, lda, b_dev, ldb, x_dev, ldx, nbatch, d, dtype, res, workspace_dev,
+                                workspace_bytes))
+    return s;
+  return batch_solve::chol(a_dev, batch_stride, lda, b_dev, ldb, x_dev, ldx, nbatch, d, dtype, res, workspace_dev,
+                           static_cast<hipStream_t>(stream));
+}
+
+int lasso_batch_lu_solve(const void* a_dev, int64_t batch_stride, int64_t lda, const void* b_dev, int64_t ldb, void* x_dev,
+                         int64_t ldx, int64_t nbatch, int64_t d, int dtype, lasso_batch_solve_result* res,
+                         void* workspace_dev, size_t workspace_bytes, void* stream) {
+  if (int s = check_batch_solve(a_dev, batch_stride, lda, b_dev, ldb, x_dev, ldx, nbatch, d, dtype, res, workspace_dev,
+                                workspace_bytes))
+    return s;
+  return batch_solve::lu(a_dev, batch_stride, lda, b_dev, ldb, x_dev, ldx, nbatch, d, dtype, res, workspace_dev,
+                         static_cast<hipStream_t>(stream));
+}
+
 // ---- conjugate gradients: conjgrad.py:13-107 (csrc/conjgrad.hip) -----------------------------
 static int check_cg_request(const lasso_cg_options* o, lasso_cg_result* res, bool dense) {
   if (!o || !res) return fail(LASSO_ERR_BAD_ARG, "null options / result");

@@ -24,6 +24,7 @@ struct lasso_cg_options;
 struct lasso_cg_result;
 struct lasso_conv_lip_options;
 struct lasso_conv_lip_result;
+struct lasso_batch_solve_result;
 
 namespace lasso {
 
@@ -625,6 +626,18 @@ size_t conv_workspace_bytes(const ConvGeom& g);
 int conv_solve(const float* w, const float* b, float* zout, const ConvGeom& g, const lasso_cg_options& o, lasso_cg_result* res,
                void* workspace, hipStream_t st);
 }  // namespace conjgrad
+
+// one dense system per batch entry (batch_solve.hip): the drivers behind lasso_batch_chol_solve / lasso_batch_lu_solve;
+// return a lasso_status
+namespace batch_solve {
+int tier_cap(int dtype, int tier);
+int general_workgroups(int64_t nbatch, int64_t d, int dtype);
+size_t workspace_bytes(int64_t nbatch, int64_t d, int dtype);
+int chol(const void* a, int64_t batch_stride, int64_t lda, const void* b, int64_t ldb, void* x, int64_t ldx, int64_t nbatch,
+         int64_t d, int dtype, lasso_batch_solve_result* res, void* workspace, hipStream_t st);
+int lu(const void* a, int64_t batch_stride, int64_t lda, const void* b, int64_t ldb, void* x, int64_t ldx, int64_t nbatch,
+       int64_t d, int dtype, lasso_batch_solve_result* res, void* workspace, hipStream_t st);
+}  // namespace batch_solve
 
 // Lanczos for the largest eigenvalue of conv_transpose2d o conv2d (conv_lanczos.hip): the driver behind
 // lasso_conv_lip_constant; g.N == 1; returns a lasso_status

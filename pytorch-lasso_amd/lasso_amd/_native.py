@@ -444,6 +444,15 @@ def _declare(lib):
     lib.lasso_conv_lip_constant.restype = i32
     lib.lasso_conv_lip_constant.argtypes = [vp, i64, i64, i32, i32, i64, i64] + [i32] * 6 + [
         C.POINTER(ConvLipOptions), C.POINTER(ConvLipResult), vp, sz, vp]
+    lib.lasso_batch_solve_tier_cap.restype = i32
+    lib.lasso_batch_solve_tier_cap.argtypes = [i32, i32]
+    lib.lasso_batch_solve_workgroups.restype = i32
+    lib.lasso_batch_solve_workgroups.argtypes = [i64, i64, i32]
+    lib.lasso_batch_solve_workspace_bytes.restype = sz
+    lib.lasso_batch_solve_workspace_bytes.argtypes = [i64, i64, i32]
+    for fn in (lib.lasso_batch_chol_solve, lib.lasso_batch_lu_solve):     # result: lasso_batch_solve_result*
+        fn.restype = i32
+        fn.argtypes = [vp, i64, i64, vp, i64, vp, i64, i64, i64, i32, vp, vp, sz, vp]
     lib.lasso_cd_solve.restype = i32
     lib.lasso_cd_solve.argtypes = [vp, i64, vp, i64, vp, i64, vp, i64, i64, i64, i64, i32, dbl, i32,
                                    dbl, pi32, pi32, vp, sz, vp]
