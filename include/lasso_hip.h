@@ -67,6 +67,7 @@
  *   - GPSR-Basic has two entry points on one driver: lasso_gpsr_solve (the dictionary as the operator) and
  *     lasso_conv_gpsr_solve (conv_transpose2d / conv2d as the operator, contiguous NCHW tensors); both LASSO_F32 only.
  *   - the orthant-wise Newton solver is lasso_own_solve: LASSO_F32, any n, d, any pitch, k <= 4096.
+ *   - the OWL-QN solver is lasso_owlqn_solve: LASSO_F32, any n, d, k, any pitch, at most 1535 held pairs.
  *   - the iterated-ridge solver is lasso_iter_ridge_solve: LASSO_F32, any n, d, any pitch, k <= 1024.
  *   - the interior-point solver is lasso_interior_point_solve: LASSO_F32, any n, any pitch, d <= 256, k <= 4096.
  *   - the Split Bregman solver is lasso_split_bregman_solve: LASSO_F32, any n, d, any pitch, k <= 4096.
@@ -937,6 +938,62 @@ int lasso_own_solve(const void* x_dev, int64_t ldx, const void* w_dev, int64_t l
                     void* z_out_dev, int64_t ldz, int64_t n, int64_t d, int64_t k, int dtype, double alpha,
                     const lasso_own_options* options, lasso_own_result* result,
                     void* workspace_dev, size_t workspace_bytes, void* stream);
+
+/* ---- OWL-QN: replaces owlqn(), lasso/nonlinear/owlqn.py:80-199, for fun(z) = 0.5 |z W^T - x|^2 ----
+ * min_z 0.5 |z W^T - x|^2 + alpha |z|_1 over the whole batch by orthant-wise L-BFGS (csrc/owlqn.hip): no k x k matrix
+ * and no cap on k.  Per iteration v = -pseudo gradient, d = project(H v, v) with H the L-BFGS operator of the held pairs
+ * (s, y) = (z - z_prev, g - g_prev), a batch-wide line search for t, z+ = project(z + t d, eta), stop once
+ * |z+ - z|_2 <= xtol; then the pair of the step is held if y.s > 1e-10 (the oldest leaves once history_size are held)
+ * and H's scaling becomes y.s / y.y.  H v is taken in the vector-free form of the two-loop recursion: one pass over the
+ * held vectors for the dots of {v, s_new, y_new} against them (fixed segments of n k, partials in double), ONE workgroup
+ * that keeps S^T Y and Y^T Y in double and runs both loops on the small vectors, one pass for
+ * d = project(gamma v + S c + Y e, v), accumulated in double and rounded once.  Every sum is folded in double in a fixed
+ * order: two solves of the same arguments give the same bits.
+ *   pairs   : the workspace holds min(history_size, maxiter - 1) pairs (never negative) and one spare slot; pass that
+ *             number to lasso_owlqn_workspace_bytes (a larger one is accepted).  The query grows with `pairs`.
+ *   options : maxiter >= 0, history_size >= 1; line_search 0 'brent' (bounded Brent on (0, 10)), 1 'backtrack' (from
+ *             the current t: ls_decay per trial, the first with f+ <= f - ls_tol <v, z+ - z> in the reference's fp32
+ *             order, at most ls_maxiter trials, then the next rung unexamined), 2 'none'.  The first iteration's t is
+ *             min(lr / |pg|_1, lr) as a float32 (and decays as one), later ones start from lr; Brent ignores it.  Bit 0
+ *             of reserved forces 128 x 128 GEMM blocks (tests); bit 1 times the three launches of the direction with
+ *             events, summed over the iterations into result->direction_ms, and counts the bytes they read and write
+ *             into result->direction_bytes (tools/bench_owlqn.py) -- both are 0 without it.
+ *   result  : n_iter, flags (LASSO_OWN_LS_NOT_CONVERGED, LASSO_OWN_NONFINITE), the objective of z0 and of z_out, and --
+ *             trace non-NULL -- host arrays of the caller: per iteration (capacity) the step t, the line-search
+ *             evaluations, the objective and |dz|_2 of the new z, the pairs held after the iteration's update, whether
+ *             that update was dropped, and H's scaling; per line-search evaluation (eval_capacity; eval_count is
+ *             written) the iteration (1-based), t and f.
+ * Refusals before any HIP call: null pointers, n < 0, d or k < 1, a leading dimension below the row length, alpha < 0,
+ * maxiter < 0, history_size < 1, ls_maxiter < 1 or an unknown line_search are LASSO_ERR_BAD_ARG; a dtype other than
+ * LASSO_F32 is LASSO_ERR_UNSUPPORTED (the workspace query returns 0); a short workspace LASSO_ERR_WORKSPACE.  n = 0
+ * writes nothing.  z0_dev is only read; z_out_dev may not alias x or W.  The call blocks: the host reads one control
+ * record per Brent evaluation, one per batch of 8 backtracking rungs and one per iteration. */
+typedef struct lasso_owlqn_options {
+  int32_t maxiter, line_search, ls_maxiter, history_size;
+  double lr, xtol, ls_tol, ls_decay;
+  int64_t reserved;
+} lasso_owlqn_options;
+typedef struct lasso_owlqn_trace {
+  int32_t capacity;                       /* iterations the arrays below hold */
+  int32_t eval_capacity;                  /* line-search evaluations eval_* hold */
+  double* t; int32_t* ls_iters; double* f; double* delta_x;
+  int32_t* pairs; int32_t* skipped; double* h_diag;
+  int32_t* eval_iter; double* eval_t; double* eval_f;
+  int64_t eval_count;                     /* out: evaluations the solve made (may exceed eval_capacity) */
+} lasso_owlqn_trace;
+typedef struct lasso_owlqn_result {
+  int32_t n_iter, flags;
+  double f0, f_final;
+  int32_t ls_failures;                    /* iterations whose backtracking ran out */
+  int32_t reserved;
+  lasso_owlqn_trace* trace;               /* nullable */
+  double direction_ms, direction_bytes;   /* bit 1 of options.reserved: device time of, and bytes moved by, the direction */
+} lasso_owlqn_result;
+size_t lasso_owlqn_workspace_bytes(int64_t n, int64_t d, int64_t k, int dtype, int64_t pairs);
+int lasso_owlqn_solve(const void* x_dev, int64_t ldx, const void* w_dev, int64_t ldw, const void* z0_dev, int64_t ldz0,
+                      void* z_out_dev, int64_t ldz, int64_t n, int64_t d, int64_t k, int dtype, double alpha,
+                      const lasso_owlqn_options* options, lasso_owlqn_result* result,
+                      void* workspace_dev, size_t workspace_bytes, void* stream);
 
 /* ---- iterated ridge: replaces iterative_ridge(), lasso/linear/solvers/iterative_ridge.py:11-141 (cg=False) ----
  * min_z 0.5 |z W^T - x|^2 + alpha |z|_1 over the whole batch by iterated ridge regression (csrc/iter_ridge.hip).  Once

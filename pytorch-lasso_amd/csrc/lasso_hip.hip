@@ -2939,6 +2939,48 @@ int lasso_own_solve(const void* x_dev, int64_t ldx, const void* w_dev, int64_t l
                     n, d, k, alpha, *o, res, workspace_dev, static_cast<hipStream_t>(stream));
 }
 
+// ---- OWL-QN: lasso/nonlinear/owlqn.py:80-199 with fun = 0.5 |z W^T - x|^2 (csrc/owlqn.hip) ----
+size_t lasso_owlqn_workspace_bytes(int64_t n, int64_t d, int64_t k, int dtype, int64_t pairs) {
+  if (dtype != LASSO_F32 || n < 0 || d <= 0 || k <= 0 || n > INT32_MAX || d > INT32_MAX || k > INT32_MAX || pairs < 0 ||
+      pairs > owlqn::kMaxPairs)
+    return 0;
+  return owlqn::workspace_bytes(n, d, k, pairs);
+}
+
+int lasso_owlqn_solve(const void* x_dev, int64_t ldx, const void* w_dev, int64_t ldw, const void* z0_dev, int64_t ldz0,
+                      void* z_out_dev, int64_t ldz, int64_t n, int64_t d, int64_t k, int dtype, double alpha,
+                      const lasso_owlqn_options* o, lasso_owlqn_result* res, void* workspace_dev, size_t workspace_bytes,
+                      void* stream) {
+  if (dtype != LASSO_F32) return fail(LASSO_ERR_UNSUPPORTED, "OWL-QN: dtype %d (fp32 tensors only)", dtype);
+  if (!o || !res) return fail(LASSO_ERR_BAD_ARG, "null options / result");
+  if (n < 0 || d <= 0 || k <= 0 || n > INT32_MAX || d > INT32_MAX || k > INT32_MAX)
+    return fail(LASSO_ERR_BAD_ARG, "bad shape");
+  if (!(alpha >= 0.0)) return fail(LASSO_ERR_BAD_ARG, "alpha < 0");
+  if (o->line_search < 0 || o->line_search > 2)
+    return fail(LASSO_ERR_BAD_ARG, "line_search must be one of 0 (brent), 1 (backtrack), 2 (none)");
+  if (o->maxiter < 0 || o->history_size < 1 || (o->line_search == 1 && o->ls_maxiter < 1))
+    return fail(LASSO_ERR_BAD_ARG, "maxiter < 0, history_size < 1 or ls_maxiter < 1");
+  if (const lasso_owlqn_trace* t = res->trace) {
+    if (t->capacity < 0 || t->eval_capacity < 0 ||
+        (t->capacity > 0 && (!t->t || !t->ls_iters || !t->f || !t->delta_x || !t->pairs || !t->skipped || !t->h_diag)) ||
+        (t->eval_capacity > 0 && (!t->eval_iter || !t->eval_t || !t->eval_f)))
+      return fail(LASSO_ERR_BAD_ARG, "trace with a null array");
+  }
+  const int pairs = owlqn::pairs_needed(*o);
+  if (pairs > owlqn::kMaxPairs)
+    return fail(LASSO_ERR_UNSUPPORTED, "OWL-QN: min(history_size, maxiter - 1) = %d > %d pairs", pairs, owlqn::kMaxPairs);
+  res->n_iter = res->flags = res->ls_failures = res->reserved = 0;
+  res->f0 = res->f_final = res->direction_ms = res->direction_bytes = 0.0;
+  if (res->trace) res->trace->eval_count = 0;
+  if (n == 0) return LASSO_OK;
+  if (!x_dev || !w_dev || !z0_dev || !z_out_dev || !workspace_dev) return fail(LASSO_ERR_BAD_ARG, "null pointer");
+  if (ldx < d || ldw < k || ldz < k || ldz0 < k) return fail(LASSO_ERR_BAD_ARG, "leading dimension too small");
+  if (workspace_bytes < lasso_owlqn_workspace_bytes(n, d, k, dtype, pairs))
+    return fail(LASSO_ERR_WORKSPACE, "need %zu bytes", lasso_owlqn_workspace_bytes(n, d, k, dtype, pairs));
+  return owlqn::solve((const float*)x_dev, ldx, (const float*)w_dev, ldw, (const float*)z0_dev, ldz0, (float*)z_out_dev, ldz,
+                      n, d, k, alpha, *o, res, workspace_dev, static_cast<hipStream_t>(stream));
+}
+
 // ---- iterated ridge: iterative_ridge.py:11-141 (csrc/iter_ridge.hip) -------------------------
 size_t lasso_iter_ridge_workspace_bytes(int64_t n, int64_t d, int64_t k, int dtype) {
   if (dtype != LASSO_F32 || n < 0 || d <= 0 || k <= 0 || k > 1024 || n > INT32_MAX || d > INT32_MAX) return 0;

@@ -14,6 +14,8 @@ struct lasso_gpsr_options;
 struct lasso_gpsr_result;
 struct lasso_own_options;
 struct lasso_own_result;
+struct lasso_owlqn_options;
+struct lasso_owlqn_result;
 struct lasso_iter_ridge_options;
 struct lasso_iter_ridge_result;
 struct lasso_interior_point_options;
@@ -584,6 +586,16 @@ int solve(const float* x, int64_t ldx, const float* w, int64_t ldw, const float*
           int64_t n, int64_t d, int64_t k, double alpha, const lasso_own_options& o, lasso_own_result* res, void* workspace,
           hipStream_t st);
 }  // namespace own
+
+// OWL-QN (owlqn.hip): the driver behind lasso_owlqn_solve; `pairs` held pairs fit the workspace; returns a lasso_status
+namespace owlqn {
+constexpr int kMaxPairs = 1535;      // held pairs at most (the coefficient kernel's small vectors live in LDS)
+int pairs_needed(const lasso_owlqn_options& o);
+size_t workspace_bytes(int64_t n, int64_t d, int64_t k, int64_t pairs);
+int solve(const float* x, int64_t ldx, const float* w, int64_t ldw, const float* z0, int64_t ldz0, float* zout, int64_t ldz,
+          int64_t n, int64_t d, int64_t k, double alpha, const lasso_owlqn_options& o, lasso_owlqn_result* res, void* workspace,
+          hipStream_t st);
+}  // namespace owlqn
 
 // iterated ridge (iter_ridge.hip): the drivers behind lasso_iter_ridge_solve / lasso_iter_ridge_rows; return a lasso_status
 namespace iter_ridge {

@@ -29,6 +29,7 @@ GPSR_ZERO_SOLUTION, GPSR_TAU_FACTOR_CHANGED, GPSR_LINESEARCH_FAILED = 1, 2, 4
 GPSR_DEBIAS_NO_NONZEROS, GPSR_DEBIAS_TOO_MANY = 8, 16
 OWN_BRENT, OWN_BACKTRACK, OWN_NONE = 0, 1, 2
 OWN_LS_NOT_CONVERGED, OWN_NONFINITE = 1, 2
+OWLQN_MAX_PAIRS = 1535                                                # most pairs lasso_owlqn_solve holds
 ITER_RIDGE_CONVERGED, ITER_RIDGE_NAN, ITER_RIDGE_MAXITER = 0, 1, 2
 INTERIOR_POINT_CONVERGED, INTERIOR_POINT_MAXITER, INTERIOR_POINT_BAD_START = 0, 1, 2
 CG_ABS_TOL, CG_REL_TOL, CG_CURV_CONVERGED, CG_CURV_NEGATIVE, CG_MAXITER = 0, 1, 2, 3, 4
@@ -93,6 +94,27 @@ class OwnResult(C.Structure):
     """lasso_own_result"""
     _fields_ = [('n_iter', C.c_int32), ('flags', C.c_int32), ('f0', C.c_double), ('f_final', C.c_double),
                 ('cholesky_info', C.c_int32), ('ls_failures', C.c_int32), ('trace', C.POINTER(OwnTrace))]
+
+
+class OwlqnOptions(C.Structure):
+    """lasso_owlqn_options"""
+    _fields_ = [(name, C.c_int32) for name in ('maxiter', 'line_search', 'ls_maxiter', 'history_size')] + \
+               [(name, C.c_double) for name in ('lr', 'xtol', 'ls_tol', 'ls_decay')] + [('reserved', C.c_int64)]
+
+
+class OwlqnTrace(C.Structure):
+    """lasso_owlqn_trace: host arrays of the caller"""
+    _pd, _pi = C.POINTER(C.c_double), C.POINTER(C.c_int32)
+    _fields_ = [('capacity', C.c_int32), ('eval_capacity', C.c_int32), ('t', _pd), ('ls_iters', _pi), ('f', _pd),
+                ('delta_x', _pd), ('pairs', _pi), ('skipped', _pi), ('h_diag', _pd), ('eval_iter', _pi), ('eval_t', _pd),
+                ('eval_f', _pd), ('eval_count', C.c_int64)]
+
+
+class OwlqnResult(C.Structure):
+    """lasso_owlqn_result"""
+    _fields_ = [('n_iter', C.c_int32), ('flags', C.c_int32), ('f0', C.c_double), ('f_final', C.c_double),
+                ('ls_failures', C.c_int32), ('reserved', C.c_int32), ('trace', C.POINTER(OwlqnTrace)),
+                ('direction_ms', C.c_double), ('direction_bytes', C.c_double)]
 
 
 class IterRidgeOptions(C.Structure):
@@ -409,6 +431,11 @@ def _declare(lib):
     lib.lasso_own_solve.restype = i32
     lib.lasso_own_solve.argtypes = [vp, i64, vp, i64, vp, i64, vp, i64, i64, i64, i64, i32, dbl,
                                     C.POINTER(OwnOptions), C.POINTER(OwnResult), vp, sz, vp]
+    lib.lasso_owlqn_workspace_bytes.restype = sz
+    lib.lasso_owlqn_workspace_bytes.argtypes = [i64, i64, i64, i32, i64]
+    lib.lasso_owlqn_solve.restype = i32
+    lib.lasso_owlqn_solve.argtypes = [vp, i64, vp, i64, vp, i64, vp, i64, i64, i64, i64, i32, dbl,
+                                      C.POINTER(OwlqnOptions), C.POINTER(OwlqnResult), vp, sz, vp]
     lib.lasso_iter_ridge_workspace_bytes.restype = sz
     lib.lasso_iter_ridge_workspace_bytes.argtypes = [i64, i64, i64, i32]
     lib.lasso_iter_ridge_solve.restype = i32
