@@ -68,6 +68,8 @@
  *     lasso_conv_gpsr_solve (conv_transpose2d / conv2d as the operator, contiguous NCHW tensors); both LASSO_F32 only.
  *   - the orthant-wise Newton solver is lasso_own_solve: LASSO_F32, any n, d, any pitch, k <= 4096.
  *   - the OWL-QN solver is lasso_owlqn_solve: LASSO_F32, any n, d, k, any pitch, at most 1535 held pairs.
+ *   - the BFGS iterated-ridge solver is lasso_irbfgs_solve: LASSO_F32, any d, any pitch, k <= 1024, a workspace of
+ *     2 n k^2 floats (lasso_irbfgs_update is its per-row update kernel on packed operands).
  *   - the iterated-ridge solver is lasso_iter_ridge_solve: LASSO_F32, any n, d, any pitch, k <= 1024.
  *   - the interior-point solver is lasso_interior_point_solve: LASSO_F32, any n, any pitch, d <= 256, k <= 4096.
  *   - the Split Bregman solver is lasso_split_bregman_solve: LASSO_F32, any n, d, any pitch, k <= 4096.
@@ -994,6 +996,86 @@ int lasso_owlqn_solve(const void* x_dev, int64_t ldx, const void* w_dev, int64_t
                       void* z_out_dev, int64_t ldz, int64_t n, int64_t d, int64_t k, int dtype, double alpha,
                       const lasso_owlqn_options* options, lasso_owlqn_result* result,
                       void* workspace_dev, size_t workspace_bytes, void* stream);
+
+/* ---- BFGS iterated ridge: replaces iterative_ridge_bfgs(), lasso/nonlinear/iterative_ridge_bfgs.py:45-140, for
+ * f(z) = 0.5 |z W^T - x|^2 ----
+ * min_z 0.5 |z W^T - x|^2 + alpha |z|_1 over the whole batch (csrc/irbfgs.hip).  Every row i keeps its own BFGS Hessian
+ * estimate B_i [k][k] (the identity at the start).  Per iteration, with g = (z W^T - x) W and mask = |z| < eps:
+ *   diag = alpha / |z|, rhs = g + diag z (both 0 where masked); the system is B_i with the masked rows and columns
+ *   zeroed and diag + tikhonov added to its diagonal; d = the batch's solutions by lasso_batch_chol_solve's kernels --
+ *   if ANY row's factorisation fails, the upper triangles are filled and the WHOLE batch is solved by the LU kernels
+ *   (the reference's 'Cholesky factorization failed. Reverting to LU decomposition...'); a singular system there is
+ *   LASSO_ERR_BAD_ARG with result.bad_row -- judged by the lowest row with a zero pivot: if its solution is finite
+ *   the system was singular; if not, a NaN operand reached it and the row stays NaN, as from the reference (that row
+ *   is read back, one more host read on this route);
+ *   t: line_search 1 = the bounded-Brent minimiser on (0, 10) of f(z - t d) + alpha |z - t d|_1 (one t for the batch;
+ *   an evaluation is one pass over [n,k], no product), 0 = min(lr / |g(z0)|_1, lr) as a float32 in iteration 1, lr later;
+ *   z+ = where(mask, z, z - t d); stop once |z+ - z|_2 <= xtol (absolute, compared as float32) or the objective is not
+ *   finite; otherwise every row's update with s = z+ - z, y = g+ - g:  valid = |y.s| > 1e-10, rho = 1 / y.s (1000 where
+ *   invalid), on the first update B *= rho (y.y) for every row, then where valid
+ *   B <- (B + rho y y^T) - (B s)(B s)^T / (s^T B s).  No update follows the iteration that stops or the last one.
+ * The update and the next iteration's system come from ONE launch per iteration (lasso_irbfgs_update is that launch
+ * on its own): B is read twice, written once, and half a matrix is written for the system.  y.s, y.y, B s and s^T B s
+ * are summed in double and rounded once; element (i, j) of the update is a symmetric function of (i, j), so B is
+ * bitwise symmetric (the reference's baddbmm(B, rho y, y^T) is not).  Every sum is folded in a fixed order: the same
+ * arguments give the same bits.
+ *   workspace: lasso_irbfgs_workspace_bytes = TWO [n][k][k] float regions (B, which the reference holds too, and the
+ *             emitted systems), six [n][k] and two [n][d] ones, W^T, the partial sums and
+ *             lasso_batch_solve_workspace_bytes(n, k).  It grows with n k^2: the caller splits a large batch.
+ *   options : maxiter >= 0, line_search 0 / 1, lr, xtol, tikhonov, eps >= 0.  Bit 1 of reserved times the update launches
+ *             with events (result.row_ms), counts the bytes of their k x k traffic (result.row_bytes) and times the
+ *             solves of the systems (result.solve_ms) -- all 0 without it (tools/bench_irbfgs.py); every other bit must be 0.
+ *   result  : n_iter, flags (LASSO_IRBFGS_*), the objective of z0 and of z_out, lu_count = iterations that took the
+ *             LU route, and -- trace non-NULL -- host arrays of the caller: per iteration (capacity) t, the Brent
+ *             evaluations, the objective and |dz|_2 of the new z, the rows whose update was invalid (-1: no update
+ *             followed), whether the LU route ran; per Brent evaluation (eval_capacity; eval_count is written) the
+ *             iteration (1-based), t and f.
+ * Refusals before any HIP call: null pointers, n < 0, d or k < 1, a leading dimension below the row length, alpha < 0,
+ * a negative maxiter, lr, xtol, tikhonov or eps, an unknown line_search or reserved bit are LASSO_ERR_BAD_ARG; a dtype
+ * other than LASSO_F32 and k > lasso_batch_solve_tier_cap(LASSO_F32, LASSO_BATCH_TIER_GENERAL) = 1024 are
+ * LASSO_ERR_UNSUPPORTED (the workspace query returns 0); a short workspace LASSO_ERR_WORKSPACE.  n = 0 writes nothing.
+ * z0_dev is only read; z_out_dev may not alias x or W.  The call enqueues on `stream` only and blocks: the host reads
+ * one record per solve of the systems (two on the LU route), one per Brent evaluation and one per iteration.
+ *
+ * lasso_irbfgs_update: the row kernel alone, on packed operands: b_dev [n][k][k], x_dev / g_dev [n][k] (the new iterate
+ * and its gradient, read), x_prev_dev / g_prev_dev [n][k] (read, then overwritten with x and g), system_dev [n][k][k]
+ * (out: the lower triangles and diagonals of the masked, loaded systems of x; the strict upper triangles are not
+ * defined), rhs_dev [n][k] and valid_dev [n] int32 (out).  mode 0: B = I is written, no update; 1: the update (with
+ * `first` != 0 the first update's scaling); 2: B is used as it is.  max_workgroups > 0 bounds the launch's grid (rows are
+ * strided over it), 0 = the default.  Needs no workspace; blocks until the launch has finished.  Refusals as above
+ * (mode outside 0..2 is LASSO_ERR_BAD_ARG). */
+#define LASSO_IRBFGS_CONVERGED 1
+#define LASSO_IRBFGS_NONFINITE 2
+typedef struct lasso_irbfgs_options {
+  int32_t maxiter, line_search;
+  double lr, xtol, tikhonov, eps;
+  int64_t reserved;
+} lasso_irbfgs_options;
+typedef struct lasso_irbfgs_trace {
+  int32_t capacity;                       /* iterations the arrays below hold */
+  int32_t eval_capacity;                  /* Brent evaluations eval_* hold */
+  double* t; int32_t* ls_iters; double* f; double* delta_x;
+  int32_t* invalid_rows; int32_t* lu;
+  int32_t* eval_iter; double* eval_t; double* eval_f;
+  int64_t eval_count;                     /* out: evaluations the solve made (may exceed eval_capacity) */
+} lasso_irbfgs_trace;
+typedef struct lasso_irbfgs_result {
+  int32_t n_iter, flags;
+  double f0, f_final;
+  int32_t lu_count, reserved;
+  int64_t bad_row;                        /* -1, or the lowest row whose system was singular on the LU route */
+  lasso_irbfgs_trace* trace;              /* nullable */
+  double row_ms, row_bytes;               /* bit 1 of options.reserved: device time and k x k bytes of the update launches */
+  double solve_ms;                        /* ... and the time in the solves of the systems, their host reads included */
+} lasso_irbfgs_result;
+size_t lasso_irbfgs_workspace_bytes(int64_t n, int64_t d, int64_t k, int dtype);
+int lasso_irbfgs_solve(const void* x_dev, int64_t ldx, const void* w_dev, int64_t ldw, const void* z0_dev, int64_t ldz0,
+                       void* z_out_dev, int64_t ldz, int64_t n, int64_t d, int64_t k, int dtype, double alpha,
+                       const lasso_irbfgs_options* options, lasso_irbfgs_result* result,
+                       void* workspace_dev, size_t workspace_bytes, void* stream);
+int lasso_irbfgs_update(void* b_dev, const void* x_dev, const void* g_dev, void* x_prev_dev, void* g_prev_dev,
+                        void* system_dev, void* rhs_dev, int32_t* valid_dev, int64_t n, int64_t k, int dtype, double alpha,
+                        double tikhonov, double eps, int mode, int first, int max_workgroups, void* stream);
 
 /* ---- iterated ridge: replaces iterative_ridge(), lasso/linear/solvers/iterative_ridge.py:11-141 (cg=False) ----
  * min_z 0.5 |z W^T - x|^2 + alpha |z|_1 over the whole batch by iterated ridge regression (csrc/iter_ridge.hip).  Once

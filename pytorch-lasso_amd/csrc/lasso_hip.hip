@@ -2981,6 +2981,65 @@ int lasso_owlqn_solve(const void* x_dev, int64_t ldx, const void* w_dev, int64_t
                       n, d, k, alpha, *o, res, workspace_dev, static_cast<hipStream_t>(stream));
 }
 
+// ---- BFGS iterated ridge: lasso/nonlinear/iterative_ridge_bfgs.py:45-140 with f = 0.5 |z W^T - x|^2 (csrc/irbfgs.hip) ----
+size_t lasso_irbfgs_workspace_bytes(int64_t n, int64_t d, int64_t k, int dtype) {
+  if (dtype != LASSO_F32 || n < 0 || d <= 0 || k <= 0 || n > INT32_MAX || d > INT32_MAX ||
+      k > batch_solve::tier_cap(LASSO_F32, LASSO_BATCH_TIER_GENERAL))
+    return 0;
+  return irbfgs::workspace_bytes(n, d, k);
+}
+
+int lasso_irbfgs_solve(const void* x_dev, int64_t ldx, const void* w_dev, int64_t ldw, const void* z0_dev, int64_t ldz0,
+                       void* z_out_dev, int64_t ldz, int64_t n, int64_t d, int64_t k, int dtype, double alpha,
+                       const lasso_irbfgs_options* o, lasso_irbfgs_result* res, void* workspace_dev, size_t workspace_bytes,
+                       void* stream) {
+  if (dtype != LASSO_F32) return fail(LASSO_ERR_UNSUPPORTED, "iterative_ridge_bfgs: dtype %d (fp32 tensors only)", dtype);
+  if (!o || !res) return fail(LASSO_ERR_BAD_ARG, "null options / result");
+  if (n < 0 || d <= 0 || k <= 0 || n > INT32_MAX || d > INT32_MAX || k > INT32_MAX)
+    return fail(LASSO_ERR_BAD_ARG, "bad shape");
+  const int cap = batch_solve::tier_cap(LASSO_F32, LASSO_BATCH_TIER_GENERAL);
+  if (k > cap) return fail(LASSO_ERR_UNSUPPORTED, "iterative_ridge_bfgs: k=%lld > %d", (long long)k, cap);
+  if (!(alpha >= 0.0)) return fail(LASSO_ERR_BAD_ARG, "alpha < 0");
+  if ((o->reserved & ~(int64_t)2) != 0) return fail(LASSO_ERR_BAD_ARG, "iterative_ridge_bfgs: unknown bit of reserved");
+  if (o->maxiter < 0 || o->line_search < 0 || o->line_search > 1 || !(o->lr >= 0.0) || !(o->xtol >= 0.0) ||
+      !(o->tikhonov >= 0.0) || !(o->eps >= 0.0))
+    return fail(LASSO_ERR_BAD_ARG, "maxiter, lr, xtol, tikhonov, eps >= 0 and line_search 0 / 1 are required");
+  if (const lasso_irbfgs_trace* t = res->trace) {
+    if (t->capacity < 0 || t->eval_capacity < 0 ||
+        (t->capacity > 0 && (!t->t || !t->ls_iters || !t->f || !t->delta_x || !t->invalid_rows || !t->lu)) ||
+        (t->eval_capacity > 0 && (!t->eval_iter || !t->eval_t || !t->eval_f)))
+      return fail(LASSO_ERR_BAD_ARG, "trace with a null array");
+  }
+  res->n_iter = res->flags = res->lu_count = res->reserved = 0;
+  res->f0 = res->f_final = res->row_ms = res->row_bytes = res->solve_ms = 0.0;
+  res->bad_row = -1;
+  if (res->trace) res->trace->eval_count = 0;
+  if (n == 0) return LASSO_OK;
+  if (!x_dev || !w_dev || !z0_dev || !z_out_dev || !workspace_dev) return fail(LASSO_ERR_BAD_ARG, "null pointer");
+  if (ldx < d || ldw < k || ldz < k || ldz0 < k) return fail(LASSO_ERR_BAD_ARG, "leading dimension too small");
+  if (workspace_bytes < lasso_irbfgs_workspace_bytes(n, d, k, dtype))
+    return fail(LASSO_ERR_WORKSPACE, "need %zu bytes", lasso_irbfgs_workspace_bytes(n, d, k, dtype));
+  return irbfgs::solve((const float*)x_dev, ldx, (const float*)w_dev, ldw, (const float*)z0_dev, ldz0, (float*)z_out_dev, ldz,
+                       n, d, k, alpha, *o, res, workspace_dev, static_cast<hipStream_t>(stream));
+}
+
+int lasso_irbfgs_update(void* b_dev, const void* x_dev, const void* g_dev, void* x_prev_dev, void* g_prev_dev,
+                        void* system_dev, void* rhs_dev, int32_t* valid_dev, int64_t n, int64_t k, int dtype, double alpha,
+                        double tikhonov, double eps, int mode, int first, int max_workgroups, void* stream) {
+  if (dtype != LASSO_F32) return fail(LASSO_ERR_UNSUPPORTED, "iterative_ridge_bfgs: dtype %d (fp32 tensors only)", dtype);
+  if (n < 0 || k <= 0 || n > INT32_MAX || k > INT32_MAX) return fail(LASSO_ERR_BAD_ARG, "bad shape");
+  const int cap = batch_solve::tier_cap(LASSO_F32, LASSO_BATCH_TIER_GENERAL);
+  if (k > cap) return fail(LASSO_ERR_UNSUPPORTED, "iterative_ridge_bfgs: k=%lld > %d", (long long)k, cap);
+  if (!(alpha >= 0.0) || !(tikhonov >= 0.0) || !(eps >= 0.0)) return fail(LASSO_ERR_BAD_ARG, "alpha, tikhonov, eps >= 0 are required");
+  if (mode < 0 || mode > 2 || max_workgroups < 0) return fail(LASSO_ERR_BAD_ARG, "mode must be 0, 1 or 2 and max_workgroups >= 0");
+  if (n == 0) return LASSO_OK;
+  if (!b_dev || !x_dev || !g_dev || !x_prev_dev || !g_prev_dev || !system_dev || !rhs_dev || !valid_dev)
+    return fail(LASSO_ERR_BAD_ARG, "null pointer");
+  return irbfgs::update((float*)b_dev, (const float*)x_dev, (const float*)g_dev, (float*)x_prev_dev, (float*)g_prev_dev,
+                        (float*)system_dev, (float*)rhs_dev, valid_dev, n, k, alpha, tikhonov, eps, mode, first, max_workgroups,
+                        static_cast<hipStream_t>(stream));
+}
+
 // ---- iterated ridge: iterative_ridge.py:11-141 (csrc/iter_ridge.hip) -------------------------
 size_t lasso_iter_ridge_workspace_bytes(int64_t n, int64_t d, int64_t k, int dtype) {
   if (dtype != LASSO_F32 || n < 0 || d <= 0 || k <= 0 || k > 1024 || n > INT32_MAX || d > INT32_MAX) return 0;

@@ -16,6 +16,8 @@ struct lasso_own_options;
 struct lasso_own_result;
 struct lasso_owlqn_options;
 struct lasso_owlqn_result;
+struct lasso_irbfgs_options;
+struct lasso_irbfgs_result;
 struct lasso_iter_ridge_options;
 struct lasso_iter_ridge_result;
 struct lasso_interior_point_options;
@@ -596,6 +598,18 @@ int solve(const float* x, int64_t ldx, const float* w, int64_t ldw, const float*
           int64_t n, int64_t d, int64_t k, double alpha, const lasso_owlqn_options& o, lasso_owlqn_result* res, void* workspace,
           hipStream_t st);
 }  // namespace owlqn
+
+// BFGS iterated ridge (irbfgs.hip): the drivers behind lasso_irbfgs_solve / lasso_irbfgs_update; return a lasso_status
+namespace irbfgs {
+size_t workspace_bytes(int64_t n, int64_t d, int64_t k);
+int solve(const float* x, int64_t ldx, const float* w, int64_t ldw, const float* z0, int64_t ldz0, float* zout, int64_t ldz,
+          int64_t n, int64_t d, int64_t k, double alpha, const lasso_irbfgs_options& o, lasso_irbfgs_result* res, void* workspace,
+          hipStream_t st);
+// mode 0: B = I; 1: the update (first: with the first update's scaling); 2: B as it is.  x_prev / g_prev become x / g
+int update(float* B, const float* x, const float* g, float* x_prev, float* g_prev, float* sys, float* rhs, int32_t* valid,
+           int64_t n, int64_t k, double alpha, double tikhonov, double eps, int mode, int first, int max_workgroups,
+           hipStream_t st);
+}  // namespace irbfgs
 
 // iterated ridge (iter_ridge.hip): the drivers behind lasso_iter_ridge_solve / lasso_iter_ridge_rows; return a lasso_status
 namespace iter_ridge {

@@ -30,6 +30,9 @@ GPSR_DEBIAS_NO_NONZEROS, GPSR_DEBIAS_TOO_MANY = 8, 16
 OWN_BRENT, OWN_BACKTRACK, OWN_NONE = 0, 1, 2
 OWN_LS_NOT_CONVERGED, OWN_NONFINITE = 1, 2
 OWLQN_MAX_PAIRS = 1535                                                # most pairs lasso_owlqn_solve holds
+IRBFGS_CONVERGED, IRBFGS_NONFINITE = 1, 2
+IRBFGS_MAX_K = 1024                                                   # lasso_batch_solve_tier_cap(LASSO_F32, general)
+IRBFGS_TIME_ROWS = 2                                                  # bit 1 of lasso_irbfgs_options.reserved
 ITER_RIDGE_CONVERGED, ITER_RIDGE_NAN, ITER_RIDGE_MAXITER = 0, 1, 2
 INTERIOR_POINT_CONVERGED, INTERIOR_POINT_MAXITER, INTERIOR_POINT_BAD_START = 0, 1, 2
 CG_ABS_TOL, CG_REL_TOL, CG_CURV_CONVERGED, CG_CURV_NEGATIVE, CG_MAXITER = 0, 1, 2, 3, 4
@@ -115,6 +118,28 @@ class OwlqnResult(C.Structure):
     _fields_ = [('n_iter', C.c_int32), ('flags', C.c_int32), ('f0', C.c_double), ('f_final', C.c_double),
                 ('ls_failures', C.c_int32), ('reserved', C.c_int32), ('trace', C.POINTER(OwlqnTrace)),
                 ('direction_ms', C.c_double), ('direction_bytes', C.c_double)]
+
+
+class IrbfgsOptions(C.Structure):
+    """lasso_irbfgs_options"""
+    _fields_ = [('maxiter', C.c_int32), ('line_search', C.c_int32), ('lr', C.c_double), ('xtol', C.c_double),
+                ('tikhonov', C.c_double), ('eps', C.c_double), ('reserved', C.c_int64)]
+
+
+class IrbfgsTrace(C.Structure):
+    """lasso_irbfgs_trace: host arrays of the caller"""
+    _pd, _pi = C.POINTER(C.c_double), C.POINTER(C.c_int32)
+    _fields_ = [('capacity', C.c_int32), ('eval_capacity', C.c_int32), ('t', _pd), ('ls_iters', _pi), ('f', _pd),
+                ('delta_x', _pd), ('invalid_rows', _pi), ('lu', _pi), ('eval_iter', _pi), ('eval_t', _pd),
+                ('eval_f', _pd), ('eval_count', C.c_int64)]
+
+
+class IrbfgsResult(C.Structure):
+    """lasso_irbfgs_result"""
+    _fields_ = [('n_iter', C.c_int32), ('flags', C.c_int32), ('f0', C.c_double), ('f_final', C.c_double),
+                ('lu_count', C.c_int32), ('reserved', C.c_int32), ('bad_row', C.c_int64),
+                ('trace', C.POINTER(IrbfgsTrace)), ('row_ms', C.c_double), ('row_bytes', C.c_double),
+                ('solve_ms', C.c_double)]
 
 
 class IterRidgeOptions(C.Structure):
@@ -436,6 +461,13 @@ def _declare(lib):
     lib.lasso_owlqn_solve.restype = i32
     lib.lasso_owlqn_solve.argtypes = [vp, i64, vp, i64, vp, i64, vp, i64, i64, i64, i64, i32, dbl,
                                       C.POINTER(OwlqnOptions), C.POINTER(OwlqnResult), vp, sz, vp]
+    lib.lasso_irbfgs_workspace_bytes.restype = sz
+    lib.lasso_irbfgs_workspace_bytes.argtypes = [i64, i64, i64, i32]
+    lib.lasso_irbfgs_solve.restype = i32
+    lib.lasso_irbfgs_solve.argtypes = [vp, i64, vp, i64, vp, i64, vp, i64, i64, i64, i64, i32, dbl,
+                                       C.POINTER(IrbfgsOptions), C.POINTER(IrbfgsResult), vp, sz, vp]
+    lib.lasso_irbfgs_update.restype = i32
+    lib.lasso_irbfgs_update.argtypes = [vp] * 8 + [i64, i64, i32, dbl, dbl, dbl, i32, i32, i32, vp]
     lib.lasso_iter_ridge_workspace_bytes.restype = sz
     lib.lasso_iter_ridge_workspace_bytes.argtypes = [i64, i64, i64, i32]
     lib.lasso_iter_ridge_solve.restype = i32
