@@ -67,7 +67,8 @@
  *   - GPSR-Basic has two entry points on one driver: lasso_gpsr_solve (the dictionary as the operator) and
  *     lasso_conv_gpsr_solve (conv_transpose2d / conv2d as the operator, contiguous NCHW tensors); both LASSO_F32 only.
  *   - the orthant-wise Newton solver is lasso_own_solve: LASSO_F32, any n, d, any pitch, k <= 4096.
- *   - the OWL-QN solver is lasso_owlqn_solve: LASSO_F32, any n, d, k, any pitch, at most 1535 held pairs.
+ *   - the OWL-QN solver is lasso_owlqn_solve: LASSO_F32, any n, d, k, any pitch, at most 1535 held pairs;
+ *     lasso_owlqn_glm_solve is the same solver on the logistic loss (LASSO_GLM_BERNOULLI), same limits and workspace.
  *   - the BFGS iterated-ridge solver is lasso_irbfgs_solve: LASSO_F32, any d, any pitch, k <= 1024, a workspace of
  *     2 n k^2 floats (lasso_irbfgs_update is its per-row update kernel on packed operands).
  *   - the iterated-ridge solver is lasso_iter_ridge_solve: LASSO_F32, any n, d, any pitch, k <= 1024.
@@ -996,6 +997,23 @@ int lasso_owlqn_solve(const void* x_dev, int64_t ldx, const void* w_dev, int64_t
                       void* z_out_dev, int64_t ldz, int64_t n, int64_t d, int64_t k, int dtype, double alpha,
                       const lasso_owlqn_options* options, lasso_owlqn_result* result,
                       void* workspace_dev, size_t workspace_bytes, void* stream);
+
+/* ---- OWL-QN on a generalised-linear objective: owlqn() with fun(z) = sum loss(u, x), u = z W^T ----
+ * lasso_owlqn_solve with the objective's family as one more argument; everything else -- the arguments, the options,
+ * result and trace structs, the refusals, the direction, the ring, the line searches, the one control record per
+ * decision -- is lasso_owlqn_solve's.  The workspace comes from lasso_owlqn_workspace_bytes: the layout is identical
+ * (the buffer that holds the residual holds r = d loss / d u).
+ *   LASSO_GLM_BERNOULLI  loss = softplus(u) - x u, torch's binary_cross_entropy_with_logits(u, x, reduction='sum'); x is
+ *                        any real target (0/1 or soft), not validated.  Evaluated without exp(+|u|):
+ *                          e = expf(-|u|), loss = max(u, 0) - x u + log1pf(e), r = (u >= 0 ? 1 : e) / (1 + e) - x,
+ *                        finite for every finite u.  The objective is the double fold of the per-element float32 losses
+ *                        plus alpha |z|_1; the backtracking test sees it rounded to float32, as the reference computes it.
+ * Any other family is LASSO_ERR_UNSUPPORTED (before any HIP call). */
+#define LASSO_GLM_BERNOULLI 1             /* family: logistic loss of logits u against targets x */
+int lasso_owlqn_glm_solve(const void* x_dev, int64_t ldx, const void* w_dev, int64_t ldw, const void* z0_dev, int64_t ldz0,
+                          void* z_out_dev, int64_t ldz, int64_t n, int64_t d, int64_t k, int dtype, double alpha,
+                          int family, const lasso_owlqn_options* options, lasso_owlqn_result* result,
+                          void* workspace_dev, size_t workspace_bytes, void* stream);
 
 /* ---- BFGS iterated ridge: replaces iterative_ridge_bfgs(), lasso/nonlinear/iterative_ridge_bfgs.py:45-140, for
  * f(z) = 0.5 |z W^T - x|^2 ----

@@ -2947,10 +2947,11 @@ size_t lasso_owlqn_workspace_bytes(int64_t n, int64_t d, int64_t k, int dtype, i
   return owlqn::workspace_bytes(n, d, k, pairs);
 }
 
-int lasso_owlqn_solve(const void* x_dev, int64_t ldx, const void* w_dev, int64_t ldw, const void* z0_dev, int64_t ldz0,
-                      void* z_out_dev, int64_t ldz, int64_t n, int64_t d, int64_t k, int dtype, double alpha,
-                      const lasso_owlqn_options* o, lasso_owlqn_result* res, void* workspace_dev, size_t workspace_bytes,
-                      void* stream) {
+// both OWL-QN entry points: the refusals, then the driver on the objective's family
+static int owlqn_entry(const void* x_dev, int64_t ldx, const void* w_dev, int64_t ldw, const void* z0_dev, int64_t ldz0,
+                       void* z_out_dev, int64_t ldz, int64_t n, int64_t d, int64_t k, int dtype, double alpha, int family,
+                       const lasso_owlqn_options* o, lasso_owlqn_result* res, void* workspace_dev, size_t workspace_bytes,
+                       void* stream) {
   if (dtype != LASSO_F32) return fail(LASSO_ERR_UNSUPPORTED, "OWL-QN: dtype %d (fp32 tensors only)", dtype);
   if (!o || !res) return fail(LASSO_ERR_BAD_ARG, "null options / result");
   if (n < 0 || d <= 0 || k <= 0 || n > INT32_MAX || d > INT32_MAX || k > INT32_MAX)
@@ -2978,7 +2979,26 @@ int lasso_owlqn_solve(const void* x_dev, int64_t ldx, const void* w_dev, int64_t
   if (workspace_bytes < lasso_owlqn_workspace_bytes(n, d, k, dtype, pairs))
     return fail(LASSO_ERR_WORKSPACE, "need %zu bytes", lasso_owlqn_workspace_bytes(n, d, k, dtype, pairs));
   return owlqn::solve((const float*)x_dev, ldx, (const float*)w_dev, ldw, (const float*)z0_dev, ldz0, (float*)z_out_dev, ldz,
-                      n, d, k, alpha, *o, res, workspace_dev, static_cast<hipStream_t>(stream));
+                      n, d, k, alpha, family, *o, res, workspace_dev, static_cast<hipStream_t>(stream));
+}
+
+int lasso_owlqn_solve(const void* x_dev, int64_t ldx, const void* w_dev, int64_t ldw, const void* z0_dev, int64_t ldz0,
+                      void* z_out_dev, int64_t ldz, int64_t n, int64_t d, int64_t k, int dtype, double alpha,
+                      const lasso_owlqn_options* o, lasso_owlqn_result* res, void* workspace_dev, size_t workspace_bytes,
+                      void* stream) {
+  return owlqn_entry(x_dev, ldx, w_dev, ldw, z0_dev, ldz0, z_out_dev, ldz, n, d, k, dtype, alpha, owlqn::kFamilyRss, o, res,
+                     workspace_dev, workspace_bytes, stream);
+}
+
+// ---- OWL-QN on a generalised-linear objective: fun = sum loss(z W^T, x) (csrc/owlqn.hip's link epilogues) ----
+int lasso_owlqn_glm_solve(const void* x_dev, int64_t ldx, const void* w_dev, int64_t ldw, const void* z0_dev, int64_t ldz0,
+                          void* z_out_dev, int64_t ldz, int64_t n, int64_t d, int64_t k, int dtype, double alpha, int family,
+                          const lasso_owlqn_options* o, lasso_owlqn_result* res, void* workspace_dev, size_t workspace_bytes,
+                          void* stream) {
+  if (family != LASSO_GLM_BERNOULLI)
+    return fail(LASSO_ERR_UNSUPPORTED, "OWL-QN: family %d (LASSO_GLM_BERNOULLI = %d only)", family, LASSO_GLM_BERNOULLI);
+  return owlqn_entry(x_dev, ldx, w_dev, ldw, z0_dev, ldz0, z_out_dev, ldz, n, d, k, dtype, alpha, family, o, res, workspace_dev,
+                     workspace_bytes, stream);
 }
 
 // ---- BFGS iterated ridge: lasso/nonlinear/iterative_ridge_bfgs.py:45-140 with f = 0.5 |z W^T - x|^2 (csrc/irbfgs.hip) ----

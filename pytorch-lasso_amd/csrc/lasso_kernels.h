@@ -589,14 +589,16 @@ int solve(const float* x, int64_t ldx, const float* w, int64_t ldw, const float*
           hipStream_t st);
 }  // namespace own
 
-// OWL-QN (owlqn.hip): the driver behind lasso_owlqn_solve; `pairs` held pairs fit the workspace; returns a lasso_status
+// OWL-QN (owlqn.hip): the driver behind lasso_owlqn_solve and lasso_owlqn_glm_solve; `pairs` held pairs fit the workspace;
+// family 0: fun = 0.5 |z W^T - x|^2, LASSO_GLM_BERNOULLI: the logistic loss of u = z W^T; returns a lasso_status
 namespace owlqn {
 constexpr int kMaxPairs = 1535;      // held pairs at most (the coefficient kernel's small vectors live in LDS)
+constexpr int kFamilyRss = 0;
 int pairs_needed(const lasso_owlqn_options& o);
 size_t workspace_bytes(int64_t n, int64_t d, int64_t k, int64_t pairs);
 int solve(const float* x, int64_t ldx, const float* w, int64_t ldw, const float* z0, int64_t ldz0, float* zout, int64_t ldz,
-          int64_t n, int64_t d, int64_t k, double alpha, const lasso_owlqn_options& o, lasso_owlqn_result* res, void* workspace,
-          hipStream_t st);
+          int64_t n, int64_t d, int64_t k, double alpha, int family, const lasso_owlqn_options& o, lasso_owlqn_result* res,
+          void* workspace, hipStream_t st);
 }  // namespace owlqn
 
 // BFGS iterated ridge (irbfgs.hip): the drivers behind lasso_irbfgs_solve / lasso_irbfgs_update; return a lasso_status

@@ -149,12 +149,12 @@ __global__ __launch_bounds__(256) void trial_kernel(const float* __restrict__ Z,
   block_fold<3, 0>(s, nomax, red, part + ((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * kPart);
 }
 
-// the objective of `count` rungs (product != 0: part_r holds |z_t W^T - x|^2) and, for a backtracking, the
-// sufficient-decrease test in the reference's order (orthant_wise_newton.py:23): the first rung with
+// the objective of `count` rungs (product != 0: part_r holds the candidates' loss sums -- |z_t W^T - x|^2 with scale 0.5,
+// a generalised-linear loss with scale 1, which multiplies exactly) and, for a backtracking, the sufficient-decrease test in the reference's order (orthant_wise_newton.py:23): the first rung with
 // f+ <= f - tol <v, z+ - z> is accepted.  product == 0: the one candidate is the step the search chose -- accepted.
 __global__ __launch_bounds__(256) void decide_kernel(const double* __restrict__ part_t, int nb_t, const double* __restrict__ part_r,
-                                                     int nb_r, int count, int product, int backtrack, double alpha, float tol,
-                                                     Ctl* __restrict__ ctl) {
+                                                     int nb_r, int count, int product, int backtrack, double scale, double alpha,
+                                                     float tol, Ctl* __restrict__ ctl) {
   __shared__ double red[256], t[kPart], r[kPart];
   if (threadIdx.x == 0) {
     ctl->accept = product ? -1 : 0;
@@ -169,9 +169,9 @@ __global__ __launch_bounds__(256) void decide_kernel(const double* __restrict__ 
       if (!product) {
         ctl->dz2 = t[2];
       } else {
-        ctl->ft[j] = 0.5 * r[0] + alpha * t[0];
+        ctl->ft[j] = scale * r[0] + alpha * t[0];
         if (backtrack) {
-          const float fnew = __fadd_rn(__fmul_rn(0.5f, (float)r[0]), __fmul_rn((float)alpha, (float)t[0]));
+          const float fnew = __fadd_rn(__fmul_rn((float)scale, (float)r[0]), __fmul_rn((float)alpha, (float)t[0]));
           const float bound = __fsub_rn(ctl->f32, __fmul_rn(tol, (float)t[1]));
           ctl->fnew[j] = fnew;
           ctl->bound[j] = bound;

@@ -1,6 +1,9 @@
 // OWL-QN (the reference's lasso/nonlinear/owlqn.py with fun(z) = 0.5 |z W^T - x|^2) on the fp32 MFMA GEMM: the driver
 // behind lasso_owlqn_solve.  min 0.5 |z W^T - x|^2 + alpha |z|_1 over the whole batch with the L-BFGS operator of the
 // last `history` pairs (s, y) = (z - z_prev, g - g_prev) in place of a Hessian: no k x k matrix, no cap on k.
+// The same driver is behind lasso_owlqn_glm_solve, where fun(z) = sum softplus(u) - x u with u = z W^T (the Bernoulli
+// family): LinkEpi<true> / LinkEpi<false> stand in for EPI_RESID / EPI_TRIAL, the buffer of resid holds
+// r = sigmoid(u) - x, the objective's scale is 1 instead of 0.5, and everything else below is shared.
 //
 // Products (solver_common.hpp's gemm_kernel with an epilogue):
 //   EPI_RESID  resid = z W^T - x stored, block partials of |resid|^2                                 (orthant_common.hpp)
@@ -147,18 +150,66 @@ struct GradEpi {
   }
 };
 
-// f = 0.5 |resid|^2 + alpha |z|_1 of the current z, |pg|_1, and the candidate pair's y.s, y.y and verdict, from the
-// partials RESID and GradEpi left
+// The Bernoulli family's link on the accumulators u = z W^T against the targets x (the counterparts of EPI_RESID and
+// EPI_TRIAL): loss = softplus(u) - x u, r = d loss / d u = sigmoid(u) - x, both from e = exp(-|u|) <= 1 alone -- no
+// exp(+|u|), so |u| > 88.7 stays finite (loss -> max(u, 0) - x u, r -> {0, 1} - x).  STORE: r goes to Out (ld nn);
+// block partials {sum of the float32 losses, added in double}.  A lane outside the tile holds u = 0, worth log 2: it is
+// left out of the sum, and its r = 0.5 - x is dropped by the buffer bounds like every store outside the operand.
+template <bool STORE>
+struct LinkEpi {
+  const float* X; int64_t ldx;        // the targets x [m][nn]
+  float* Out;                         // STORE: r (ld nn)
+  int64_t a_stride;                   // !STORE: per rung offset of the A operand
+  double* part;                       // [rungs][blocks][kPart]
+
+  template <int BM, int BN>
+  __device__ __forceinline__ void run(const Tile<BM, BN>& t, f32x4 (&acc)[BM / 32][BN / 32], char* smem) const {
+    constexpr int MI = BM / 32, NJ = BN / 32;
+    const int64_t ldn = t.nn;
+    const __amdgpu_buffer_rsrc_t xrs = t.rsrc(X, ldx);
+    __amdgpu_buffer_rsrc_t ors = xrs;
+    if constexpr (STORE) ors = t.rsrc(Out, ldn);
+    double s[1] = {0.0};
+#pragma unroll
+    for (int mi = 0; mi < MI; ++mi) {
+      unsigned o[NJ][4];
+      t.offs(mi, ldn, o);
+      float x[NJ][4];
+#pragma unroll
+      for (int nj = 0; nj < NJ; ++nj)
+#pragma unroll
+        for (int rg = 0; rg < 4; ++rg) x[nj][rg] = t.ld32(xrs, t.off(mi, nj, rg, ldx));
+#pragma unroll
+      for (int nj = 0; nj < NJ; ++nj)
+#pragma unroll
+        for (int rg = 0; rg < 4; ++rg) {
+          const float u = acc[mi][nj][rg], xx = x[nj][rg];
+          const float e = expf(-fabsf(u));
+          const float loss = __fadd_rn(__fsub_rn(fmaxf(u, 0.0f), __fmul_rn(xx, u)), log1pf(e));
+          if (t.inside(o[nj][rg])) s[0] += (double)loss;
+          if constexpr (STORE) {
+            const float r = __fsub_rn(__fdiv_rn(u >= 0.0f ? 1.0f : e, __fadd_rn(1.0f, e)), xx);
+            t.st32(r, ors, o[nj][rg]);
+          }
+        }
+    }
+    float nomax[1] = {0.0f};
+    block_fold<1, 0>(s, nomax, reinterpret_cast<double*>(smem), t.partial(part));
+  }
+};
+
+// f = scale * (the loss sum RESID or the link left: 0.5 |resid|^2, or 1 x the Bernoulli loss) + alpha |z|_1 of the
+// current z, |pg|_1, and the candidate pair's y.s, y.y and verdict, from the partials of the two products
 __global__ __launch_bounds__(256) void eval_kernel(const double* __restrict__ part_r, int nb_r, const double* __restrict__ part_g,
-                                                   int nb_g, double alpha, QnCtl* __restrict__ ctl) {
+                                                   int nb_g, double scale, double alpha, QnCtl* __restrict__ ctl) {
   __shared__ double red[256], a[kPart], b[kPart];
   fold_partials(part_r, nb_r, 1, 0, red, a);
   fold_partials(part_g, nb_g, 4, 0, red, b);
   if (threadIdx.x == 0) {
     ctl->c.rr = a[0];
     ctl->c.l1 = b[0];
-    ctl->c.f = 0.5 * a[0] + alpha * b[0];
-    ctl->c.f32 = __fadd_rn(__fmul_rn(0.5f, (float)a[0]), __fmul_rn((float)alpha, (float)b[0]));
+    ctl->c.f = scale * a[0] + alpha * b[0];
+    ctl->c.f32 = __fadd_rn(__fmul_rn((float)scale, (float)a[0]), __fmul_rn((float)alpha, (float)b[0]));
     ctl->pgl1 = b[1];
     ctl->ys = b[2];
     ctl->yy = b[3];
@@ -430,9 +481,12 @@ int pairs_needed(const lasso_owlqn_options& o) { return std::max(0, std::min(o.h
 size_t workspace_bytes(int64_t n, int64_t d, int64_t k, int64_t pairs) { return carve(nullptr, n, d, k, pairs).bytes + 256; }
 
 int solve(const float* x, int64_t ldx, const float* w, int64_t ldw, const float* z0, int64_t ldz0, float* zout, int64_t ldz,
-          int64_t n64, int64_t d64, int64_t k64, double alpha, const lasso_owlqn_options& o, lasso_owlqn_result* res,
-          void* workspace, hipStream_t st) {
+          int64_t n64, int64_t d64, int64_t k64, double alpha, int family, const lasso_owlqn_options& o,
+          lasso_owlqn_result* res, void* workspace, hipStream_t st) {
   const int n = (int)n64, d = (int)d64, k = (int)k64;
+  if (family != kFamilyRss && family != LASSO_GLM_BERNOULLI) return fail(LASSO_ERR_UNSUPPORTED, "OWL-QN: family %d", family);
+  const bool glm = family != kFamilyRss;
+  const double scale = glm ? 1.0 : 0.5;                     // f = scale * (the loss sum of the first product) + alpha |z|_1
   PairRing ring(pairs_needed(o));
   const Space ws = carve(workspace, n, d, k, ring.capacity());
   const int cus = device_cus();
@@ -465,9 +519,15 @@ int solve(const float* x, int64_t ldx, const float* w, int64_t ldw, const float*
   // resid, g, v, f of the z in its buffer -- and (pair) the candidate pair against z_prev / g_prev in the ring's next slot
   auto evaluate = [&](bool pair) -> int {
     const float* const Z = ws.Zb[zb.cur()];
-    Epi er = {};
-    er.X = x; er.ldx = ldx; er.Out = ws.R; er.part = ws.part_r;
-    LASSO_HIP_TRY(launch_gemm<EPI_RESID>(Z, k, w, ldw, n, d, k, er, side_d, 1, st));
+    if (glm) {
+      LinkEpi<true> el = {};
+      el.X = x; el.ldx = ldx; el.Out = ws.R; el.part = ws.part_r;
+      LASSO_HIP_TRY(solver::launch_gemm(Z, k, w, ldw, n, d, k, el, side_d, 1, st));
+    } else {
+      Epi er = {};
+      er.X = x; er.ldx = ldx; er.Out = ws.R; er.part = ws.part_r;
+      LASSO_HIP_TRY(launch_gemm<EPI_RESID>(Z, k, w, ldw, n, d, k, er, side_d, 1, st));
+    }
     GradEpi eg = {};
     eg.Z = Z; eg.V = ws.V; eg.part = ws.part_g; eg.alpha = (float)alpha; eg.pair = pair ? 1 : 0;
     // g goes where g_prev is not; without a pair it IS the first g_prev
@@ -479,7 +539,7 @@ int solve(const float* x, int64_t ldx, const float* w, int64_t ldw, const float*
       eg.Y = ws.Y + (int64_t)ring.candidate() * ws.stride;
     }
     LASSO_HIP_TRY(solver::launch_gemm(ws.R, d, ws.Wt, d, n, k, d, eg, side_k, 1, st));
-    hipLaunchKernelGGL(eval_kernel, dim3(1), dim3(256), 0, st, ws.part_r, pd, ws.part_g, pk, alpha, ws.ctl);
+    hipLaunchKernelGGL(eval_kernel, dim3(1), dim3(256), 0, st, ws.part_r, pd, ws.part_g, pk, scale, alpha, ws.ctl);
     LASSO_HIP_TRY(hipGetLastError());
     return fetch();
   };
@@ -509,13 +569,17 @@ int solve(const float* x, int64_t ldx, const float* w, int64_t ldw, const float*
   auto trial = [&](const Steps& steps, int count, bool product, bool backtrack) -> int {
     hipLaunchKernelGGL(trial_kernel, dim3(gk, count), dim3(256), 0, st, ws.Zb[zb.cur()], ws.V, ws.D, ws.Zc, nk, steps, ws.part_t);
     LASSO_HIP_TRY(hipGetLastError());
-    if (product) {
+    if (product && glm) {
+      LinkEpi<false> et = {};
+      et.X = x; et.ldx = ldx; et.a_stride = nk; et.part = ws.part_r;
+      LASSO_HIP_TRY(solver::launch_gemm(ws.Zc, k, w, ldw, n, d, k, et, side_d, count, st));
+    } else if (product) {
       Epi et = {};
       et.X = x; et.ldx = ldx; et.a_stride = nk; et.part = ws.part_r;
       LASSO_HIP_TRY(launch_gemm<EPI_TRIAL>(ws.Zc, k, w, ldw, n, d, k, et, side_d, count, st));
     }
     hipLaunchKernelGGL(decide_kernel, dim3(1), dim3(256), 0, st, ws.part_t, gk, ws.part_r, pd, count, product ? 1 : 0,
-                       backtrack ? 1 : 0, alpha, (float)o.ls_tol, &ws.ctl->c);
+                       backtrack ? 1 : 0, scale, alpha, (float)o.ls_tol, &ws.ctl->c);
     LASSO_HIP_TRY(hipGetLastError());
     if (!product || backtrack) {
       hipLaunchKernelGGL(accept_kernel, dim3(gk), dim3(256), 0, st, ws.Zc, ws.Zb[zb.target()], nk, &ws.ctl->c);

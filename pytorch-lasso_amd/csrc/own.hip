@@ -127,7 +127,7 @@ int solve(const float* x, int64_t ldx, const float* w, int64_t ldw, const float*
       LASSO_HIP_TRY(launch_gemm<EPI_TRIAL>(ws.Zc, k, w, ldw, n, d, k, et, side_d, count, st));
     }
     hipLaunchKernelGGL(decide_kernel, dim3(1), dim3(256), 0, st, ws.part_t, gk, ws.part_r, pd, count, product ? 1 : 0,
-                       backtrack ? 1 : 0, alpha, (float)o.ls_tol, ws.ctl);
+                       backtrack ? 1 : 0, 0.5, alpha, (float)o.ls_tol, ws.ctl);
     LASSO_HIP_TRY(hipGetLastError());
     if (!product || backtrack) {
       hipLaunchKernelGGL(accept_kernel, dim3(gk), dim3(256), 0, st, ws.Zc, ws.Z, nk, ws.ctl);

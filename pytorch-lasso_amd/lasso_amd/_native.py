@@ -30,6 +30,7 @@ GPSR_DEBIAS_NO_NONZEROS, GPSR_DEBIAS_TOO_MANY = 8, 16
 OWN_BRENT, OWN_BACKTRACK, OWN_NONE = 0, 1, 2
 OWN_LS_NOT_CONVERGED, OWN_NONFINITE = 1, 2
 OWLQN_MAX_PAIRS = 1535                                                # most pairs lasso_owlqn_solve holds
+GLM_BERNOULLI = 1                                                     # lasso_owlqn_glm_solve's family
 IRBFGS_CONVERGED, IRBFGS_NONFINITE = 1, 2
 IRBFGS_MAX_K = 1024                                                   # lasso_batch_solve_tier_cap(LASSO_F32, general)
 IRBFGS_TIME_ROWS = 2                                                  # bit 1 of lasso_irbfgs_options.reserved
@@ -461,6 +462,9 @@ def _declare(lib):
     lib.lasso_owlqn_solve.restype = i32
     lib.lasso_owlqn_solve.argtypes = [vp, i64, vp, i64, vp, i64, vp, i64, i64, i64, i64, i32, dbl,
                                       C.POINTER(OwlqnOptions), C.POINTER(OwlqnResult), vp, sz, vp]
+    lib.lasso_owlqn_glm_solve.restype = i32
+    lib.lasso_owlqn_glm_solve.argtypes = [vp, i64, vp, i64, vp, i64, vp, i64, i64, i64, i64, i32, dbl, i32,
+                                          C.POINTER(OwlqnOptions), C.POINTER(OwlqnResult), vp, sz, vp]
     lib.lasso_irbfgs_workspace_bytes.restype = sz
     lib.lasso_irbfgs_workspace_bytes.argtypes = [i64, i64, i64, i32]
     lib.lasso_irbfgs_solve.restype = i32

@@ -1,5 +1,5 @@
 """HIP-backed OWL-QN: the arguments, defaults, warnings and prints of ``lasso.nonlinear.owlqn`` (reference
-lasso/nonlinear/owlqn.py:80-199) on the kernels of csrc/owlqn.hip, for the objective ``rss(x, weight)``."""
+lasso/nonlinear/owlqn.py:80-199) on the kernels of csrc/owlqn.hip, for the objectives ``rss(x, weight)`` and ``bernoulli(x, weight)``."""
 import ctypes as C
 import warnings
 from typing import NamedTuple
@@ -20,14 +20,27 @@ class rss(NamedTuple):
     weight: torch.Tensor
 
 
+class bernoulli(NamedTuple):
+    """The objective ``fun(z) = sum(softplus(u) - x * u)`` with ``u = z @ weight.T`` over the whole batch, which is
+    ``F.binary_cross_entropy_with_logits(u, x, reduction='sum')``: x [n,d], weight [d,k].  ``x`` is any real target --
+    hard 0/1 or soft in [0, 1]; as in torch it is not validated.  A description, not a function, like ``rss``."""
+    x: torch.Tensor
+    weight: torch.Tensor
+
+
+_FAMILIES = {bernoulli: nat.GLM_BERNOULLI}                     # rss: lasso_owlqn_solve; these: lasso_owlqn_glm_solve
+
+
 def owlqn(fun, x0, alpha=1., lr=1, max_iter=20, xtol=1e-5, history_size=100, line_search='brent', ls_options=None,
           verbose=0, return_info=False):
-    """Orthant-wise limited-memory quasi-Newton for min_z fun(z) + alpha ||z||_1 with ``fun = rss(x, weight)``:
-    x0 [n,k] -> z [n,k] (a new tensor on the device of ``x0``; no input is modified).  Any other ``fun`` raises
-    NotImplementedError: only ``rss(x, weight)`` objectives run on the HIP path.
+    """Orthant-wise limited-memory quasi-Newton for min_z fun(z) + alpha ||z||_1 with ``fun = rss(x, weight)`` or
+    ``fun = bernoulli(x, weight)``: x0 [n,k] -> z [n,k] (a new tensor on the device of ``x0``; no input is modified).
+    Any other ``fun`` raises NotImplementedError: only these two descriptions run on the HIP path.
 
         z = owlqn(rss(x, weight), z0, alpha=0.5)
         # reference: owlqn(lambda z: 0.5 * (z @ weight.T - x).pow(2).sum(), z0, alpha=0.5)
+        z = owlqn(bernoulli(x, weight), z0, alpha=0.1)
+        # reference: owlqn(lambda z: F.binary_cross_entropy_with_logits(z @ weight.T, x, reduction='sum'), z0, alpha=0.1)
 
     The arguments and defaults are the reference's (owlqn.py:81-82) plus ``return_info``.  One objective, one line
     search, one L-BFGS memory and one stop test ``||x_new - x||_2 <= xtol`` serve the whole batch.  ``line_search``:
@@ -50,6 +63,9 @@ def owlqn(fun, x0, alpha=1., lr=1, max_iter=20, xtol=1e-5, history_size=100, lin
         d = project(gamma v + S c + Y e, v) accumulated in double and rounded once -- the same operator, another
         order of operations.
       * An unknown ``line_search`` raises its RuntimeError up front, not at the first iteration.
+      * ``bernoulli``: the objective is the double fold of per-element float32 losses, and the link is evaluated in
+        the stable form e = exp(-|u|), loss = max(u, 0) - x u + log1p(e), sigmoid(u) = (u >= 0 ? 1 : e) / (1 + e):
+        no exp(+|u|), so logits beyond 88.7 give a finite loss and residual.
     Only min(history_size, max_iter - 1) pairs are ever reserved (at most 1535).
 
     float32 tensors only, all of one dtype (anything else raises NotImplementedError naming the dtype); no cap on k.
@@ -61,7 +77,7 @@ def owlqn(fun, x0, alpha=1., lr=1, max_iter=20, xtol=1e-5, history_size=100, lin
         ls_options = {}
     if line_search not in _LINE_SEARCHES:
         raise RuntimeError("line_search must be one of {'brent', 'backtrack', 'none'}.")
-    if not isinstance(fun, rss):
+    if not isinstance(fun, (rss, bernoulli)):
         raise NotImplementedError("lasso_amd: only rss(x, weight) objectives run on the HIP path (got %s)"
                                   % type(fun).__name__)
     for name in ls_options:
@@ -70,7 +86,7 @@ def owlqn(fun, x0, alpha=1., lr=1, max_iter=20, xtol=1e-5, history_size=100, lin
     ls = dict(_LS_DEFAULTS, **ls_options)
     x, weight = fun.x, fun.weight
     if not (torch.is_tensor(x) and torch.is_tensor(weight)) or x.dim() != 2 or weight.dim() != 2:
-        raise RuntimeError("owlqn: rss(x, weight) expects 2-D tensors x [n,d] and weight [d,k]")
+        raise RuntimeError("owlqn: %s(x, weight) expects 2-D tensors x [n,d] and weight [d,k]" % type(fun).__name__)
     d, k = weight.shape
     n = x.size(0)
     assert x.size(1) == d
@@ -111,10 +127,13 @@ def owlqn(fun, x0, alpha=1., lr=1, max_iter=20, xtol=1e-5, history_size=100, lin
         L = nat.lib()
         with torch.cuda.device(dev):
             ws = nat.workspace(dev, L.lasso_owlqn_workspace_bytes(n, d, k, nat.LASSO_F32, pairs), "owlqn")
-            status = L.lasso_owlqn_solve(
-                nat.ptr(xg), xg.stride(0) if n > 1 else d, nat.ptr(wg), wg.stride(0) if d > 1 else k,
-                nat.ptr(z0g), k, nat.ptr(z), k, n, d, k, nat.LASSO_F32, float(alpha),
-                C.byref(options), C.byref(res), nat.ptr(ws), ws.numel(), nat.stream_ptr(dev))
+            head = (nat.ptr(xg), xg.stride(0) if n > 1 else d, nat.ptr(wg), wg.stride(0) if d > 1 else k,
+                    nat.ptr(z0g), k, nat.ptr(z), k, n, d, k, nat.LASSO_F32, float(alpha))
+            tail = (C.byref(options), C.byref(res), nat.ptr(ws), ws.numel(), nat.stream_ptr(dev))
+            if isinstance(fun, rss):
+                status = L.lasso_owlqn_solve(*head, *tail)
+            else:
+                status = L.lasso_owlqn_glm_solve(*head, _FAMILIES[type(fun)], *tail)
         nat.check(status)
         its = min(res.n_iter, cap)
         evs = min(trace.eval_count, ecap)
