@@ -837,7 +837,16 @@ int lasso_patches_reconstruct(const void* patches_dev, int64_t ld, const float* 
  * has reduced lambda 100 times, ends the solve (LASSO_GPSR_LINESEARCH_FAILED) with the last accepted z -- the
  * reference would loop for ever.  z0_dev is only read; z_out_dev may not alias x or W.
  * The call blocks: the host reads the control block once per outer iteration.  LASSO_F32 only (else
- * LASSO_ERR_UNSUPPORTED); any n >= 0, d, k >= 1; n = 0 writes nothing. */
+ * LASSO_ERR_UNSUPPORTED); any n >= 0, d, k >= 1; n = 0 writes nothing.
+ * options->reserved: LASSO_FORCE_BLOCKS_128 is the one defined bit; any other is LASSO_ERR_BAD_ARG with nothing written. */
+/* A bit of options.reserved that the solvers on the shared fp32 GEMM shell take (lasso_gpsr_solve, lasso_conv_gpsr_solve,
+ * the dense lasso_cg_solve, lasso_iter_ridge_solve, lasso_interior_point_solve, lasso_irbfgs_solve): every product of the
+ * solve runs on 128 x 128 blocks, also below the size at which the solver would choose them (tests; the codes are those
+ * of a solve that chose them itself).  A row pitch of 2^22 elements or more keeps 64 x 64 blocks.
+ * lasso_solver_block_side(m, nn, ldmax) is the side -- 64 or 128 -- an unforced solve on the current device gives a
+ * product [m, nn] whose widest row pitch (operands, output, contraction) is ldmax elements; 0 for a bad shape. */
+#define LASSO_FORCE_BLOCKS_128 8
+int lasso_solver_block_side(int64_t m, int64_t nn, int64_t ldmax);
 typedef struct lasso_gpsr_options {
   int32_t stop_criterion, maxiter, miniter, init;
   int32_t continuation, debias, cont_steps, maxiter_debias, miniter_debias, reserved;
@@ -886,7 +895,9 @@ int lasso_gpsr_solve(const void* x_dev, int64_t ldx, const void* w_dev, int64_t 
  * Two kernel families (csrc/conv_gpsr.hip): "implicit" where the implicit-GEMM kernels of lasso_conv_ista_solve cover
  * the geometry (the rule of lasso_conv_ista_kernel_name: stride 1, few channels, 3/5/7 kernels, K a multiple of 4),
  * "patches" (patch matrix + GEMM, GEMM + overlap-add) everywhere else.  Bit 0 of options->reserved forces "patches";
- * lasso_conv_gpsr_form says which one a solve of that geometry with that `reserved` takes ("" for a refused geometry). */
+ * lasso_conv_gpsr_form says which one a solve of that geometry with that `reserved` takes ("" for a refused geometry).
+ * LASSO_FORCE_BLOCKS_128 in options->reserved gives the GEMMs of "patches" 128 x 128 blocks (tests; the form is
+ * unaffected); every other bit is LASSO_ERR_BAD_ARG. */
 size_t lasso_conv_gpsr_workspace_bytes(int64_t N, int64_t C, int64_t H, int64_t W, int64_t K, int64_t Hz, int64_t Wz,
                                        int kh, int kw, int sh, int sw, int ph, int pw);
 const char* lasso_conv_gpsr_form(int64_t N, int64_t C, int64_t H, int64_t W, int64_t K, int64_t Hz, int64_t Wz, int kh,
@@ -1042,7 +1053,8 @@ int lasso_owlqn_glm_solve(const void* x_dev, int64_t ldx, const void* w_dev, int
  *             lasso_batch_solve_workspace_bytes(n, k).  It grows with n k^2: the caller splits a large batch.
  *   options : maxiter >= 0, line_search 0 / 1, lr, xtol, tikhonov, eps >= 0.  Bit 1 of reserved times the update launches
  *             with events (result.row_ms), counts the bytes of their k x k traffic (result.row_bytes) and times the
- *             solves of the systems (result.solve_ms) -- all 0 without it (tools/bench_irbfgs.py); every other bit must be 0.
+ *             solves of the systems (result.solve_ms) -- all 0 without it (tools/bench_irbfgs.py); LASSO_FORCE_BLOCKS_128
+ *             forces 128 x 128 GEMM blocks (tests); every other bit must be 0.
  *   result  : n_iter, flags (LASSO_IRBFGS_*), the objective of z0 and of z_out, lu_count = iterations that took the
  *             LU route, and -- trace non-NULL -- host arrays of the caller: per iteration (capacity) t, the Brent
  *             evaluations, the objective and |dz|_2 of the new z, the rows whose update was invalid (-1: no update
@@ -1105,7 +1117,8 @@ int lasso_irbfgs_update(void* b_dev, const void* x_dev, const void* g_dev, void*
  * trial and handed to the search as an un-rounded double; z += t p on the support.  The solve stops once
  * sum |update| <= n k tol (converged), on a NaN objective or update, or after maxiter iterations.  Every sum is folded
  * in double in a fixed order: two solves of the same arguments give the same bits.
- *   options : maxiter >= 0, line_search 0 / 1, tol >= 0 (per element), tikhonov >= 0, eps >= 0, reserved = 0.
+ *   options : maxiter >= 0, line_search 0 / 1, tol >= 0 (per element), tikhonov >= 0, eps >= 0; reserved = 0 or
+ *             LASSO_FORCE_BLOCKS_128 (128 x 128 GEMM blocks, tests).
  *   result  : n_iter, status, the objective of z0 and the last fval, bad_row / bad_minor (-1 / 0, or the lowest row whose
  *             system had a non-positive or NaN pivot and 1 + that pivot's index in the compacted system: then
  *             LASSO_ERR_BAD_ARG and z_out is not written), and -- trace non-NULL -- host arrays of the caller: per iteration
@@ -1115,13 +1128,13 @@ int lasso_irbfgs_update(void* b_dev, const void* x_dev, const void* g_dev, void*
  * (masked entries of z_sol are 0); its workspace is lasso_iter_ridge_workspace_bytes(n, 1, k, dtype); support_max_out is
  * nullable.  z_sol may not alias z.
  * Refusals before any HIP call: null pointers, n < 0, d or k < 1, a leading dimension below the row length, alpha < 0,
- * negative options or reserved != 0 are LASSO_ERR_BAD_ARG; a dtype other than LASSO_F32 and k > 1024
+ * negative options or an undefined bit of reserved are LASSO_ERR_BAD_ARG; a dtype other than LASSO_F32 and k > 1024
  * LASSO_ERR_UNSUPPORTED (the workspace query returns 0); a short workspace LASSO_ERR_WORKSPACE.  n = 0 writes nothing.
  * The workspace grows linearly in n: the general tier's scratch is at most 256 triangles and 256 MiB.  The calls block. */
 typedef struct lasso_iter_ridge_options {
   int32_t maxiter, line_search;
   double tol, tikhonov, eps;
-  int64_t reserved;                       /* must be 0 */
+  int64_t reserved;                       /* 0 or LASSO_FORCE_BLOCKS_128 */
 } lasso_iter_ridge_options;
 typedef struct lasso_iter_ridge_trace {
   int32_t capacity;                       /* iterations the arrays below hold */
@@ -1205,20 +1218,21 @@ int lasso_split_bregman_solve(const void* x_dev, int64_t ldx, const void* w_dev,
  * mean never stops it, and with tol <= 0 the host reads nothing between the start's flag and the end.  A pivot that is
  * not positive is not repaired: that row's codes are NaN.  Every sum is folded in double in a fixed order: two solves
  * of the same arguments give the same bits.
- *   options : maxiter >= 0, barrier_init, tol, eps >= 0, reserved = 0.
+ *   options : maxiter >= 0, barrier_init, tol, eps >= 0; reserved = 0 or LASSO_FORCE_BLOCKS_128 (128 x 128 GEMM blocks,
+ *             tests).
  *   result  : n_iter, status, obj0 = alpha sum z + 0.5 sum lambda^2 of the start, and -- trace non-NULL -- host arrays
  *             of the caller: per iteration (capacity) that objective and the three means.
  * lasso_interior_point_rows is the per-row Newton system on its own: y [n][d] with (I + W diag(c_i) W^T) y_i = b_i from
  * W [d][k], c [n][k] >= 0 and b [n][d].  y may alias b.  It needs no workspace.
  * Refusals before any HIP call: null pointers, n < 0, d or k < 1, a leading dimension below the row length, alpha < 0
- * or NaN, maxiter < 0, eps < 0, a NaN option or reserved != 0 are LASSO_ERR_BAD_ARG; a dtype other than LASSO_F32,
- * d > 256 and k > 4096 LASSO_ERR_UNSUPPORTED (the workspace query returns 0); a short workspace LASSO_ERR_WORKSPACE.
+ * or NaN, maxiter < 0, eps < 0, a NaN option or an undefined bit of reserved are LASSO_ERR_BAD_ARG; a dtype other than
+ * LASSO_F32, d > 256 and k > 4096 LASSO_ERR_UNSUPPORTED (the workspace query returns 0); a short workspace LASSO_ERR_WORKSPACE.
  * n = 0 writes nothing.  The workspace grows linearly in n: the state z, s [n][2k], lambda [n][d], five [n][k] and four
  * [n][d] temporaries, 64 bytes per row of ratios; there is no n d^2 term.  The calls block. */
 typedef struct lasso_interior_point_options {
   int32_t maxiter, pad_;
   double barrier_init, tol, eps;
-  int64_t reserved;                       /* must be 0 */
+  int64_t reserved;                       /* 0 or LASSO_FORCE_BLOCKS_128 */
 } lasso_interior_point_options;
 typedef struct lasso_interior_point_trace {
   int32_t capacity, pad_;                 /* iterations the arrays below hold */
@@ -1260,7 +1274,8 @@ int lasso_interior_point_rows(const void* w_dev, int64_t ldw, const void* c_dev,
  * (H = (Hz - 1) sh - 2 ph + kh, likewise W); LASSO_F32 only.
  *   options : maxiter >= 0, tol >= 0, rtol >= 0, tik >= 0.  Bit 0 of reserved takes the plain forms -- dense: the
  *             product stores Ap and a pass of its own takes curv; convolutional: conv_transpose2d as GEMM + overlap-add
- *             also where an implicit kernel covers the geometry -- every other bit must be 0.
+ *             also where an implicit kernel covers the geometry.  Dense only: LASSO_FORCE_BLOCKS_128 forces 128 x 128
+ *             GEMM blocks (tests; the float64 product has one block side and ignores it).  Every other bit must be 0.
  *   result  : n_iter (the index i of the iteration an exit fired in; maxiter for status 4), status, host_reads (waits
  *             of the host for the device's control record: one per chunk of iterations; with rtol = 0 and tol = 0 one
  *             at the end), form (LASSO_CG_FORM_*: what ran), termcond, and -- trace non-NULL -- host arrays of the

@@ -615,7 +615,9 @@ int solve_f32(const float* A, int64_t lda, const float* b, int64_t ldb, float* x
   const int cus = device_cus();
   const int64_t ldmax = std::max<int64_t>((int64_t)k, lda);
   if (ldmax * 64 * 4 >= ((int64_t)1 << 31)) return fail(LASSO_ERR_UNSUPPORTED, "row pitch beyond the 32-bit offsets of a 64-row block");
-  const int side = block_side(n, k, ldmax, cus);
+  // LASSO_FORCE_BLOCKS_128 (tests): 128 x 128 blocks below the size at which block_side takes them
+  const bool force128 = (o.reserved & LASSO_FORCE_BLOCKS_128) && ldmax * 128 * 4 < ((int64_t)1 << 31);
+  const int side = force128 ? 128 : block_side(n, k, ldmax, cus);
   const bool fused = !(o.reserved & 1);
   const int ncb = (k + side - 1) / side;
   res->form = fused ? LASSO_CG_FORM_FUSED : LASSO_CG_FORM_UNFUSED;

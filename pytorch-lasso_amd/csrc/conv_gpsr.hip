@@ -252,8 +252,11 @@ int conv_solve(const float* x, const float* w, const float* z0, float* zout, con
                 (long long)M);
   ConvOp op;
   op.rows = (int)M; op.cols = g.K; op.nd = (int64_t)g.N * g.C * g.H * g.W;
-  op.side_k = block_side((int)M, g.K, std::max<int64_t>(ldr, g.K), cus);          // products [M,K]
-  op.side_c = block_side(ckk, (int)M, std::max<int64_t>(M, g.K), cus);            // COLSt [C kh kw, M]
+  // LASSO_FORCE_BLOCKS_128 (tests): 128 x 128 blocks below the size at which block_side takes them
+  const bool force128 = (o.reserved & LASSO_FORCE_BLOCKS_128) &&
+                        std::max<int64_t>({M, (int64_t)g.K, (int64_t)ldr}) * 128 * 4 < ((int64_t)1 << 31);
+  op.side_k = force128 ? 128 : block_side((int)M, g.K, std::max<int64_t>(ldr, g.K), cus);          // products [M,K]
+  op.side_c = force128 ? 128 : block_side(ckk, (int)M, std::max<int64_t>(M, g.K), cus);            // COLSt [C kh kw, M]
   op.pk_gemm = gemm_parts((int)M, g.K, op.side_k);
   op.pk_cap = gemm_parts((int)M, g.K, 64);
   op.cus = cus;

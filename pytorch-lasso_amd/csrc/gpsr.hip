@@ -63,6 +63,8 @@ LinearSpace carve(void* base, int64_t n, int64_t d, int64_t k) {
 
 size_t workspace_bytes(int64_t n, int64_t d, int64_t k) { return carve(nullptr, n, d, k).bytes + 256; }
 
+int block_side_here(int m, int nn, int64_t ldmax) { return block_side(m, nn, ldmax, solver::device_cus()); }
+
 int solve(const float* x, int64_t ldx, const float* w, int64_t ldw, const float* z0, int64_t ldz0, float* zout, int64_t ldz,
           int64_t n64, int64_t d64, int64_t k64, double alpha, const lasso_gpsr_options& o, lasso_gpsr_result* res,
           void* workspace, hipStream_t st) {
@@ -74,8 +76,11 @@ int solve(const float* x, int64_t ldx, const float* w, int64_t ldw, const float*
   }
   LinearOp op;
   op.rows = n; op.cols = k; op.nd = (int64_t)n * d;
-  op.side_k = block_side(n, k, std::max<int64_t>({(int64_t)d, (int64_t)k, ldx}), cus);       // products [n,k]
-  op.side_d = block_side(n, d, std::max<int64_t>({(int64_t)d, (int64_t)k, ldx, ldw}), cus);  // products [n,d]
+  const int64_t ldmax_k = std::max<int64_t>({(int64_t)d, (int64_t)k, ldx}), ldmax_d = std::max<int64_t>(ldmax_k, ldw);
+  // LASSO_FORCE_BLOCKS_128 (tests): 128 x 128 blocks below the size at which block_side takes them
+  const bool force128 = (o.reserved & LASSO_FORCE_BLOCKS_128) && ldmax_d * 128 * 4 < ((int64_t)1 << 31);
+  op.side_k = force128 ? 128 : block_side(n, k, ldmax_k, cus);           // products [n,k]
+  op.side_d = force128 ? 128 : block_side(n, d, ldmax_d, cus);           // products [n,d]
   op.pk = gemm_parts(n, k, op.side_k);
   op.pd = gemm_parts(n, d, op.side_d);
   op.y = x; op.ldy = ldx; op.y_rows = n; op.y_cols = d;

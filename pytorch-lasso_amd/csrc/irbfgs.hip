@@ -428,7 +428,10 @@ int solve(const float* x, int64_t ldx, const float* w, int64_t ldw, const float*
   const int cus = device_cus();
   const int64_t ldmax = std::max<int64_t>({(int64_t)d, (int64_t)k, ldx, ldw});
   if (ldmax * 64 * 4 >= ((int64_t)1 << 31)) return fail(LASSO_ERR_UNSUPPORTED, "row pitch beyond the 32-bit offsets of a 64-row block");
-  const int side_k = block_side(n, k, ldmax, cus), side_d = block_side(n, d, ldmax, cus);
+  // LASSO_FORCE_BLOCKS_128 (tests): 128 x 128 blocks below the size at which block_side takes them
+  const bool force128 = (o.reserved & LASSO_FORCE_BLOCKS_128) && ldmax * 128 * 4 < ((int64_t)1 << 31);
+  const int side_k = force128 ? 128 : block_side(n, k, ldmax, cus);      // products [n,k]
+  const int side_d = force128 ? 128 : block_side(n, d, ldmax, cus);      // products [n,d]
   const int pd = gemm_parts(n, d, side_d);
   const int64_t nk = (int64_t)n * k, nd = (int64_t)n * d;
   const int gk = ew_grid(nk), gd = ew_grid(nd);

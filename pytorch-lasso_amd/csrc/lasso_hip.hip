@@ -2866,7 +2866,8 @@ size_t lasso_gpsr_workspace_bytes(int64_t n, int64_t d, int64_t k, int dtype) {
 }
 
 // the option, trace and result checks the two GPSR entry points share; clears the result
-static int check_gpsr_request(const lasso_gpsr_options* o, lasso_gpsr_result* res, bool has_z0) {
+static int check_gpsr_request(const lasso_gpsr_options* o, lasso_gpsr_result* res, bool has_z0, int defined_bits) {
+  if (o->reserved & ~defined_bits) return fail(LASSO_ERR_BAD_ARG, "GPSR: an undefined bit of reserved");
   if (o->stop_criterion < 0 || o->stop_criterion > 4) return fail(LASSO_ERR_BAD_ARG, "Unknown stopping criterion");
   if (!has_z0 && o->init == 1) return fail(LASSO_ERR_UNSUPPORTED, "GPSR: init=1 (random start) is passed as z0");
   if (!has_z0 && o->init != 0 && o->init != 2) return fail(LASSO_ERR_BAD_ARG, "Unknown initialization option");
@@ -2893,7 +2894,7 @@ int lasso_gpsr_solve(const void* x_dev, int64_t ldx, const void* w_dev, int64_t 
   if (!o || !res) return fail(LASSO_ERR_BAD_ARG, "null options / result");
   if (n < 0 || d <= 0 || k <= 0 || n > INT32_MAX || d > INT32_MAX || k > INT32_MAX)
     return fail(LASSO_ERR_BAD_ARG, "bad shape");
-  if (int s = check_gpsr_request(o, res, z0_dev != nullptr)) return s;
+  if (int s = check_gpsr_request(o, res, z0_dev != nullptr, LASSO_FORCE_BLOCKS_128)) return s;
   if (n == 0) return LASSO_OK;
   if (!x_dev || !w_dev || !z_out_dev || !workspace_dev) return fail(LASSO_ERR_BAD_ARG, "null pointer");
   if (ldx < d || ldw < k || ldz < k || (z0_dev && ldz0 < k)) return fail(LASSO_ERR_BAD_ARG, "leading dimension too small");
@@ -3020,7 +3021,8 @@ int lasso_irbfgs_solve(const void* x_dev, int64_t ldx, const void* w_dev, int64_
   const int cap = batch_solve::tier_cap(LASSO_F32, LASSO_BATCH_TIER_GENERAL);
   if (k > cap) return fail(LASSO_ERR_UNSUPPORTED, "iterative_ridge_bfgs: k=%lld > %d", (long long)k, cap);
   if (!(alpha >= 0.0)) return fail(LASSO_ERR_BAD_ARG, "alpha < 0");
-  if ((o->reserved & ~(int64_t)2) != 0) return fail(LASSO_ERR_BAD_ARG, "iterative_ridge_bfgs: unknown bit of reserved");
+  if ((o->reserved & ~(int64_t)(2 | LASSO_FORCE_BLOCKS_128)) != 0)
+    return fail(LASSO_ERR_BAD_ARG, "iterative_ridge_bfgs: unknown bit of reserved");
   if (o->maxiter < 0 || o->line_search < 0 || o->line_search > 1 || !(o->lr >= 0.0) || !(o->xtol >= 0.0) ||
       !(o->tikhonov >= 0.0) || !(o->eps >= 0.0))
     return fail(LASSO_ERR_BAD_ARG, "maxiter, lr, xtol, tikhonov, eps >= 0 and line_search 0 / 1 are required");
@@ -3076,7 +3078,8 @@ int lasso_iter_ridge_solve(const void* x_dev, int64_t ldx, const void* w_dev, in
     return fail(LASSO_ERR_BAD_ARG, "bad shape");
   if (k > 1024) return fail(LASSO_ERR_UNSUPPORTED, "iterated ridge: k=%lld > 1024", (long long)k);
   if (!(alpha >= 0.0)) return fail(LASSO_ERR_BAD_ARG, "alpha < 0");
-  if (o->reserved != 0) return fail(LASSO_ERR_BAD_ARG, "iterated ridge: reserved must be 0");
+  if ((o->reserved & ~(int64_t)LASSO_FORCE_BLOCKS_128) != 0)
+    return fail(LASSO_ERR_BAD_ARG, "iterated ridge: only bit 3 of reserved is defined");
   if (o->maxiter < 0 || o->line_search < 0 || o->line_search > 1 || !(o->tol >= 0.0) || !(o->tikhonov >= 0.0) || !(o->eps >= 0.0))
     return fail(LASSO_ERR_BAD_ARG, "maxiter, tol, tikhonov, eps >= 0 and line_search 0 / 1 are required");
   if (const lasso_iter_ridge_trace* t = res->trace) {
@@ -3171,7 +3174,8 @@ int lasso_interior_point_solve(const void* x_dev, int64_t ldx, const void* w_dev
   if (d > 256) return fail(LASSO_ERR_UNSUPPORTED, "interior point: d=%lld > 256", (long long)d);
   if (k > 4096) return fail(LASSO_ERR_UNSUPPORTED, "interior point: k=%lld > 4096", (long long)k);
   if (!(alpha >= 0.0)) return fail(LASSO_ERR_BAD_ARG, "alpha < 0");
-  if (o->reserved != 0) return fail(LASSO_ERR_BAD_ARG, "interior point: reserved must be 0");
+  if ((o->reserved & ~(int64_t)LASSO_FORCE_BLOCKS_128) != 0)
+    return fail(LASSO_ERR_BAD_ARG, "interior point: only bit 3 of reserved is defined");
   if (o->maxiter < 0 || !(o->eps >= 0.0) || o->tol != o->tol || o->barrier_init != o->barrier_init)
     return fail(LASSO_ERR_BAD_ARG, "maxiter >= 0, eps >= 0 and numbers for tol and barrier_init are required");
   if (const lasso_interior_point_trace* t = res->trace) {
@@ -3201,6 +3205,12 @@ int lasso_interior_point_rows(const void* w_dev, int64_t ldw, const void* c_dev,
   if (ldw < k || ldc < k || ldb < d || ldy < d) return fail(LASSO_ERR_BAD_ARG, "leading dimension too small");
   return interior_point::rows((const float*)w_dev, ldw, (const float*)c_dev, ldc, (const float*)b_dev, ldb, (float*)y_dev, ldy,
                               n, d, k, static_cast<hipStream_t>(stream));
+}
+
+// ---- the block side of the solvers' GEMM shell (csrc/solver_common.hpp) ----------------------
+int lasso_solver_block_side(int64_t m, int64_t nn, int64_t ldmax) {
+  if (m < 0 || nn < 0 || m > INT32_MAX || nn > INT32_MAX) return 0;
+  return gpsr::block_side_here((int)m, (int)nn, ldmax);
 }
 
 // ---- one dense system per batch entry: utils.py:43-58 (csrc/batch_solve.hip) -----------------
@@ -3268,7 +3278,8 @@ static int check_cg_request(const lasso_cg_options* o, lasso_cg_result* res, boo
   if (o->maxiter < 0 || !(o->tol >= 0.0) || !(o->rtol >= 0.0) || !(o->tik >= 0.0))
     return fail(LASSO_ERR_BAD_ARG, "conjugate gradients: maxiter, tol, rtol, tik >= 0 are required");
   if (dense && o->tik != 0.0) return fail(LASSO_ERR_BAD_ARG, "conjugate gradients: the dense form takes tik = 0");
-  if (o->reserved & ~1) return fail(LASSO_ERR_BAD_ARG, "conjugate gradients: only bit 0 of reserved is defined");
+  if (o->reserved & ~(dense ? 1 | LASSO_FORCE_BLOCKS_128 : 1))
+    return fail(LASSO_ERR_BAD_ARG, "conjugate gradients: an undefined bit of reserved");
   if (const lasso_cg_trace* t = res->trace)
     if (t->capacity < 0) return fail(LASSO_ERR_BAD_ARG, "trace with a negative capacity");
   res->n_iter = 0;
@@ -3759,7 +3770,7 @@ int lasso_conv_gpsr_solve(const void* x_dev, const void* w_dev, const void* z0_d
   if (conv_gpsr_too_large(g))
     return fail(LASSO_ERR_UNSUPPORTED, "convolutional GPSR: %lld code pixels / %lld image elements are beyond 32-bit block offsets",
                 (long long)(N * Hz * Wz), (long long)(C * H * W));
-  if (int s = check_gpsr_request(o, res, z0_dev != nullptr)) return s;
+  if (int s = check_gpsr_request(o, res, z0_dev != nullptr, 1 | LASSO_FORCE_BLOCKS_128)) return s;
   if (N == 0) return LASSO_OK;
   if (!x_dev || !w_dev || !z_out_dev || !workspace_dev) return fail(LASSO_ERR_BAD_ARG, "null pointer");
   const size_t need = gpsr::conv_workspace_bytes(g);

@@ -569,6 +569,8 @@ hipError_t launch_ridge_solve(const double* A, const double* B, double* V, int64
 
 // GPSR-Basic (gpsr.hip): the driver behind lasso_gpsr_solve; returns a lasso_status, failure text through lasso::fail
 namespace gpsr {
+// solver_common.hpp's block_side on the current device, for lasso_solver_block_side: 64 or 128
+int block_side_here(int m, int nn, int64_t ldmax);
 size_t workspace_bytes(int64_t n, int64_t d, int64_t k);
 int solve(const float* x, int64_t ldx, const float* w, int64_t ldw, const float* z0, int64_t ldz0, float* zout, int64_t ldz,
           int64_t n, int64_t d, int64_t k, double alpha, const lasso_gpsr_options& o, lasso_gpsr_result* res, void* workspace,

@@ -41,6 +41,7 @@ CG_FORMS = ('fused', 'unfused', 'conv-implicit', 'conv-patches')      # LASSO_CG
 LIP_STATUS = ('converged', 'breakdown', 'maxiter', 'nonfinite')         # LASSO_LIP_*
 LIP_SPACES = ('image', 'code')                                        # LASSO_LIP_SPACE_*
 CG_PLAIN_FORM = 1                                                     # bit 0 of lasso_cg_options.reserved
+FORCE_BLOCKS_128 = 8                                                  # LASSO_FORCE_BLOCKS_128, a bit of options.reserved
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = None
@@ -509,6 +510,8 @@ def _declare(lib):
         C.POINTER(ConvLipOptions), C.POINTER(ConvLipResult), vp, sz, vp]
     lib.lasso_batch_solve_tier_cap.restype = i32
     lib.lasso_batch_solve_tier_cap.argtypes = [i32, i32]
+    lib.lasso_solver_block_side.restype = i32
+    lib.lasso_solver_block_side.argtypes = [i64, i64, i64]
     lib.lasso_batch_solve_workgroups.restype = i32
     lib.lasso_batch_solve_workgroups.argtypes = [i64, i64, i32]
     lib.lasso_batch_solve_workspace_bytes.restype = sz

@@ -394,3 +394,90 @@ def test_ridge_code_satisfies_the_normal_equations():
         # (at this rtol float32 ends on the residual or, as the reference does, on curv_sum <= 3 eps: both mean converged)
         assert info["status"] in (1, 2) and im["status"] in (1, 2)
         assert resid(z) <= 4.0 * resid(zm)
+
+
+# ---- 128 x 128 GEMM blocks, forced (LASSO_FORCE_BLOCKS_128) and chosen -------------------------------------------------------
+# block_side() takes 128-blocks only from 2 x CUs blocks on (256 CUs: 8.4 M elements of the product), far above the
+# shapes of this file.  The bit runs the product p A^T on Tile<128, 128>: CurvEpi (its per-row slots, one per column
+# block, and skip()) in the fused form, StoreEpi in the plain one.  Shapes: more than one 128-block in a dimension and a
+# nearly empty last one; k a multiple of 32 (LDS-DMA), of 4 (16-byte loads), odd (scalar loads); nine rows under three
+# column blocks.
+F128 = [(130, 96), (259, 132), (131, 31), (9, 288)]
+F128_KW = dict(maxiter=6, rtol=0.0, tol=0.0)
+_F128_MODEL = {}
+
+
+def f128_model(n, k, maxiter=6):
+    """the fresh-shape construction above, computed once per shape -> (A, b, xm, im, bar, rtol)"""
+    key = (n, k, maxiter)
+    if key not in _F128_MODEL:
+        A, b = dense_inputs(dict(n=n, k=k, d=max(4, k // 4), seed=40))
+        kw = dict(F128_KW, maxiter=maxiter)
+        xm, im = model.batch_cg(A, b, **kw)
+        bar, rtol = spread_against(lambda **knobs: model.batch_cg(A, b, **kw, **knobs), xm, im)
+        _F128_MODEL[key] = (A, b, xm, im, bar, rtol)
+    return _F128_MODEL[key]
+
+
+def check_f128(tag, x, info, reference, iterations=6):
+    A, b, xm, im, bar, rtol = reference
+    dx, rs = float((x - xm).abs().max()), seq_rel(info, im)
+    print("fresh %s: max|dx| = %.3g (bar %.3g), sequences rel %.3g (rtol %.3g)" % (tag, dx, bar, rs, rtol))
+    record_margins("conjgrad/fresh_" + tag, dict(dx=dx, bar=bar, seq_rel=rs, seq_rtol=rtol))
+    assert info["status"] == 4 and info["iterations"] == iterations and len(info["rs"]) == iterations
+    assert dx <= bar and rs <= rtol
+
+
+@pytest.mark.parametrize("force", [8, 0], ids=["f128", "s64"])
+@pytest.mark.parametrize("plain", [0, 1], ids=["fused", "plain"])
+@pytest.mark.parametrize("n,k", F128)
+def test_forced_128_blocks_against_the_model(n, k, plain, force):
+    from lasso_amd import _native as nat
+    assert nat.FORCE_BLOCKS_128 == 8 and nat.CG_PLAIN_FORM == 1
+    reference = f128_model(n, k)
+    x, res, info, _ = abi_dense(reference[0], reference[1], reserved=force | plain, **F128_KW)
+    assert info["form"] == ("unfused" if plain else "fused")
+    check_f128("%dx%d_%s_%s" % (n, k, "plain" if plain else "fused", "f128" if force else "s64"), x, info, reference)
+
+
+@pytest.mark.parametrize("plain", [0, 1], ids=["fused", "plain"])
+def test_forced_128_blocks_pitched_repeatable_and_refused(plain):
+    from lasso_amd import _native as nat
+    force = nat.FORCE_BLOCKS_128 | plain
+    A, b = f128_model(259, 132)[:2]
+    x0, _, i0, _ = abi_dense(A, b, reserved=force, **F128_KW)
+    x1, _, i1, _ = abi_dense(A, b, reserved=force, **F128_KW)
+    assert torch.equal(bits(x0), bits(x1)) and i0 == i1        # two forced solves are bitwise equal
+    for tag, plan in plans(("a", "b", "x")):                   # as at 64: the layout does not change a bit
+        if tag == "natural" or not (tag.startswith("all-") or tag.endswith("-pitched")):
+            continue
+        x, res, info, ops = abi_dense(A, b, plan=plan, reserved=force, **F128_KW)
+        for name, p in ops.items():
+            p.check(written=(name == "x"))
+        assert torch.equal(bits(x), bits(x0)) and info == i0, tag
+    for bad in (force | 2, force | 4, force | 0x7f00):
+        x, res, _, ops = abi_dense(A, b, plan=dict(x="pitched"), reserved=bad, expect=nat.LASSO_ERR_BAD_ARG, **F128_KW)
+        assert (ops["x"].buffer == SENTINEL).all(), bad
+        for name, p in ops.items():
+            p.check(written=False)
+
+
+def test_block_side_rule_at_its_threshold():
+    """the smallest [n, 260] product that takes 128-blocks by itself: 3 column blocks, ceil(2 CUs / 3) row blocks, the
+    last of them 91 rows.  The solve is unforced."""
+    from lasso_amd import _native as nat
+    L = nat.lib()
+    cus = C.c_int(0)
+    nat.check(L.lasso_hip_device_cus(C.byref(cus)))
+    k = 260
+    rb = -(-2 * cus.value // 3)
+    n = 128 * (rb - 1) + 91
+    ldmax = max(k, k)                                          # as csrc/conjgrad.hip takes it: lda = k
+    assert L.lasso_solver_block_side(n, k, ldmax) == 128
+    assert L.lasso_solver_block_side(n - 128, k, ldmax) == 64
+    assert L.lasso_solver_block_side(n, k, 1 << 22) == 64      # a row pitch beyond the 32-bit block offsets
+    print("block_side threshold: %d CUs, n = %d" % (cus.value, n))
+    reference = f128_model(n, k, maxiter=3)
+    for plain in (0, 1):
+        x, res, info, _ = abi_dense(reference[0], reference[1], reserved=plain, **dict(F128_KW, maxiter=3))
+        check_f128("threshold_%dx%d_%s" % (n, k, "plain" if plain else "fused"), x, info, reference, iterations=3)

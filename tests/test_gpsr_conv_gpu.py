@@ -61,11 +61,12 @@ def test_golden_case(cases, name):
         assert not z.any()
 
 
-def against_model(tag, x, w, tau, z0=None, **kw):
-    bars, gaps, z_m, info_m = z_bar(x, w, tau, z0=z0, **kw)
+def against_model(tag, x, w, tau, z0=None, solve=None, model=None, **kw):
+    """solve: hip (the Python entry point) or a function of its arguments; model: z_bar's tuple, where it is shared"""
+    bars, gaps, z_m, info_m = model or z_bar(x, w, tau, z0=z0, **kw)
     for fn, bound, f in info_m["decisions"]:          # the model's branches are not within rounding of flipping
         assert abs(fn - bound) >= 1e-4 * abs(f), (tag, fn, bound, f)
-    z, info = hip(x, w, tau, z0=z0, **kw)
+    z, info = (solve or hip)(x, w, tau, z0=z0, **kw)
     assert info["iterations"] == info_m["iterations"], tag
     assert info["trials"] == info_m["trials"], tag
     dev = dict(z=float((z.cpu() - z_m).abs().max()), lam=max_rel(info["accepted_lambda"], info_m["accepted_lambda"]),
@@ -251,8 +252,9 @@ def test_c_abi_guards_z0_untouched_and_bad_arg_writes_nothing():
     ws = torch.empty(L.lasso_conv_gpsr_workspace_bytes(*geom), dtype=torch.uint8, device="cuda")
     stream = nat.stream_ptr(xg.device)
 
-    def solve(g, stop_criterion=3):
+    def solve(g, stop_criterion=3, reserved=0):
         opt, res = nat.GpsrOptions(), nat.GpsrResult()
+        opt.reserved = reserved
         opt.stop_criterion, opt.maxiter, opt.miniter, opt.tol = stop_criterion, 4, 5, 0.0
         opt.mu, opt.lambda_backtrack, opt.first_tau_factor, opt.tol_debias = 0.1, 0.5, -1.0, 1e-4
         st = L.lasso_conv_gpsr_solve(nat.ptr(xg), nat.ptr(wg), nat.ptr(z0), z_out.data_ptr(), *g, nat.LASSO_F32, 0.3,
@@ -262,6 +264,9 @@ def test_c_abi_guards_z0_untouched_and_bad_arg_writes_nothing():
     bad = geom[:5] + (10,) + geom[6:]
     assert solve(bad)[0] == nat.LASSO_ERR_BAD_ARG
     assert solve(geom, stop_criterion=9)[0] == nat.LASSO_ERR_BAD_ARG
+    for bad in (2, 4, 0x7f00):                                          # bits 0 and 3 are the defined ones
+        for defined in (0, 1, nat.FORCE_BLOCKS_128, 1 | nat.FORCE_BLOCKS_128):
+            assert solve(geom, reserved=defined | bad)[0] == nat.LASSO_ERR_BAD_ARG, (defined, bad)
     assert bool((buf == 777.0).all())                                   # nothing was written
     st, res = solve(geom)
     assert st == nat.LASSO_OK and res.n_iter == 4
@@ -305,3 +310,79 @@ def test_verbose_lines_match_the_reference_and_the_model(cases):
         assert any("Iter =" in a for a in l1) == (name == "debias")
         for a, b in zip(l1, l2):
             assert same_line(a, b), (name, a, b)
+
+
+# ---- the "patches" form on 128 x 128 GEMM blocks, forced (LASSO_FORCE_BLOCKS_128) -------------------------------------------
+# block_side() takes 128-blocks only from 2 x CUs blocks on, far above any geometry here.  Bit 0 | bit 3 of reserved:
+# the general form with both of its products -- [M, K] over the patch matrix (the epilogue modes of DESIGN 3.8) and the
+# transposed STORE into COLSt [C kh kw, M] -- on Tile<128, 128>.  K130 has M = 260, K = 130, C kh kw = 27: ragged last
+# blocks in both.
+def abi_solve(x, w, tau, z0=None, reserved=0, stride=1, padding=0, stop_criterion=3, tol=1e-2, maxiter=1000, miniter=5,
+              init=0, continuation=False, debias=False, **kwargs):
+    """lasso_conv_gpsr_solve directly (`reserved` bits other than bit 0 are not reachable from Python), z between guard
+    bands; the request and the report are the Python entry point's own -> (z on the CPU, info)"""
+    from lasso_amd import _native as nat
+    from lasso_amd.conv2d import gpsr as py
+    opt = dict(py._KW_DEFAULTS, **kwargs)
+    (sh, sw), (ph, pw) = py._pair(stride), py._pair(padding)
+    (N, Cin, H, W), (K, _, kh, kw) = x.shape, w.shape
+    Hz, Wz = (H + 2 * ph - kh) // sh + 1, (W + 2 * pw - kw) // sw + 1
+    geom = (N, Cin, H, W, K, Hz, Wz, kh, kw, sh, sw, ph, pw)
+    xg, wg, z0g = x.cuda(), w.cuda(), None if z0 is None else z0.cuda()
+    nz, guard = N * K * Hz * Wz, 64
+    buf = torch.full((nz + 2 * guard,), 777.0, device="cuda")
+    options, res, keep = py._request(stop_criterion, tol, maxiter, miniter, init, continuation, debias, opt, z0 is not None)
+    options.reserved = reserved
+    L = nat.lib()
+    form = L.lasso_conv_gpsr_form(*geom, reserved).decode()
+    ws = torch.empty(L.lasso_conv_gpsr_workspace_bytes(*geom), dtype=torch.uint8, device="cuda")
+    nat.check(L.lasso_conv_gpsr_solve(nat.ptr(xg), nat.ptr(wg), nat.ptr(z0g), buf[guard:].data_ptr(), *geom, nat.LASSO_F32,
+                                      float(tau), C.byref(options), C.byref(res), nat.ptr(ws), ws.numel(),
+                                      nat.stream_ptr(xg.device)))
+    torch.cuda.synchronize()
+    assert bool((buf[:guard] == 777.0).all()) and bool((buf[guard + nz:] == 777.0).all())
+    assert torch.equal(xg.cpu(), x) and torch.equal(wg.cpu(), w) and res.flags == 0
+    info = py._report(res, keep, stop_criterion, tol, debias, opt, 0)
+    info["form"] = form
+    return buf[guard:guard + nz].view(N, K, Hz, Wz).cpu(), info
+
+
+F128 = ("K33", "K130", "stride2_pad")
+
+
+@pytest.mark.parametrize("tag", F128)
+def test_forced_128_blocks_patches_form_against_the_model(tag):
+    from lasso_amd import _native as nat
+    assert nat.FORCE_BLOCKS_128 == 8
+    reserved = 1 | nat.FORCE_BLOCKS_128
+    N, Cc, H, W, K, ks, s, p = FRESH[tag]
+    x, w = conv_inputs((N, Cc, H, W), K, ks, seed=40 + len(tag) + K, unit_norm=ks * ks * Cc > 1)
+    kw = dict(stride=s, padding=p, maxiter=5, tol=0.0)
+    solve = lambda x, w, tau, z0=None, **kw: abi_solve(x, w, tau, z0=z0, reserved=reserved, **kw)      # noqa: E731
+    z, info = against_model(tag + "_f128", x, w, 0.3, solve=solve, **kw)
+    assert info["form"] == "patches"
+    again, info2 = abi_solve(x, w, 0.3, reserved=reserved, **kw)
+    assert torch.equal(z, again) and info == info2     # two forced solves are bitwise equal
+    if tag == "K130":
+        M, ckk = z.shape[0] * z.shape[2] * z.shape[3], Cc * ks * ks
+        assert (M, K, ckk) == (260, 130, 27)
+        z64, info64 = abi_solve(x, w, 0.3, reserved=1, **kw)
+        print("K130: forced 128-blocks bitwise the 64-block solve:", torch.equal(z, z64),
+              "max|dz| %.3g" % float((z - z64).abs().max()))
+
+
+def test_forced_128_blocks_a_ladder_of_trials_continuation_and_debias():
+    """rungs (blockIdx.z, a_stride) decided on 128-blocks, the continuation's steps and the debias CG: K130's geometry"""
+    reserved = 9
+    N, Cc, H, W, K, ks, s, p = FRESH["K130"]
+    x, w = conv_inputs((N, Cc, H, W), K, ks, seed=40 + 4 + K)
+    geo = dict(stride=s, padding=p)
+    solve = lambda x, w, tau, z0=None, **kw: abi_solve(x, w, tau, z0=z0, reserved=reserved, **kw)      # noqa: E731
+    kw = dict(maxiter=6, tol=0.0, mu=0.95, lambda_backtrack=0.6, **geo)
+    model = z_bar(x, w, 0.4, **kw)
+    assert max(model[3]["trials"]) > 1                 # the ladder runs
+    against_model("K130_ladder_f128", x, w, 0.4, solve=solve, model=model, **kw)
+    against_model("K130_cont_f128", x, w, 0.4, solve=solve, continuation=True, cont_steps=2, first_tau_factor=2.0, maxiter=4,
+                  tol=0.0, **geo)
+    z, info = against_model("K130_debias_f128", x, w, 1.5, solve=solve, maxiter=6, tol=0.0, debias=True, maxiter_debias=5, **geo)
+    assert info["iterations"] == 6 + 6 and 0 < int((z != 0).sum()) <= x.numel()      # the CG ran: 6 steps

@@ -66,11 +66,12 @@ def test_symbols_declared_and_exported():
     from lasso_amd import _native
     text = open(os.path.join(ROOT, "include", "lasso_hip.h")).read()
     for name in ("lasso_gpsr_workspace_bytes", "lasso_gpsr_solve", "lasso_gpsr_options", "lasso_gpsr_result",
-                 "lasso_gpsr_trace"):
+                 "lasso_gpsr_trace", "lasso_solver_block_side", "#define LASSO_FORCE_BLOCKS_128 8"):
         assert name in text, name
     assert "#define LASSO_HIP_ABI_VERSION 7" in text          # additive: the version stays
     lib = ctypes.CDLL(_native.lib_path())
     assert hasattr(lib, "lasso_gpsr_workspace_bytes") and hasattr(lib, "lasso_gpsr_solve")
+    assert hasattr(lib, "lasso_solver_block_side") and _native.FORCE_BLOCKS_128 == 8
     L = _native.lib()
     small = L.lasso_gpsr_workspace_bytes(64, 32, 128, _native.LASSO_F32)
     assert small > 10 * 64 * 128 * 4

@@ -8,6 +8,7 @@ same rule as for z -- 4 x the relative gap between the model's float32 and float
 (the step is a ratio of two batch-wide sums over a changing support: config 2's shape at 20 iterations moves it by
 1.0e-5 through rounding alone).  Measured gaps and achieved deviations go to parity_margins.json through
 tests/margins.py."""
+import ctypes as C
 import io
 import sys
 import warnings
@@ -19,6 +20,7 @@ import torch
 
 import gpsr_model
 from gpsr_cases import CASES, case_inputs, check_against_golden, load_case, same_line, z_bar
+from layouts import SENTINEL, place
 from margins import record_margins
 from recipes import recipe_xw
 
@@ -57,11 +59,12 @@ def test_golden_case(cases, name):
 FRESH = [(37, 10, 50), (64, 256, 1024), (130, 128, 512), (40, 300, 70), (24, 96, 1300)]
 
 
-def against_model(tag, x, w, tau, x0=None, **kw):
-    bar, gap, z_m, info_m = z_bar(x, w, tau, x0=x0, **kw)
+def against_model(tag, x, w, tau, x0=None, solve=None, model=None, **kw):
+    """solve: hip (the Python entry point) or a function of its arguments; model: z_bar's tuple, where it is shared"""
+    bar, gap, z_m, info_m = model or z_bar(x, w, tau, x0=x0, **kw)
     for fn, bound, f in info_m["decisions"]:          # the model's branches are not within rounding of flipping
         assert abs(fn - bound) >= 1e-4 * abs(f), (tag, fn, bound, f)
-    z, info = hip(x, w, tau, x0=x0, **kw)
+    z, info = (solve or hip)(x, w, tau, x0=x0, **kw)
     assert info["iterations"] == info_m["iterations"], tag
     assert info["trials"] == info_m["trials"], tag
     np.testing.assert_allclose(info["objective"], info_m["objective"], rtol=1e-6, err_msg=tag)
@@ -241,3 +244,139 @@ def test_line_search_that_cannot_succeed_ends_with_a_warning():
     with pytest.warns(UserWarning, match="line search failed"):
         z_m, info_m = gpsr_model.gpsr_basic(x, w, 0.1, maxiter=5, return_info=True)
     assert info_m["iterations"] == 0 and not z_m.any()
+
+
+# ---- the C ABI directly: 128 x 128 GEMM blocks, forced (LASSO_FORCE_BLOCKS_128) and chosen ----------------------------------
+# block_side() takes 128-blocks only from 2 x CUs blocks on (256 CUs: 8.4 M elements of the product), far above the
+# shapes of this file.  The bit runs every product of the solve -- and so every epilogue mode of DESIGN 3.8, the ladder's
+# rungs in blockIdx.z included -- on Tile<128, 128> at shapes with more than one 128-block in a dimension and a nearly
+# empty last one; the contraction lengths give the three operand forms (a multiple of 32: LDS-DMA, of 4: 16-byte loads,
+# odd: scalar loads) of both product kinds.
+def abi_solve(x, w, tau, x0=None, reserved=0, layout="natural", refused=None, stop_criterion=3, tol=1e-2, maxiter=1000,
+              miniter=5, init=0, continuation=False, debias=False, **kwargs):
+    """lasso_gpsr_solve directly: `reserved` and pitched / offset operands are not reachable from Python.  The request
+    and the report are the Python entry point's own -> (z on the CPU, info).  refused: the status a refusal must have;
+    nothing may have been written then"""
+    from lasso_amd import _native as nat
+    from lasso_amd.linear.solvers import gpsr as py
+    opt = dict(py._KW_DEFAULTS, **kwargs)
+    n, d = x.shape
+    k = w.shape[1]
+    nan = float("nan")
+    ops = [place(t, layout, nan, "cuda", nm) for t, nm in ((x, "x"), (w, "w")) + (((x0, "z0"),) if x0 is not None else ())]
+    out = place(torch.zeros(n, k), layout, SENTINEL, "cuda", "z", fill=SENTINEL)
+    options, res, keep = py._request(stop_criterion, tol, maxiter, miniter, init, continuation, debias, opt, x0 is not None)
+    options.reserved = reserved
+    L = nat.lib()
+    dev = torch.device("cuda", torch.cuda.current_device())
+    ws = torch.empty(L.lasso_gpsr_workspace_bytes(n, d, k, nat.LASSO_F32), dtype=torch.uint8, device="cuda")
+    z0p = ops[2] if x0 is not None else None
+    status = L.lasso_gpsr_solve(nat.ptr(ops[0].view), ops[0].ld, nat.ptr(ops[1].view), ops[1].ld,
+                                nat.ptr(z0p.view) if z0p else None, z0p.ld if z0p else 0, nat.ptr(out.view), out.ld, n, d, k,
+                                nat.LASSO_F32, float(tau), C.byref(options), C.byref(res), nat.ptr(ws), ws.numel(),
+                                nat.stream_ptr(dev))
+    torch.cuda.synchronize()
+    for p in ops:
+        p.check()
+    if refused is not None:
+        assert status == refused, (status, refused)
+        out.check(written=False)
+        return out.view.cpu(), None
+    nat.check(status)
+    out.check(written=True)
+    assert res.flags == 0, res.flags
+    return out.view.cpu(), py._report(res, keep, stop_criterion, tol, debias, opt, 0)
+
+
+def forced(reserved, layout="natural"):
+    return lambda x, w, tau, x0=None, **kw: abi_solve(x, w, tau, x0=x0, reserved=reserved, layout=layout, **kw)
+
+
+F128 = [(130, 64, 288), (259, 36, 132), (131, 37, 131), (40, 200, 136), (1, 40, 24)]
+F128_KW = dict(maxiter=5, tol=0.0)
+_F128_MODEL = {}
+
+
+def f128_problem(shape, tau=0.4, **kw):
+    """a problem of this section and its model (z_bar), computed once -> (x, w, model)"""
+    key = (shape, tau, tuple(sorted(kw.items())))
+    if key not in _F128_MODEL:
+        n, d, k = shape
+        x, w = recipe_xw(n, d, k, seed=20 + n)
+        _F128_MODEL[key] = (x, w, z_bar(x, w, tau, **kw))
+    return _F128_MODEL[key]
+
+
+@pytest.mark.parametrize("reserved", [8, 0], ids=["f128", "s64"])
+@pytest.mark.parametrize("shape", F128, ids=lambda s: "x".join(map(str, s)))
+def test_forced_128_blocks_against_the_model(shape, reserved):
+    from lasso_amd import _native as nat
+    assert nat.FORCE_BLOCKS_128 == 8
+    x, w, model = f128_problem(shape, **F128_KW)
+    against_model("%dx%dx%d_%s" % (shape + ("f128" if reserved else "s64",)), x, w, 0.4, solve=forced(reserved), model=model,
+                  **F128_KW)
+
+
+@pytest.mark.parametrize("reserved", [8, 0], ids=["f128", "s64"])
+def test_forced_128_blocks_continuation_debias_and_a_ladder_of_trials(reserved):
+    """the epilogue modes of the continuation steps and of the debias CG, and a line search whose rungs (blockIdx.z,
+    a_stride) are decided on 128-blocks"""
+    sfx = "_f128" if reserved else "_s64"
+    # (two solves: a tau at which the continuation's first steps still decrease the objective by more than rounding
+    # leaves more nonzeros than debias accepts)
+    kw = dict(maxiter=6, tol=0.0, continuation=True, cont_steps=3, first_tau_factor=3.0)
+    x, w, model = f128_problem((131, 37, 131), tau=0.5, **kw)
+    z, info = against_model("cont_131x37x131" + sfx, x, w, 0.5, solve=forced(reserved), model=model, **kw)
+    assert info["iterations"] == len(info["objective"]) == 8       # steps of 1, 1 and 6 iterations
+    kw = dict(maxiter=6, tol=0.0, debias=True, maxiter_debias=5)
+    x, w, model = f128_problem((131, 37, 131), tau=1.2, **kw)
+    z, info = against_model("debias_131x37x131" + sfx, x, w, 1.2, solve=forced(reserved), model=model, **kw)
+    assert info["iterations"] == 6 + 6 and 0 < int((z != 0).sum()) <= x.numel()      # the CG ran: 6 steps on the support
+    kw = dict(maxiter=7, tol=0.0, mu=0.95, lambda_backtrack=0.6)
+    x, w, model = f128_problem((259, 36, 132), **kw)
+    assert max(model[3]["trials"]) > 1                 # the ladder runs
+    against_model("ladder_259x36x132" + sfx, x, w, 0.4, solve=forced(reserved), model=model, **kw)
+
+
+def test_forced_128_blocks_pitched_repeatable_and_refused():
+    from lasso_amd import _native as nat
+    force = nat.FORCE_BLOCKS_128
+    shape = (259, 36, 132)
+    x, w, model = f128_problem(shape, **F128_KW)
+    a, ia = abi_solve(x, w, 0.4, reserved=force, **F128_KW)
+    b, ib = abi_solve(x, w, 0.4, reserved=force, **F128_KW)
+    assert torch.equal(a, b) and ia == ib              # two forced solves are bitwise equal
+    p, ip = abi_solve(x, w, 0.4, reserved=force, layout="pitched", **F128_KW)
+    assert torch.equal(p, a) and ip == ia              # the same kernels on another pitch: not a bit moves
+    for layout in ("odd", "offset"):                   # the scalar loads: another order in the contraction
+        z, _ = against_model("259x36x132_%s_f128" % layout, x, w, 0.4, solve=forced(force, layout), model=model, **F128_KW)
+        print(layout, "bitwise the natural forced solve:", torch.equal(z, a))
+    for bad in (force | 1, force | 2, force | 4, force | 0x7f00, 1):     # dense GPSR defines no other bit
+        z, _ = abi_solve(x, w, 0.4, reserved=bad, refused=nat.LASSO_ERR_BAD_ARG, **F128_KW)
+        assert (z == SENTINEL).all(), bad
+
+
+def device_cus():
+    from lasso_amd import _native as nat
+    cus = C.c_int(0)
+    nat.check(nat.lib().lasso_hip_device_cus(C.byref(cus)))
+    return cus.value
+
+
+def test_block_side_rule_at_its_threshold():
+    """the smallest [n, 260] product that takes 128-blocks by itself: 3 column blocks, ceil(2 CUs / 3) row blocks, the
+    last of them 91 rows; its [n, 32] products stay on 64-blocks (the mixed case).  The solve is unforced."""
+    from lasso_amd import _native as nat
+    L = nat.lib()
+    cus = device_cus()
+    d, k = 32, 260
+    rb = -(-2 * cus // 3)
+    n = 128 * (rb - 1) + 91
+    ldmax_k, ldmax_d = max(d, k, d), max(d, k, d, k)   # as csrc/gpsr.hip takes them: ldx = d, ldw = k
+    assert L.lasso_solver_block_side(n, k, ldmax_k) == 128
+    assert L.lasso_solver_block_side(n - 128, k, ldmax_k) == 64
+    assert L.lasso_solver_block_side(n, d, ldmax_d) == 64
+    assert L.lasso_solver_block_side(n, k, 1 << 22) == 64                 # a row pitch beyond the 32-bit block offsets
+    print("block_side threshold: %d CUs, n = %d" % (cus, n))
+    x, w = recipe_xw(n, d, k, seed=41)
+    against_model("threshold_%dx%dx%d" % (n, d, k), x, w, 0.4, solve=forced(0), maxiter=3, tol=0.0)

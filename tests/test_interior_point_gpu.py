@@ -278,7 +278,7 @@ def test_nan_in_one_row_of_x_stays_in_that_row(cases):
 
 
 # ---- the C ABI directly --------------------------------------------------------------------------------------------------
-def abi_solve(x, w, z0, alpha, maxiter, layout="natural", tol=0.0, reserved=0, shape=None):
+def abi_solve(x, w, z0, alpha, maxiter, layout="natural", tol=0.0, reserved=0, shape=None, trace=None):
     """lasso_interior_point_solve directly: `reserved` and pitched / offset operands are not reachable from Python
     -> (status, z on the CPU, result struct)"""
     from lasso_amd import _native as nat
@@ -289,6 +289,8 @@ def abi_solve(x, w, z0, alpha, maxiter, layout="natural", tol=0.0, reserved=0, s
     pz = place(torch.zeros(n, k), layout, SENTINEL, device="cuda", name="z", fill=SENTINEL)
     opts = nat.InteriorPointOptions(maxiter, 0, 0.1, tol, 1e-5, reserved)
     res = nat.InteriorPointResult()
+    if trace is not None:
+        res.trace = C.pointer(trace)
     L = nat.lib()
     ws = torch.empty(max(L.lasso_interior_point_workspace_bytes(n, d, k, nat.LASSO_F32), 16), dtype=torch.uint8, device="cuda")
     dd, kk = shape or (d, k)
@@ -328,3 +330,79 @@ def test_refusals_of_the_c_abi_write_nothing():
     assert status == nat.LASSO_ERR_UNSUPPORTED and (z == SENTINEL).all()
     status, z, res = abi_solve(x, w, torch.zeros_like(z0), 0.3, 1)      # not interior: refused after the start pass
     assert status == nat.LASSO_ERR_BAD_ARG and res.status == nat.INTERIOR_POINT_BAD_START and (z == SENTINEL).all()
+
+
+# ---- 128 x 128 GEMM blocks, forced (LASSO_FORCE_BLOCKS_128) ---------------------------------------------------------------
+# block_side() takes 128-blocks only from 2 x CUs blocks on, far above any shape here: the bit runs both products of the
+# solve ([n,d] x W on W^T and [n,k] x W^T, StoreEpi) on Tile<128, 128>.  Shapes: more than one 128-block in a dimension
+# and a nearly empty last one; contraction lengths for the three operand forms (a multiple of 32: LDS-DMA, of 4: 16-byte
+# loads, odd: scalar loads) of both products.
+F128 = [(130, 64, 288, 0.3, 3), (259, 36, 132, 0.3, 3), (131, 37, 131, 0.3, 3), (40, 200, 136, 0.3, 3), (1, 40, 24, 0.3, 3)]
+_F128_MODEL = {}
+
+
+def f128_model(n, d, k, alpha, maxiter):
+    """the fresh-shape construction above, computed once per shape -> (x, w, z0, z64, i32, i64, bar, gap)"""
+    key = (n, d, k)
+    if key not in _F128_MODEL:
+        x, w = recipe_xw(n, d, k, seed=22)
+        z0 = ridge_start(x, w, alpha)
+        kw = dict(alpha=alpha, maxiter=maxiter, tol=0.0)
+        z32, _, i32 = interior_point_model.interior_point(x, w, z0, **kw)
+        z64, _, i64 = interior_point_model.interior_point(x, w, z0, dtype=torch.float64, **kw)
+        gap = float((z32.double() - z64).abs().max())
+        _F128_MODEL[key] = (x, w, z0, z64, i32, i64, 4.0 * gap, gap)
+    return _F128_MODEL[key]
+
+
+def abi_solve_traced(x, w, z0, alpha, maxiter, layout="natural", reserved=0):
+    """abi_solve with the per-iteration records -> (status, z, result struct, {obj, prim_feas, dual_feas, gap})"""
+    from lasso_amd import _native as nat
+    arrays = [(C.c_double * max(maxiter, 1))() for _ in range(4)]
+    trace = nat.InteriorPointTrace(maxiter, 0, *arrays)
+    status, z, res = abi_solve(x, w, z0, alpha, maxiter, layout, reserved=reserved, trace=trace)
+    its = min(res.n_iter, maxiter) if status == 0 else 0
+    return status, z, res, {key: list(a[:its]) for key, a in zip(("obj", "prim_feas", "dual_feas", "gap"), arrays)}
+
+
+@pytest.mark.parametrize("reserved", [8, 0], ids=["f128", "s64"])
+@pytest.mark.parametrize("n,d,k,alpha,maxiter", F128)
+def test_forced_128_blocks_against_the_model(n, d, k, alpha, maxiter, reserved):
+    from lasso_amd import _native as nat
+    assert nat.FORCE_BLOCKS_128 == 8
+    x, w, z0, z64, i32, i64, bar, gap = f128_model(n, d, k, alpha, maxiter)
+    status, z, res, info = abi_solve_traced(x, w, z0, alpha, maxiter, reserved=reserved)
+    assert status == 0
+    dz = float((z.double() - z64).abs().max())
+    tag = "%dx%dx%d_%s" % (n, d, k, "f128" if reserved else "s64")
+    print("fresh %s: max|z - z64| = %.3g (bar %.3g)" % (tag, dz, bar))
+    record_margins("interior_point/fresh_" + tag, dict(dz=dz, bar=bar, gap=gap))
+    assert res.n_iter == maxiter and res.status == nat.INTERIOR_POINT_MAXITER
+    assert dz <= bar
+    for key in ("obj", "prim", "gap"):                       # the records, as test_fresh_shape_against_the_model
+        want, got = np.array(i64[INFO_KEYS[key]]), np.array(info[INFO_KEYS[key]])
+        model = np.array(i32[INFO_KEYS[key]])
+        floor = 4.0 * float(torch.finfo(torch.float32).eps) * float(x.abs().max()) if key == "prim" else 0.0
+        assert (np.abs(got - want) <= np.maximum(np.maximum(4.0 * np.abs(model - want), 1e-5 * np.abs(want)), floor)).all(), key
+
+
+def test_forced_128_blocks_pitched_repeatable_and_refused():
+    from lasso_amd import _native as nat
+    n, d, k, alpha, maxiter = F128[1]
+    x, w, z0, z64, _, _, bar, _ = f128_model(n, d, k, alpha, maxiter)
+    force = nat.FORCE_BLOCKS_128
+    _, a, _, ia = abi_solve_traced(x, w, z0, alpha, maxiter, reserved=force)
+    _, b, _, ib = abi_solve_traced(x, w, z0, alpha, maxiter, reserved=force)
+    assert torch.equal(a, b) and ia == ib                     # two forced solves are bitwise equal
+    margins = {}
+    for layout in ("pitched", "odd", "offset"):
+        status, z, res = abi_solve(x, w, z0, alpha, maxiter, layout, reserved=force)
+        assert status == 0 and res.n_iter == maxiter
+        margins[layout] = float((z.double() - z64).abs().max())
+        print("f128 %s: max|z - z64| = %.3g (bar %.3g), bitwise the natural forced solve: %s" % (layout, margins[layout], bar,
+                                                                                                torch.equal(z, a)))
+    record_margins("interior_point/layouts_%dx%dx%d_f128" % (n, d, k), dict(bar=bar, **margins))
+    assert max(margins.values()) <= bar
+    for bad in (force | 1, force | 4, force | (1 << 40)):
+        status, z, _ = abi_solve(x, w, z0, alpha, 1, reserved=bad)
+        assert status == nat.LASSO_ERR_BAD_ARG and (z == SENTINEL).all(), bad

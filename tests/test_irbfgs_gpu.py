@@ -263,26 +263,40 @@ def test_two_identical_calls_are_bitwise_equal(line_search):
     assert set(a[1]) == {"iterations", "t", "ls_iters", "objective", "delta_x", "invalid_rows", "lu", "evaluations"}
 
 
-def abi_solve(w, x, z0, alpha, line_search, maxiter, lr, xtol, plan):
-    """lasso_irbfgs_solve directly, every operand placed by tests/layouts.py -> (z on the CPU, result struct)"""
+def abi_solve(w, x, z0, alpha, line_search, maxiter, lr, xtol, plan, reserved=0, refused=None):
+    """lasso_irbfgs_solve directly, every operand placed by tests/layouts.py -> (z on the CPU, result struct); the
+    result carries the per-iteration trace as res.objective and res.invalid_rows.  refused: the status a refusal must
+    have; nothing may have been written then"""
     from lasso_amd import _native as nat
     n, d = x.shape
     k = w.shape[1]
     ops = dict(x=place(x, plan["x"], float("nan"), "cuda", "x"), w=place(w, plan["w"], float("nan"), "cuda", "w"),
                z0=place(z0, plan["z0"], float("nan"), "cuda", "z0"))
     out = place(torch.zeros(n, k), plan["z"], -7.25, "cuda", "z", fill=-7.25)
-    opts = nat.IrbfgsOptions(maxiter, 1 if line_search else 0, lr, xtol, 1e-4, EPS, 0)
+    opts = nat.IrbfgsOptions(maxiter, 1 if line_search else 0, lr, xtol, 1e-4, EPS, reserved)
     res = nat.IrbfgsResult()
+    cap = max(maxiter, 1)
+    t_arr, f_arr, dx_arr = ((C.c_double * cap)() for _ in range(3))
+    ls_arr, inv_arr, lu_arr = ((C.c_int32 * cap)() for _ in range(3))
+    trace = nat.IrbfgsTrace(cap, 0, t_arr, ls_arr, f_arr, dx_arr, inv_arr, lu_arr, None, None, None, 0)
+    res.trace = C.pointer(trace)
     L = nat.lib()
     ws = torch.empty(L.lasso_irbfgs_workspace_bytes(n, d, k, nat.LASSO_F32), dtype=torch.uint8, device="cuda")
-    nat.check(L.lasso_irbfgs_solve(nat.ptr(ops["x"].view), ops["x"].ld, nat.ptr(ops["w"].view), ops["w"].ld,
-                                   nat.ptr(ops["z0"].view), ops["z0"].ld, nat.ptr(out.view), out.ld, n, d, k, nat.LASSO_F32,
-                                   alpha, C.byref(opts), C.byref(res), nat.ptr(ws), ws.numel(),
-                                   nat.stream_ptr(torch.device("cuda", 0))))
+    status = L.lasso_irbfgs_solve(nat.ptr(ops["x"].view), ops["x"].ld, nat.ptr(ops["w"].view), ops["w"].ld,
+                                  nat.ptr(ops["z0"].view), ops["z0"].ld, nat.ptr(out.view), out.ld, n, d, k, nat.LASSO_F32,
+                                  alpha, C.byref(opts), C.byref(res), nat.ptr(ws), ws.numel(),
+                                  nat.stream_ptr(torch.device("cuda", 0)))
     torch.cuda.synchronize()
     for p in ops.values():
         p.check()
+    if refused is not None:
+        assert status == refused, (status, refused)
+        out.check(written=False)
+        return out.view.cpu(), res
+    nat.check(status)
     out.check(written=True)
+    its = min(res.n_iter, cap)
+    res.objective, res.invalid_rows, res.lu = list(f_arr[:its]), list(inv_arr[:its]), list(lu_arr[:its])
     return out.view.cpu(), res
 
 
@@ -335,3 +349,84 @@ def test_edges_no_rows_cpu_tensors_and_grad_inputs():
     # the default maxiter is 5 k and the default xtol stops it
     zd, info = iterative_ridge_bfgs(rss(x.cuda(), w.cuda()), z0.cuda(), alpha=0.3, return_info=True)
     assert 1 <= info["iterations"] <= 5 * 24
+
+
+# ---- 128 x 128 GEMM blocks, forced (LASSO_FORCE_BLOCKS_128) ---------------------------------------------------------------
+# block_side() takes 128-blocks only from 2 x CUs blocks on, far above any shape here: the bit runs both products of the
+# solve (the residual with its block partials, Resid0Epi, and the gradient r W on W^T, StoreEpi) on Tile<128, 128>.
+# Shapes: more than one 128-block in a dimension and a nearly empty last one; contraction lengths for the three operand
+# forms (a multiple of 32: LDS-DMA, of 4: 16-byte loads, odd: scalar loads) of both products.  The golden cases'
+# dictionary, start and fixed-step arguments (fixed4_*); n = 1 takes the dense start (the sparse one zeroes the last row).
+# The data is x = z0 W^T + 1e-6 noise, so the batch-wide |grad|_1 of the start is below 1 and the first step is lr: with
+# the recipe's x a batch this large starts with t = lr / |grad|_1 ~ 1e-5, the first pair (s, y) is a difference of nearly
+# equal float32 numbers, and the model's own summation orders end 1e-2 apart in the codes -- nothing to compare with.
+F128 = [(130, 64, 288), (259, 36, 132), (131, 37, 131), (40, 200, 136), (1, 40, 24)]
+F128_KW = dict(alpha=0.1, line_search=False, lr=0.3, maxiter=3)
+NATURAL = {nm: "natural" for nm in ("x", "w", "z0", "z")}
+_F128_MODEL = {}
+
+
+def f128_model(n, d, k):
+    """the model in float32, and how far other correct implementations move its codes and objective (the golden
+    generator's measure, here with one other summation order and float64: the spread stays a hundredth of the floor) -> (x, w, z0, z32, i32, bar, spread_z, objective rtol)"""
+    key = (n, d, k)
+    if key not in _F128_MODEL:
+        _, w, z0 = case_inputs(dict(n=n, d=d, k=k, seed=0, start="sparse" if n > 1 else "dense"))
+        x = z0 @ w.T + 1e-6 * torch.randn(n, d, generator=torch.Generator().manual_seed(77))
+        assert float(((z0 @ w.T - x) @ w).abs().sum()) <= 1.0
+        z32, i32 = irbfgs_model.iterative_ridge_bfgs(w, x, z0, **F128_KW)
+        irbfgs_model.assert_robust(i32)
+        others = [irbfgs_model.iterative_ridge_bfgs(w, x, z0, order_seed=sd, **F128_KW) for sd in (1,)]
+        others.append(irbfgs_model.iterative_ridge_bfgs(w, x, z0, dtype=torch.float64, **F128_KW))
+        for _, info in others:
+            assert info["iterations"] == i32["iterations"] == F128_KW["maxiter"] and min(i32["delta_x"]) > 0.05
+            assert info["invalid_rows"] == i32["invalid_rows"]
+        spread_z = max(float((z.double() - z32.double()).abs().max()) for z, _ in others)
+        spread_f = max(abs(info["objective"][-1] - i32["objective"][-1]) / abs(i32["objective"][-1]) for _, info in others)
+        assert spread_z <= 2.5e-3, "a case whose codes rounding alone moves: not comparable by its codes"
+        _F128_MODEL[key] = (x, w, z0, z32, i32, max(5e-5, 4.0 * spread_z), spread_z, max(1e-6, 4.0 * spread_f))
+    return _F128_MODEL[key]
+
+
+def check_f128(tag, z, res, model):
+    x, w, z0, z32, i32, bar, spread_z, f_rtol = model
+    dz = float((z - z32).abs().max())
+    f_rel = abs(res.objective[-1] - i32["objective"][-1]) / abs(i32["objective"][-1])
+    print("%s: max|dz| = %.3g (bar %.3g), objective rel %.3g (rtol %.3g)" % (tag, dz, bar, f_rel, f_rtol))
+    record_margins("irbfgs/fresh_" + tag, dict(dz=dz, bar=bar, spread_z=spread_z, objective_rel=f_rel, objective_rtol=f_rtol))
+    assert res.n_iter == i32["iterations"] and res.lu == [0] * res.n_iter
+    assert res.invalid_rows == i32["invalid_rows"][:-1] + [-1]     # (no update follows the last iteration)
+    assert (z[z0 == 0].view(torch.int32) == 0).all()               # frozen zeros stay bitwise zero
+    assert dz <= bar, (tag, dz, bar)
+    assert f_rel <= f_rtol, (tag, f_rel, f_rtol)
+
+
+@pytest.mark.parametrize("reserved", [8, 0], ids=["f128", "s64"])
+@pytest.mark.parametrize("n,d,k", F128)
+def test_forced_128_blocks_against_the_model(n, d, k, reserved):
+    from lasso_amd import _native as nat
+    assert nat.FORCE_BLOCKS_128 == 8
+    model = f128_model(n, d, k)
+    x, w, z0 = model[:3]
+    z, res = abi_solve(w, x, z0, 0.1, False, F128_KW["maxiter"], 0.3, 1e-5, NATURAL, reserved=reserved)
+    check_f128("%dx%dx%d_%s" % (n, d, k, "f128" if reserved else "s64"), z, res, model)
+
+
+def test_forced_128_blocks_pitched_repeatable_and_refused():
+    from lasso_amd import _native as nat
+    model = f128_model(*F128[1])
+    x, w, z0 = model[:3]
+    force = nat.FORCE_BLOCKS_128
+    a, ra = abi_solve(w, x, z0, 0.1, False, F128_KW["maxiter"], 0.3, 1e-5, NATURAL, reserved=force)
+    b, rb = abi_solve(w, x, z0, 0.1, False, F128_KW["maxiter"], 0.3, 1e-5, NATURAL, reserved=force)
+    assert torch.equal(a.view(torch.int32), b.view(torch.int32)) and ra.objective == rb.objective
+    for layout in ("pitched", "odd", "offset"):               # as at 64: the layout does not change a bit
+        got, res = abi_solve(w, x, z0, 0.1, False, F128_KW["maxiter"], 0.3, 1e-5, {nm: layout for nm in NATURAL}, reserved=force)
+        assert res.n_iter == F128_KW["maxiter"]
+        assert torch.equal(got.view(torch.int32), a.view(torch.int32)), layout
+    # the timing bit keeps its meaning next to the force bit
+    t, rt = abi_solve(w, x, z0, 0.1, False, F128_KW["maxiter"], 0.3, 1e-5, NATURAL, reserved=force | nat.IRBFGS_TIME_ROWS)
+    assert torch.equal(t.view(torch.int32), a.view(torch.int32)) and rt.row_ms > 0.0 and ra.row_ms == 0.0
+    for bad in (force | 1, force | 4, force | (1 << 40)):
+        z, _ = abi_solve(w, x, z0, 0.1, False, F128_KW["maxiter"], 0.3, 1e-5, NATURAL, reserved=bad, refused=nat.LASSO_ERR_BAD_ARG)
+        assert (z == -7.25).all(), bad

@@ -74,6 +74,11 @@ def abi_solve(z0, x, w, alpha, maxiter, line_search=False, tol=1e-5, tikhonov=1e
     zb.fill_(-555.0)
     opts = nat.IterRidgeOptions(maxiter, int(line_search), tol, tikhonov, eps, reserved)
     res = nat.IterRidgeResult()
+    cap = max(maxiter, 1)                                     # the per-iteration trace -> res.fval, res.support_max
+    f_arr, u_arr, t_arr, sm_arr = ((C.c_double * cap)() for _ in range(4))
+    ls_arr, sx_arr = (C.c_int32 * cap)(), (C.c_int32 * cap)()
+    trace = nat.IterRidgeTrace(cap, 0, f_arr, u_arr, t_arr, ls_arr, sx_arr, sm_arr, None, None, None, 0)
+    res.trace = C.pointer(trace)
     L = nat.lib()
     ws = torch.empty(L.lasso_iter_ridge_workspace_bytes(n, d, k, nat.LASSO_F32), dtype=torch.uint8, device="cuda")
     status = L.lasso_iter_ridge_solve(C.c_void_p(xv.data_ptr()), ldx, C.c_void_p(wv.data_ptr()), ldw,
@@ -81,6 +86,8 @@ def abi_solve(z0, x, w, alpha, maxiter, line_search=False, tol=1e-5, tikhonov=1e
                                       alpha, C.byref(opts), C.byref(res), nat.ptr(ws), ws.numel(),
                                       nat.stream_ptr(torch.device("cuda", 0)))
     torch.cuda.synchronize()
+    its = min(res.n_iter, cap) if status == 0 else 0
+    res.fval, res.support_max = list(f_arr[:its]), list(sx_arr[:its])
     return status, zv.cpu(), res, dict(x=(xb, x, ldx), w=(wb, w, ldw), z0=(z0b, z0, ldz0), z=(zb, None, ldz))
 
 
@@ -352,3 +359,72 @@ def test_fresh_shape_against_the_model(n, d, k, alpha, maxiter):
     assert dz <= bar
     f64 = i64["fval"][-1]
     assert abs(info["fval"][-1] - f64) / f64 <= max(1e-6, 4.0 * abs(i32["fval"][-1] - f64) / f64)
+
+
+# ---- 128 x 128 GEMM blocks, forced (LASSO_FORCE_BLOCKS_128) ---------------------------------------------------------------
+# block_side() takes 128-blocks only from 2 x CUs blocks on, far above any shape here: the bit runs every product of the
+# solve (StoreEpi for rhs = x W, Resid0Epi for the residual and its block partials) on Tile<128, 128>.  Shapes: more than
+# one 128-block in a dimension and a nearly empty last one; contraction lengths for the three operand forms (a multiple
+# of 32: LDS-DMA, of 4: 16-byte loads, odd: scalar loads) of both products.
+F128 = [(130, 64, 288, 2.0, 4), (259, 36, 132, 2.0, 4), (131, 37, 131, 2.0, 4), (40, 200, 136, 3.0, 3), (1, 40, 24, 2.0, 4)]
+_F128_MODEL = {}
+
+
+def f128_model(n, d, k, alpha, maxiter):
+    """the fresh-shape construction above, computed once per shape: (x, w, z0, z32, model info, bar, gap, f64, f bar)"""
+    key = (n, d, k)
+    if key not in _F128_MODEL:
+        x, w = recipe_xw(n, d, k, seed=22)
+        z0 = ridge_start(x, w, alpha)
+        kw = dict(alpha=alpha, line_search=False, maxiter=maxiter)
+        z32, i32 = iter_ridge_model.iterative_ridge(z0, x, w, **kw)
+        z64, i64 = iter_ridge_model.iterative_ridge(z0, x, w, dtype=torch.float64, **kw)
+        assert min(i32["margin"], i64["margin"]) >= 0.01, "a model stop decision that rounding could flip: choose another seed"
+        assert i32["iterations"] == i64["iterations"] == maxiter
+        gap = float((z32.double() - z64).abs().max())
+        f64 = i64["fval"][-1]
+        _F128_MODEL[key] = (x, w, z0, z32, i32, 4.0 * gap, gap, f64, max(1e-6, 4.0 * abs(i32["fval"][-1] - f64) / f64))
+    return _F128_MODEL[key]
+
+
+@pytest.mark.parametrize("reserved", [8, 0], ids=["f128", "s64"])
+@pytest.mark.parametrize("n,d,k,alpha,maxiter", F128)
+def test_forced_128_blocks_against_the_model(n, d, k, alpha, maxiter, reserved):
+    from lasso_amd import _native as nat
+    assert nat.FORCE_BLOCKS_128 == 8
+    x, w, z0, z32, i32, bar, gap, f64, f_bar = f128_model(n, d, k, alpha, maxiter)
+    status, z, res, _ = abi_solve(z0, x, w, alpha, maxiter, reserved=reserved)
+    assert status == 0 and res.bad_row == -1
+    dz = float((z - z32).abs().max())
+    tag = "%dx%dx%d_%s" % (n, d, k, "f128" if reserved else "s64")
+    print("fresh %s: max|dz| = %.3g (bar %.3g), supports %s" % (tag, dz, bar, res.support_max))
+    record_margins("iter_ridge/fresh_" + tag, dict(dz=dz, bar=bar, gap=gap))
+    assert res.n_iter == maxiter and res.support_max == i32["support_max"]
+    assert dz <= bar
+    assert abs(res.fval[-1] - f64) / f64 <= f_bar
+
+
+def test_forced_128_blocks_pitched_repeatable_and_refused():
+    from lasso_amd import _native as nat
+    n, d, k, alpha, maxiter = F128[1]
+    x, w, z0, z32, i32, bar = f128_model(n, d, k, alpha, maxiter)[:6]
+    force = nat.FORCE_BLOCKS_128
+    _, a, ra, _ = abi_solve(z0, x, w, alpha, maxiter, reserved=force)
+    _, b, rb, _ = abi_solve(z0, x, w, alpha, maxiter, reserved=force)
+    assert torch.equal(a, b) and ra.fval == rb.fval            # two forced solves are bitwise equal
+    status, zp, rp, bufs = abi_solve(z0, x, w, alpha, maxiter, reserved=force, pitches=(d + 3, k + 1, k + 5, k + 7))
+    assert status == 0 and rp.n_iter == maxiter and rp.support_max == i32["support_max"]
+    dz = float((zp - z32).abs().max())
+    print("pitched f128: max|dz| = %.3g (bar %.3g), against the packed forced solve %.3g" % (dz, bar, float((zp - a).abs().max())))
+    record_margins("iter_ridge/pitched_%dx%dx%d_f128" % (n, d, k), dict(dz=dz, bar=bar))
+    assert dz <= bar                                          # (odd pitches take the scalar loads: another summation order)
+    for key, (buf, src, ld) in bufs.items():                  # inputs and every padding word are as they were
+        rows, cols = (n if key != "w" else d), (d if key == "x" else k)
+        host = buf.cpu()
+        body = host[1:1 + rows * ld].view(rows, ld)
+        fill = 777.0 if src is not None else -555.0
+        assert src is None or torch.equal(body[:, :cols], src), key
+        assert (body[:, cols:] == fill).all() and host[0] == fill and (host[1 + rows * ld:] == fill).all(), key
+    for bad in (force | 1, force | 4, force | (1 << 40)):
+        status, z, _, _ = abi_solve(z0, x, w, alpha, maxiter, reserved=bad)
+        assert status == nat.LASSO_ERR_BAD_ARG and (z == -555.0).all(), bad
