@@ -69,6 +69,8 @@
  *   - the orthant-wise Newton solver is lasso_own_solve: LASSO_F32, any n, d, any pitch, k <= 4096.
  *   - the OWL-QN solver is lasso_owlqn_solve: LASSO_F32, any n, d, k, any pitch, at most 1535 held pairs;
  *     lasso_owlqn_glm_solve is the same solver on the logistic loss (LASSO_GLM_BERNOULLI), same limits and workspace.
+ *   - ISTA / FISTA through a one-layer decoder act(z W^T + b) is lasso_ista_nl_solve: LASSO_F32, any n, d, k, any pitch,
+ *     identity / sigmoid / tanh / ReLU, a fixed step or the per-row power-iteration step.
  *   - the BFGS iterated-ridge solver is lasso_irbfgs_solve: LASSO_F32, any d, any pitch, k <= 1024, a workspace of
  *     2 n k^2 floats (lasso_irbfgs_update is its per-row update kernel on packed operands).
  *   - the iterated-ridge solver is lasso_iter_ridge_solve: LASSO_F32, any n, d, any pitch, k <= 1024.
@@ -1025,6 +1027,69 @@ int lasso_owlqn_glm_solve(const void* x_dev, int64_t ldx, const void* w_dev, int
                           void* z_out_dev, int64_t ldz, int64_t n, int64_t d, int64_t k, int dtype, double alpha,
                           int family, const lasso_owlqn_options* options, lasso_owlqn_result* result,
                           void* workspace_dev, size_t workspace_bytes, void* stream);
+
+/* ---- ISTA / FISTA through a one-layer decoder: replaces ista_nl(), lasso/nonlinear/ista.py:55-128, for
+ * decoder(z) = act(z W^T + b) ----
+ * min_z 0.5 |act(z W^T + b) - x|^2 + alpha |z|_1 by (fast) iterative shrinkage (csrc/ista_nl.hip).  What the reference
+ * takes from autograd has a closed form for this family; with u = y W^T + b and a = act(u), per iteration
+ *   product 1  y W^T; its epilogue stores r = (a - x) act'(u) -- and, lr_auto, c = act'(u)^2 + (a - x) act''(u)
+ *   product 2  r W = the gradient; its epilogue does z_next = softshrink(y - t g, alpha t), the momentum point
+ *              y_next = z_next + ((t_k - 1) / t_{k+1}) (z_next - z) when `fast`, and the block partials of sum |z - z_next|
+ * and u, a and the gradient never exist in memory.  Sigmoid and tanh are evaluated from exp(-|u|) / exp(-2 |u|) alone (no
+ * logit overflows); ReLU's derivative is (u > 0), torch's subgradient.
+ *   bias_dev   : [d], nullable.  W is [d][k] (ldw), torch.nn.Linear's own layout.
+ *   activation : LASSO_ACT_IDENTITY / _SIGMOID / _TANH / _RELU; anything else is LASSO_ERR_UNSUPPORTED before any HIP call.
+ *   options    : maxiter >= 0; fast; lr (the fixed step) or lr_auto != 0: every iteration takes the per-row step
+ *                t_i = 0.98 / L_i, L_i from the reference's power iteration (hessian_2norm, ista.py:26-52) on the row's
+ *                Hessian H_i = W^T diag(c_i) W at the step's point: u <- u0, power_iters times v = normalise(H u),
+ *                u = normalise(H v), then L = v . H u -- 2 power_iters + 1 applications of H, each the same two products
+ *                (the first multiplies by c, the second emits the rows' sums of squares, last the rows' dots; the
+ *                normalisation v / max(|v|, 1e-8) is a per-row scale in the next epilogue, not a pass).  u0_dev [n][k]
+ *                (ldu0) is the start vector, the same at every step (the reference draws a new one at every step);
+ *                required with lr_auto (else LASSO_ERR_BAD_ARG), ignored without.  t_i is torch's `0.98 / L`: the
+ *                reciprocal times 0.98f; a row with H_i = 0 gets inf / NaN, nothing is checked or repaired.  tol: the
+ *                reference's batch-wide rule, sum |z - z_next| <= n k tol in float32, ends the solve with that iteration's
+ *                z_next; tol <= 0 (or NaN) runs maxiter iterations.  Bit 0 of reserved forces 128 x 128 GEMM blocks, as in
+ *                lasso_owlqn_solve (tests); any other bit is LASSO_ERR_BAD_ARG.
+ *   result     : n_iter, stopped (the rule fired), last_delta (the last sum the host read; NaN without one), f0 / f_final
+ *                (the objective of z0 and of z_out; NaN unless trace->loss > 0).  l_dev (IN, nullable, device [n]): with
+ *                lr_auto and n_iter > 0 it receives the L_i of the last step.
+ *   trace      : nullable; host arrays of the caller, `capacity` iterations: deltas (nullable) the sums |z - z_next|;
+ *                loss 0: no objective is computed; 1: f0 and f_final (one more decoder product each); 2: also f[i] =
+ *                the objective of the i-th z_next (one more decoder product per iteration).
+ * The host reads one record per chunk of speculated iterations (csrc/stoprule_host.hpp; a stop inside a chunk is
+ * replayed from the chunk's head, bitwise the state the reference stops in), one per 64 iterations when tol <= 0 with a
+ * trace, none when tol <= 0 without.  The call blocks.  Every sum is folded in double in a fixed order: two solves of
+ * the same arguments give the same bits.  Refusals before any HIP call: null pointers, n < 0, d or k < 1, a leading
+ * dimension below the row length, maxiter < 0, power_iters < 1 with lr_auto are LASSO_ERR_BAD_ARG; a dtype other than
+ * LASSO_F32 is LASSO_ERR_UNSUPPORTED (the workspace query returns 0); a short workspace LASSO_ERR_WORKSPACE.  n = 0 writes
+ * nothing.  The inputs are only read; z_out_dev may not alias one. */
+#define LASSO_ACT_IDENTITY 0
+#define LASSO_ACT_SIGMOID 1
+#define LASSO_ACT_TANH 2
+#define LASSO_ACT_RELU 3
+typedef struct lasso_ista_nl_options {
+  int32_t maxiter, fast, lr_auto, power_iters;
+  double lr, tol;
+  int64_t reserved;
+} lasso_ista_nl_options;
+typedef struct lasso_ista_nl_trace {
+  int32_t capacity;                       /* iterations the arrays below hold */
+  int32_t loss;                           /* 0, 1 or 2: see above */
+  double* deltas;                         /* nullable */
+  double* f;                              /* required with loss == 2 */
+} lasso_ista_nl_trace;
+typedef struct lasso_ista_nl_result {
+  int32_t n_iter, stopped;
+  double last_delta, f0, f_final;
+  void* l_dev;                            /* in: device [n] floats or NULL */
+} lasso_ista_nl_result;
+size_t lasso_ista_nl_workspace_bytes(int64_t n, int64_t d, int64_t k, int dtype, int auto_lr);
+int lasso_ista_nl_solve(const void* x_dev, int64_t ldx, const void* w_dev, int64_t ldw, const void* bias_dev,
+                        const void* z0_dev, int64_t ldz0, void* z_out_dev, int64_t ldz, const void* u0_dev, int64_t ldu0,
+                        int64_t n, int64_t d, int64_t k, int dtype, double alpha, int activation,
+                        const lasso_ista_nl_options* options, lasso_ista_nl_result* result, lasso_ista_nl_trace* trace,
+                        void* workspace_dev, size_t workspace_bytes, void* stream);
 
 /* ---- BFGS iterated ridge: replaces iterative_ridge_bfgs(), lasso/nonlinear/iterative_ridge_bfgs.py:45-140, for
  * f(z) = 0.5 |z W^T - x|^2 ----

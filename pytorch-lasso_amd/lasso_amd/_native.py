@@ -31,6 +31,7 @@ OWN_BRENT, OWN_BACKTRACK, OWN_NONE = 0, 1, 2
 OWN_LS_NOT_CONVERGED, OWN_NONFINITE = 1, 2
 OWLQN_MAX_PAIRS = 1535                                                # most pairs lasso_owlqn_solve holds
 GLM_BERNOULLI = 1                                                     # lasso_owlqn_glm_solve's family
+ACT_IDENTITY, ACT_SIGMOID, ACT_TANH, ACT_RELU = 0, 1, 2, 3               # LASSO_ACT_*: lasso_ista_nl_solve's activation
 IRBFGS_CONVERGED, IRBFGS_NONFINITE = 1, 2
 IRBFGS_MAX_K = 1024                                                   # lasso_batch_solve_tier_cap(LASSO_F32, general)
 IRBFGS_TIME_ROWS = 2                                                  # bit 1 of lasso_irbfgs_options.reserved
@@ -120,6 +121,23 @@ class OwlqnResult(C.Structure):
     _fields_ = [('n_iter', C.c_int32), ('flags', C.c_int32), ('f0', C.c_double), ('f_final', C.c_double),
                 ('ls_failures', C.c_int32), ('reserved', C.c_int32), ('trace', C.POINTER(OwlqnTrace)),
                 ('direction_ms', C.c_double), ('direction_bytes', C.c_double)]
+
+
+class IstaNlOptions(C.Structure):
+    """lasso_ista_nl_options"""
+    _fields_ = [(name, C.c_int32) for name in ('maxiter', 'fast', 'lr_auto', 'power_iters')] + \
+               [('lr', C.c_double), ('tol', C.c_double), ('reserved', C.c_int64)]
+
+
+class IstaNlTrace(C.Structure):
+    """lasso_ista_nl_trace: host arrays of the caller"""
+    _fields_ = [('capacity', C.c_int32), ('loss', C.c_int32), ('deltas', C.POINTER(C.c_double)), ('f', C.POINTER(C.c_double))]
+
+
+class IstaNlResult(C.Structure):
+    """lasso_ista_nl_result"""
+    _fields_ = [('n_iter', C.c_int32), ('stopped', C.c_int32), ('last_delta', C.c_double), ('f0', C.c_double),
+                ('f_final', C.c_double), ('l_dev', C.c_void_p)]
 
 
 class IrbfgsOptions(C.Structure):
@@ -466,6 +484,11 @@ def _declare(lib):
     lib.lasso_owlqn_glm_solve.restype = i32
     lib.lasso_owlqn_glm_solve.argtypes = [vp, i64, vp, i64, vp, i64, vp, i64, i64, i64, i64, i32, dbl, i32,
                                           C.POINTER(OwlqnOptions), C.POINTER(OwlqnResult), vp, sz, vp]
+    lib.lasso_ista_nl_workspace_bytes.restype = sz
+    lib.lasso_ista_nl_workspace_bytes.argtypes = [i64, i64, i64, i32, i32]
+    lib.lasso_ista_nl_solve.restype = i32
+    lib.lasso_ista_nl_solve.argtypes = [vp, i64, vp, i64, vp, vp, i64, vp, i64, vp, i64, i64, i64, i64, i32, dbl, i32,
+                                        C.POINTER(IstaNlOptions), C.POINTER(IstaNlResult), C.POINTER(IstaNlTrace), vp, sz, vp]
     lib.lasso_irbfgs_workspace_bytes.restype = sz
     lib.lasso_irbfgs_workspace_bytes.argtypes = [i64, i64, i64, i32]
     lib.lasso_irbfgs_solve.restype = i32
